@@ -24,6 +24,11 @@ Other BASELINE configurations (not the driver's line; --config):
   c5  64 x (1920 x 1072) BGR frames, 1000 templates    whole match(), FRAME-sharded (rank r takes frames r::N)
 --scaling weak (default: the per-GPU work is fixed) | strong (the total work is fixed and divided over the ranks).
 
+A plain run sets up, picks the launch path, warms up, times --steps steps and prints the headline line; --full adds what
+the line carried before that split: the one-batch-at-a-time figure, the stability and batch-vs-single-frame checks, the
+per-kernel pass and roofline, the strong-scaling estimate, the secondary frames and the CPU baseline (checked against the
+GPU's list).  --dump-outputs DIR writes the match lists of the last timed step (dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -44,6 +49,7 @@ VALU_ISSUE_CEILING = 0.6e12  # wave-instructions per second the chip issues of t
 THRESHOLD = 90.0
 T_LEVELS = (4, 8)
 PREFETCH = 256  # capacity (records) of the per-frame match list exchanged between ranks / sent to the host
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -217,6 +223,31 @@ def cpu_baseline(ts, frame, budget_s: float = 12.0):
     }, last[0]
 
 
+def dump_outputs(out_dir, counts, recs):
+    """--dump-outputs: what the timed path handed its caller in the last step -- every frame's match list -- as float64
+    arrays.  matches.npy [n, 8]: (rank, frame, x, y, similarity, raw, class_idx, template_id), each list sorted by its
+    fields (the order in which a list is appended is not part of the result; duplicates are kept); match_counts.npy
+    [ranks, frames, 2]: (matches, overflow flag).  Rows beyond the 64 MB budget are cut to a fixed, seeded sample."""
+    from shape_based_matching_amd.templates import MATCH_DTYPE
+
+    rows = []
+    for r in range(counts.shape[0]):
+        for b in range(counts.shape[1]):
+            m = np.sort(np.ascontiguousarray(recs[r, b, : counts[r, b, 0]], MATCH_DTYPE), order=list(MATCH_DTYPE.names))
+            a = np.empty((len(m), 8), np.float64)
+            a[:, 0], a[:, 1] = r, b
+            for k, name in enumerate(MATCH_DTYPE.names):
+                a[:, 2 + k] = m[name]
+            rows.append(a)
+    matches = np.concatenate(rows) if rows else np.zeros((0, 8), np.float64)
+    limit = (DUMP_LIMIT_BYTES - counts.size * 8 - 1024) // (8 * 8)
+    if len(matches) > limit:
+        matches = matches[np.sort(np.random.default_rng(0).choice(len(matches), limit, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "matches.npy"), matches)
+    np.save(os.path.join(out_dir, "match_counts.npy"), counts.astype(np.float64))
+
+
 def spawn_ranks(n_gpus):
     """`python3 bench.py --gpus N` without a launcher: start the N ranks ourselves, one process per GPU, BEFORE anything in
     this process imports torch or touches a GPU (a process that has initialised the GPU must not be replaced or forked).
@@ -274,6 +305,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="default: 1000 (case1), 200 (c3), 50 (c5), 10 (c4)")
     ap.add_argument("--warmup", type=int, default=None, help="default: a tenth of the steps")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: one-batch-at-a-time figure, stability checks, per-kernel pass and roofline, "
+                         "strong-scaling estimate, secondary frames, CPU baseline (each of the last three can be turned off "
+                         "below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the match lists of the last timed step to DIR/*.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--force-collective", action="store_true",
@@ -613,6 +650,69 @@ def main():
 
     elapsed = timed(args.warmup, args.steps)
 
+    # what the last timed step handed back: its slot's match lists, in pinned host memory once the step has completed
+    last = active[0][(step_no[0] - 1) % len(active[0])]
+    last_counts, last_recs = last.host_counts(), last.host_records()
+    if (last_counts[:, :, 1] != 0).any() or (last_counts[:, :, 0] > cap).any():
+        raise SystemExit(f"match list overflow: {last_counts.tolist()}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_counts, last_recs)
+
+    total_templates = wl.n_total if wl.maps is not None else ts.n_templates
+    frames_per_step_total = (wl.total_frames if wl.shard == "frames" else B)
+    value = total_templates * (ROWS * COLS / 1e6) * frames_per_step_total * args.steps / elapsed
+    headline = {
+        "metric": "templates*Mpixels/sec (whole Detector::match, frame resident in HBM)" if wl.stage == "match"
+                  else "templates*Mpixels/sec (template loop only, pyramid resident)",
+        "value": value,
+        "unit": "templates*Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": wl.data,
+    }
+    src_ranks = range(world) if wl.shard == "templates" else range(1)
+    cfg = {
+        "workload": wl.desc,
+        "stage": "whole Detector::match per frame" if wl.stage == "match" else "template loop (matchClass) on resident Stage-B pyramids",
+        "templates_total": total_templates,
+        "templates_per_gpu": count,
+        "frame": [ROWS, COLS, CH],
+        "parallelism": ((f"row bands of the build x{n_bands} + " if banded else "")
+                        + (f"template-shard x{world}" if wl.shard == "templates" else f"frame-shard x{world}"))
+                       + (" + RCCL all-gather of match lists" if collective else ""),
+        "frames_per_step": frames_per_step_total,
+        "frames_per_step_per_gpu": B,
+        "us_per_frame": elapsed / args.steps / frames_per_step_total * 1e6,
+        "frames_in_flight": len(active[0]) * B,
+        "input_buffers": len(ring),
+        "launch": launch,
+        "exchange": exchange_path[0],
+        "n_ranks_seen": n_ranks_seen,
+        "hip_runtime": capi.HIP_RUNTIME,  # the process's ONE HIP runtime: "system" or torch's bundled copy (capi.py)
+        # frame 0 of the last step: every rank's list, gathered (frame-sharded: rank 0's first frame)
+        "matches_distinct": len(capi.canonicalize(np.concatenate([last_recs[r, 0, : last_counts[r, 0, 0]] for r in src_ranks]))),
+    }
+
+    def finish(out):
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(out) + "\n").encode())
+        os.close(json_fd)
+        for sl in slots:
+            sl.ctx.close()
+        if collective:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(dict(headline, config=cfg))
+        return
+
     # one step at a time on one stream (latency-bound figure), same K steps, outside the timed region
     if len(slots) > 1:
         slots[0].ctx.set_pipeline_depth(1)  # one batch in flight: latency sizing
@@ -655,9 +755,7 @@ def main():
         if not banded:
             ctx.set_result_mirror(slots[0].h_buf.data_ptr() + HDR, slots[0].h_buf.data_ptr())
     # frame 0 of the step: every rank's list, gathered (frame-sharded: rank 0's first frame)
-    src_ranks = range(world) if wl.shard == "templates" else range(1)
     matches = np.concatenate([recs[r, 0, : counts[r, 0, 0]] for r in src_ranks])
-    n_matches = len(capi.canonicalize(matches.copy()))
 
     # per-kernel durations: a second pass of the same steps on ONE slot (its stream runs the kernels back to back with
     # nothing synchronised in between, so a kernel's duration is its own: with two slots the kernels of the two steps
@@ -856,35 +954,14 @@ def main():
                 traffic = kern.get(dom, {}).get("hbm_traffic_bytes_per_launch")
             except Exception:
                 traffic = None
-        total_templates = wl.n_total if wl.maps is not None else ts.n_templates
-        frames_per_step_total = (wl.total_frames if wl.shard == "frames" else B)
-        value = total_templates * (ROWS * COLS / 1e6) * frames_per_step_total * args.steps / elapsed
-        cfg = {
-            "workload": wl.desc,
-            "stage": "whole Detector::match per frame" if wl.stage == "match" else "template loop (matchClass) on resident Stage-B pyramids",
-            "templates_total": total_templates,
-            "templates_per_gpu": count,
-            "frame": [ROWS, COLS, CH],
-            "parallelism": ((f"row bands of the build x{n_bands} + " if banded else "")
-                            + (f"template-shard x{world}" if wl.shard == "templates" else f"frame-shard x{world}"))
-                           + (" + RCCL all-gather of match lists" if collective else ""),
-            "frames_per_step": frames_per_step_total,
-            "frames_per_step_per_gpu": B,
-            "us_per_frame": elapsed / args.steps / frames_per_step_total * 1e6,
-            "frames_in_flight": len(active[0]) * B,
-            "input_buffers": len(ring),
-            "launch": launch,
-            "exchange": exchange_path[0],
-            "n_ranks_seen": n_ranks_seen,
-            "hip_runtime": capi.HIP_RUNTIME,  # the process's ONE HIP runtime: "system" or torch's bundled copy (capi.py)
+        cfg.update({
             ("ms_per_step_one_frame_at_a_time" if B == 1 else "ms_per_step_one_batch_at_a_time"): single_ms,
             # SURVEY 8d's two times per frame, from the per-kernel pass (kernels alone on one stream):
             # t_match = all kernels, t_templ = the template loop (coarse + refinement) only
             "t_match_kernels_us_per_frame": sum(v["ms_per_step"] for v in kern.values()) * 1e3 / B,
             "t_templ_kernels_us_per_frame": sum(v["ms_per_step"] for k, v in kern.items() if k.startswith("k_similarity")) * 1e3 / B,
-            "matches_distinct": n_matches,
             "coarse_candidates_rank0": n_cand,
-        }
+        })
         frac_by_frame = {}
         if strong:
             cfg["strong_estimate"] = strong
@@ -907,20 +984,7 @@ def main():
                 t = e["kernel_launch_us"].get(dom)
                 if t:
                     frac_by_frame[key] = dom_bytes / (sum(t) / len(t) * 1e-6) / 1e9 / HBM_PEAK_GBS
-        out = {
-            "metric": "templates*Mpixels/sec (whole Detector::match, frame resident in HBM)" if wl.stage == "match"
-                      else "templates*Mpixels/sec (template loop only, pyramid resident)",
-            "value": value,
-            "unit": "templates*Mpixels/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": wl.data,
+        out = dict(headline, **{
             "config": cfg,
             "roofline": {
                 "bound": "hbm",
@@ -957,7 +1021,7 @@ def main():
                                if traffic is not None else None),
             },
             "kernels": kern,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline and wl.stage == "match":
             base_ts = ts.subset(range(first, first + count))
             if base_ts.n_templates > 360:  # a bounded sample of the same workload
@@ -969,13 +1033,7 @@ def main():
                 if capi.canonicalize(np.ascontiguousarray(cpu_list, MATCH_DTYPE).copy()).tobytes() != capi.canonicalize(matches.copy()).tobytes():
                     raise SystemExit("GPU match list of frame 0 differs from the CPU oracle's")
                 out["cpu_baseline"]["gpu_list_equals_cpu_list"] = True
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
-    os.close(json_fd)
-    for sl in slots:
-        sl.ctx.close()
-    if collective:
-        dist.destroy_process_group()
+    finish(out if rank == 0 else None)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT
+from conftest import GOLDEN, ROOT
 from shape_based_matching_amd.templates import read_class_yaml, write_class_yaml
 
 DEMO = os.path.join(ROOT, "shape_based_matching_amd", "sbm_facade_demo")
@@ -29,14 +29,16 @@ def test_cpp_yaml_roundtrip_of_python_written_file(tmp_path, case1):
     assert same(read_class_yaml(out % "test"), ts)
 
 
-@pytest.mark.skipif(not (os.path.exists(DEMO) and os.path.exists(REFERENCE)), reason="needs the demo and the reference tree")
+@pytest.mark.skipif(not os.path.exists(DEMO), reason="facade demo not built")
 @pytest.mark.parametrize("case,name", [(0, "circle"), (1, "test"), (2, "test")])
 def test_cpp_reads_the_reference_yaml_files(tmp_path, case, name):
-    """The reference's own OpenCV-written YAML (test/case*/..._templ.yaml) parsed by the C++ reader."""
+    """The reference's own OpenCV-written YAML (test/case*/..._templ.yaml, kept byte for byte in
+    tests/golden/case*_..._templ.yaml.gz) parsed by the C++ reader."""
     out = str(tmp_path / "%s_out.yaml")
-    r = subprocess.run([DEMO, "convert", f"{REFERENCE}/test/case{case}/%s_templ.yaml", name, out], capture_output=True, text=True)
+    src = os.path.join(GOLDEN, f"case{case}_%s_templ.yaml.gz")
+    r = subprocess.run([DEMO, "convert", src, name, out], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    assert same(read_class_yaml(out % name), read_class_yaml(f"{REFERENCE}/test/case{case}/{name}_templ.yaml"))
+    assert same(read_class_yaml(out % name), read_class_yaml(src % name))
 
 
 @pytest.mark.skipif(not os.path.exists(DEMO), reason="facade demo not built")

@@ -1,10 +1,9 @@
 """Pins of the CPU oracle against material the reference itself holds.
 
 The reference cannot be built here (OpenCV is absent), so the oracle is pinned
-through the reference's own fixtures:
+through the reference's own fixtures (tests/golden/, made by tools/make_fixtures.py):
   * SIMILARITY_LUT (line2Dup.cpp:635): the oracle's closed form is compared with
-    the literal table (digest committed; table re-parsed when the reference
-    tree is present).
+    the literal table (its 256 entries and their digest are committed).
   * test/case1/test_templ.yaml: re-training template 0 from test/case1/train.png
     (test.cpp:262-313) must reproduce all 131 + 71 features, in order; rotating it
     (addTemplate_rotate) must reproduce templates 1..360.  That exercises
@@ -12,12 +11,10 @@ through the reference's own fixtures:
 """
 import hashlib
 import os
-import re
 
 import numpy as np
-import pytest
 
-from conftest import GOLDEN, REFERENCE
+from conftest import GOLDEN
 
 
 def closed_form_lut():
@@ -41,12 +38,11 @@ def test_similarity_lut_digest():
     assert hashlib.sha256(closed_form_lut().tobytes()).hexdigest() == want
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE), reason="reference tree not present")
-def test_similarity_lut_against_reference_source():
-    txt = open(os.path.join(REFERENCE, "line2Dup.cpp")).read()
-    m = re.search(r"SIMILARITY_LUT\[256\]\s*=\s*\{([^}]*)\}", txt)
-    lut3 = int(re.search(r"LUT3\s*=\s*(\d+)\s*;", txt).group(1))
-    vals = np.array([lut3 if t.strip() == "LUT3" else int(t) for t in m.group(1).split(",")], np.uint8)
+def test_similarity_lut_against_stored_reference_table():
+    """the table as the reference's source spells it (LUT3 resolved), stored by tools/make_fixtures.py"""
+    vals = np.load(os.path.join(GOLDEN, "similarity_lut.npy"))
+    assert vals.dtype == np.uint8 and vals.shape == (256,)
+    assert hashlib.sha256(vals.tobytes()).hexdigest() == open(os.path.join(GOLDEN, "similarity_lut.sha256")).read().strip()
     assert np.array_equal(vals, closed_form_lut())
 
 
@@ -112,12 +108,12 @@ def test_fast_atan2_axes(oracle):
         assert abs(oracle.fast_atan2_deg(float(y), float(x)) - want) < 0.35  # fastAtan2's documented accuracy
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE), reason="reference tree not present")
 def test_golden_templates_match_reference_yaml():
+    """the .npz template fixtures against the reference's own YAML files (kept gzipped, byte for byte)"""
     from shape_based_matching_amd.templates import TemplateSet, read_class_yaml
 
     for case, name in ((0, "circle"), (1, "test"), (2, "test")):
-        ts = read_class_yaml(f"{REFERENCE}/test/case{case}/{name}_templ.yaml")
+        ts = read_class_yaml(os.path.join(GOLDEN, f"case{case}_{name}_templ.yaml.gz"))
         g = TemplateSet.load_npz(os.path.join(GOLDEN, f"case{case}_templates.npz"))
         assert np.array_equal(ts.levels, g.levels) and np.array_equal(ts.features, g.features)
         assert ts.class_ids == g.class_ids

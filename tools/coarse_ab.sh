@@ -5,12 +5,12 @@ out=${1:-gpurun_out/coarse_ab}
 mkdir -p "$out"
 for mode in block wave; do
   export SBM_COARSE=$mode
-  python bench.py --no-cpu-baseline --steps 300 --warmup 50 > $out/case1_$mode.json 2>>$out/err.log
-  python bench.py --no-cpu-baseline --steps 300 --warmup 50 --frame tiled --no-extra-frames > $out/tiled_$mode.json 2>>$out/err.log
-  python bench.py --no-cpu-baseline --steps 300 --warmup 50 --batch 1 --no-extra-frames > $out/single_$mode.json 2>>$out/err.log
-  python bench.py --no-cpu-baseline --config c3 --steps 50 --warmup 5 > $out/c3_$mode.json 2>>$out/err.log
-  python bench.py --no-cpu-baseline --config c4 --templates 720 --steps 10 --warmup 2 > $out/c4_$mode.json 2>>$out/err.log
-  python bench.py --no-cpu-baseline --config c5 --steps 20 --warmup 3 > $out/c5_$mode.json 2>>$out/err.log
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 300 --warmup 50 > $out/case1_$mode.json 2>>$out/err.log || exit $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 300 --warmup 50 --frame tiled --no-extra-frames > $out/tiled_$mode.json 2>>$out/err.log || exit $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 300 --warmup 50 --batch 1 --no-extra-frames > $out/single_$mode.json 2>>$out/err.log || exit $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --config c3 --steps 50 --warmup 5 > $out/c3_$mode.json 2>>$out/err.log || exit $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --config c4 --templates 720 --steps 10 --warmup 2 > $out/c4_$mode.json 2>>$out/err.log || exit $?
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --config c5 --steps 20 --warmup 3 > $out/c5_$mode.json 2>>$out/err.log || exit $?
   echo "$mode done"
 done
 python - "$out" <<'PY'

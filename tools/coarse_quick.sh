@@ -2,10 +2,10 @@
 # quick look at the coarse pass on the bench workloads (GPU box).  usage: tools/coarse_quick.sh <outdir>
 out=${1:-gpurun_out/cq}
 mkdir -p "$out"
-python bench.py --no-cpu-baseline --steps 300 --warmup 50 > $out/case1.json 2>>$out/err.log
-python bench.py --no-cpu-baseline --steps 300 --warmup 50 --frame tiled --no-extra-frames > $out/tiled.json 2>>$out/err.log
-python bench.py --no-cpu-baseline --config c3 --steps 50 --warmup 5 > $out/c3.json 2>>$out/err.log
-python bench.py --no-cpu-baseline --config c5 --steps 20 --warmup 3 > $out/c5.json 2>>$out/err.log
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 300 --warmup 50 > $out/case1.json 2>>$out/err.log || exit $?
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --steps 300 --warmup 50 --frame tiled --no-extra-frames > $out/tiled.json 2>>$out/err.log || exit $?
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --config c3 --steps 50 --warmup 5 > $out/c3.json 2>>$out/err.log || exit $?
+timeout -k 10 600 python bench.py --full --no-cpu-baseline --config c5 --steps 20 --warmup 3 > $out/c5.json 2>>$out/err.log || exit $?
 python - "$out" <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(sys.argv[1] + "/*.json")):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""print the essentials of bench.py JSON lines: value, step time, per-kernel launch times, secondary frames"""
+"""print the essentials of `bench.py --full` JSON lines: value, step time, per-kernel launch times, secondary frames"""
 import json
 import sys
 

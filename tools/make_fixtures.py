@@ -10,8 +10,13 @@ Every output is DATA held by the reference's tests, re-encoded compactly:
   case0_circle_bgr.npz       <- test/case0/templ/circle.png (the training image of test.cpp:scale_test)
   case0_info_scales.npy      <- the `scale:` values of test/case0/circle_info.yaml (float32)
   similarity_lut.sha256      <- digest of the 256 SIMILARITY_LUT entries (line2Dup.cpp:635)
+  similarity_lut.npy         <- the 256 SIMILARITY_LUT entries themselves (uint8)
+  case0_circle_templ.yaml.gz, case1_test_templ.yaml.gz, case2_test_templ.yaml.gz
+                             <- test/case*/{circle,test}_templ.yaml byte for byte, gzipped (the OpenCV-written
+                                files the YAML readers are checked against)
 No reference source text is copied.
 """
+import gzip
 import hashlib
 import os
 import re
@@ -60,6 +65,17 @@ def main():
     lut = parse_similarity_lut(f"{REF}/line2Dup.cpp")
     with open(f"{OUT}/similarity_lut.sha256", "w") as fh:
         fh.write(hashlib.sha256(lut.tobytes()).hexdigest() + "\n")
+    reference_data_fixtures()
+
+
+def reference_data_fixtures():
+    """the reference's template YAML files and its similarity table, kept as they are (gzip without name or time stamp,
+    so that re-running this leaves the files unchanged)"""
+    for case, name in ((0, "circle"), (1, "test"), (2, "test")):
+        raw = open(f"{REF}/test/case{case}/{name}_templ.yaml", "rb").read()
+        with open(f"{OUT}/case{case}_{name}_templ.yaml.gz", "wb") as fh, gzip.GzipFile("", "wb", 9, fh, mtime=0) as gz:
+            gz.write(raw)
+    np.save(f"{OUT}/similarity_lut.npy", parse_similarity_lut(f"{REF}/line2Dup.cpp"))
 
 
 if __name__ == "__main__":
