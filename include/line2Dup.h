@@ -229,6 +229,15 @@ public:
     std::vector<std::vector<Match>> matchBatch(const std::vector<cv::Mat>& sources, float threshold,
                                                const std::vector<std::string>& class_ids = std::vector<std::string>(),
                                                const cv::Mat mask = cv::Mat()) const;
+    /* matchBatchNMS: matchBatch followed by what every reference caller runs next (test.cpp:470-491,
+     *   test_jabil.cpp:128-148): boxes Rect(m.x, m.y, templ[0].width, templ[0].height) and cv_dnn::NMSBoxes(boxes, scores,
+     *   score_threshold, nms_threshold, idx, eta, top_k).  Element f is match(sources[f], ...) taken at the indices NMSBoxes
+     *   returns for it, in that order; the epilogue and the NMS run on the device (sbm_match_batch_host_end_nms).  Same
+     *   threading contract as matchBatch. */
+    std::vector<std::vector<Match>> matchBatchNMS(const std::vector<cv::Mat>& sources, float threshold,
+                                                  const std::vector<std::string>& class_ids, float score_threshold,
+                                                  float nms_threshold, float eta = 1.f, int top_k = 0,
+                                                  const cv::Mat mask = cv::Mat()) const;
     void matchAsync(const std::vector<cv::Mat>& sources, float threshold,
                     const std::vector<std::string>& class_ids = std::vector<std::string>(), const cv::Mat mask = cv::Mat()) const;
     std::vector<std::vector<Match>> wait() const;

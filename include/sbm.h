@@ -286,6 +286,50 @@ int sbm_match_batch_device_banded(sbm_ctx* ctx, const void* d_imgs, int64_t fram
  * duplicates.  Host-side, in place; returns the new count. */
 int64_t sbm_canonicalize(sbm_match_rec* recs, int64_t n);
 
+/* ---- match epilogue + NMS on the device ------------------------------------
+ * What every reference caller does with Detector::match's list: build Rect(m.x, m.y, templ[0].width, templ[0].height)
+ * per match and run cv_dnn::NMSBoxes(boxes, scores, score_threshold, nms_threshold, idx) (include/nms.hpp; test.cpp:491,
+ * test_jabil.cpp:148).  For one frame, over the union of its stored records in every part:
+ *   1. the epilogue Detector::match applies (line2Dup.cpp:1142-1145), exactly as the facade returns it: sort by
+ *      (similarity desc, template_id asc, class_idx asc, y asc, x asc) (sbm_canonicalize's order), then drop a record
+ *      equal to its predecessor in (x, y, similarity, class_idx) (Match::operator== under std::unique, which also drops
+ *      exact duplicates);
+ *   2. NMSBoxes on that list with nms.hpp's arithmetic: keep similarity > score_threshold; if top_k > 0 the first top_k;
+ *      greedy walk keeping a box iff its overlap (integer areas, double Jaccard, 1 - (float)distance, 1 when both boxes
+ *      are empty) with every kept box is <= the threshold, the threshold multiplied by eta after each kept box while
+ *      eta < 1 and it is > 0.5.  A record's box is (x, y, w0, h0), w0 / h0 the level-0 size of the uploaded template
+ *      labelled (class_idx, template_id);
+ *   3. output: the kept records in walk order (a subsequence of the epilogue list).
+ * nms_threshold = 1, score_threshold < 0, top_k = 0 keeps every record (an overlap is at most 1): the call is then the
+ * device form of Detector::match's epilogue alone.
+ *
+ * Layout: n_parts blocks part_stride bytes apart; in block p frame f's records are at d_recs + p * part_stride +
+ * f * cap * 24 and its {n_matches, overflow} int32 pair at d_counts + p * part_stride + 8 * f.  Producers:
+ *   sbm_match_batch_device: n_parts = 1 (part_stride unused);  sbm_match_device: n_frames = 1 (d_counts: its count, the
+ *   overflow word next to it must be zero);  the gathered buffer of sbm_match_{batch_,}device_sharded: d_counts =
+ *   d_gathered, d_recs = d_gathered + header, part_stride = one shard, n_parts = world (the sharded merge).
+ * Output: frame f's kept records at d_out + f * out_cap (records), {n_kept, flags} at d_out_counts + 2 * f (int32).
+ * flags: bit 0 a part overflowed (count > cap or overflow word != 0; the stage ran on the stored records), bit 1
+ * n_kept > out_cap (the first out_cap are stored), bit 2 a record that entered the walk carries a label no uploaded
+ * template has (its box is empty).
+ * Stream-ordered and safe to capture: steady-state calls never synchronise, allocate or read device memory from the
+ * host.  The first call after a template upload builds the label -> size table, and a call with a larger
+ * n_parts * cap (> 2048 records per frame take global scratch) grows the scratch; both synchronise the device (the rule of
+ * sbm_match_batch_device).  Labels that are not unique within the upload: SBM_ERR_INVALID. */
+typedef struct sbm_nms_params {
+    float score_threshold;
+    float nms_threshold;
+    float eta;     /* 1 = fixed threshold */
+    int32_t top_k; /* 0 = all */
+} sbm_nms_params;
+int sbm_nms_batch_device(sbm_ctx* ctx, const void* d_recs, const void* d_counts, int64_t cap, int32_t n_frames,
+                         int32_t n_parts, int64_t part_stride, const sbm_nms_params* p, void* d_out, int64_t out_cap,
+                         void* d_out_counts, void* stream);
+/* The host-batch sibling of sbm_match_batch_host_end: enqueues the stage above over the pending batch's device lists and
+ * copies back only the kept records: frame f's at out + f * out_cap, {n_kept, flags} at counts + 2 * f.  Ends the batch
+ * as _end does.  SBM_ERR_CAPACITY when some frame has flag bit 0 or 1 (its stored records are still returned). */
+int sbm_match_batch_host_end_nms(sbm_ctx* ctx, const sbm_nms_params* p, sbm_match_rec* out, int64_t out_cap, int32_t* counts);
+
 /* ---- pyramid state ------------------------------------------------------
  * sbm_build_pyramid: the first half of match() (line2Dup.cpp:1084-1120):
  * quantizedOrientations -> [pyrDown -> quantizedOrientations]* -> per level

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_host", "sbm_match_batch_host_begin", "sbm_match_batch_host_end", "sbm_extract_local_maxima",
     "sbm_set_pipeline_depth", "sbm_set_coarse_mode", "sbm_set_refine_order", "sbm_set_refine_bits", "sbm_get_coarse_bitplanes",
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
+    "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
 ]
 
 
@@ -44,6 +45,16 @@ class SbmConfig(C.Structure):
         ("weak_threshold", C.c_float),
         ("device_id", C.c_int32),
         ("max_candidates", C.c_int64),
+    ]
+
+
+class SbmNmsParams(C.Structure):
+    """sbm_nms_params: cv_dnn::NMSBoxes' arguments (include/nms.hpp)"""
+    _fields_ = [
+        ("score_threshold", C.c_float),
+        ("nms_threshold", C.c_float),
+        ("eta", C.c_float),
+        ("top_k", C.c_int32),
     ]
 
 
@@ -203,6 +214,8 @@ def lib() -> C.CDLL:
     L.sbm_pin_host_buffer.argtypes = [vp, vp, i64]
     L.sbm_unpin_host_buffer.argtypes = [vp, vp]
     L.sbm_match_batch_device_banded.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp, i32, vp]
+    L.sbm_nms_batch_device.argtypes = [vp, vp, vp, i64, i32, i32, i64, C.POINTER(SbmNmsParams), vp, i64, vp, vp]
+    L.sbm_match_batch_host_end_nms.argtypes = [vp, C.POINTER(SbmNmsParams), vp, i64, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("sbm_last_error", "sbm_destroy", "sbm_canonicalize"):
@@ -308,6 +321,34 @@ class Context:
                                             channels, C.c_void_p(d_mask) if d_mask else None, C.c_float(threshold),
                                             C.c_void_p(d_out), cap, C.c_void_p(d_counts),
                                             C.c_void_p(stream) if stream else None))
+
+    def nms_batch_device(self, d_recs: int, d_counts: int, cap: int, n_frames: int, d_out: int, out_cap: int, d_out_counts: int,
+                         score_threshold: float, nms_threshold: float, eta: float = 1.0, top_k: int = 0, n_parts: int = 1,
+                         part_stride: int = 0, stream: int = 0):
+        """match epilogue + NMSBoxes per frame on the device (sbm_nms_batch_device): part p, frame f's records at
+        d_recs + p*part_stride + f*cap*24 bytes, its {n, overflow} at d_counts + p*part_stride + 8*f; frame f's kept
+        records at d_out + f*out_cap records, {n_kept, flags} at d_out_counts + 2*f int32."""
+        prm = SbmNmsParams(score_threshold, nms_threshold, eta, top_k)
+        _check(lib().sbm_nms_batch_device(self._h, C.c_void_p(d_recs), C.c_void_p(d_counts), cap, n_frames, n_parts, part_stride,
+                                          C.byref(prm), C.c_void_p(d_out) if d_out else None, out_cap, C.c_void_p(d_out_counts),
+                                          C.c_void_p(stream) if stream else None))
+
+    def match_batch_host_nms(self, frames: Sequence[np.ndarray], threshold: float, score_threshold: float, nms_threshold: float,
+                             eta: float = 1.0, top_k: int = 0, cap: int = 1024, out_cap: int = 256, sub_batch: int = 0,
+                             mask: Optional[np.ndarray] = None):
+        """sbm_match_batch_host_begin + sbm_match_batch_host_end_nms: per frame the NMS-kept records (a list of record
+        arrays) and the {n_kept, flags} pairs"""
+        arrs = [_img(f) for f in frames]
+        r, c, ch = arrs[0][1:]
+        assert all(a[1:] == (r, c, ch) for a in arrs)
+        ptrs = (C.c_void_p * len(arrs))(*[a[0].ctypes.data for a in arrs])
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = np.zeros((len(arrs), out_cap), MATCH_DTYPE)
+        counts = np.zeros((len(arrs), 2), np.int32)
+        prm = SbmNmsParams(score_threshold, nms_threshold, eta, top_k)
+        _check(lib().sbm_match_batch_host_begin(self._h, ptrs, len(arrs), r, c, c * ch, ch, _p(m), C.c_float(threshold), cap, sub_batch))
+        _check(lib().sbm_match_batch_host_end_nms(self._h, C.byref(prm), _p(out), out_cap, _p(counts)))
+        return [out[f, : counts[f, 0]].copy() for f in range(len(arrs))], counts
 
     def set_result_mirror(self, mirror_out: int, mirror_count: int):
         """Device-visible (e.g. pinned host) addresses that receive a copy of every result."""

@@ -20,6 +20,7 @@
 #include "sbm_kernels.h"
 #include "sbm_quantize_stream.h"
 #include "sbm_train_kernels.h"
+#include "sbm_nms_kernels.h"
 
 using namespace sbm;
 
@@ -28,3 +29,4 @@ using namespace sbm;
 #include "sbm_capi_match.inc"   // the match entry points of include/sbm.h
 #include "sbm_capi_stages.inc"  // stage entry points, profiling
 #include "sbm_capi_multi.inc"   // RCCL, sharded / banded steps, sbm_match_sharded
+#include "sbm_capi_nms.inc"     // match epilogue + NMS on the device

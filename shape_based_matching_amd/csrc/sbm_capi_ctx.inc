@@ -216,6 +216,15 @@ struct sbm_ctx {
         int64_t cap = 0;
     } pending;
     DevBuf d_scratch;
+    // match epilogue + NMS (sbm_nms_batch_device): (class_idx, template_id) -> level-0 size table of the upload it was
+    // built from (templates_gen), the scratch of frames whose lists exceed LDS, the host batch's kept lists
+    uint64_t templates_gen = 0;
+    uint64_t nms_labels_gen = ~(uint64_t)0;
+    int nms_n_labels = 0;
+    bool nms_labels_unique = true;
+    DevBuf d_nms_labels, d_nms_scratch, d_nms_out;
+    int32_t* h_nms_counts = nullptr;
+    int h_nms_counts_frames = 0;
 
     // hipGraph cache for sbm_match_device (one captured graph per distinct argument tuple)
     struct GraphEntry {

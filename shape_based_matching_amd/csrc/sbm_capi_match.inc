@@ -71,6 +71,7 @@ void sbm_destroy(sbm_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_res_count) (void)hipHostFree(c->h_res_count);
+    if (c->h_nms_counts) (void)hipHostFree(c->h_nms_counts);
     c->drop_graphs();
     for (int l = 0; l < SBM_MAX_LEVELS; ++l)
         if (c->ev_fork[l]) (void)hipEventDestroy(c->ev_fork[l]);
@@ -79,7 +80,7 @@ void sbm_destroy(sbm_ctx* c)
     c->clear_timings();
     DevBuf* singles[] = {&c->d_tls, &c->d_fxy, &c->d_flabel, &c->d_flevel, &c->d_foff, &c->d_class, &c->d_tid, &c->d_active, &c->d_citems, &c->d_cfoff, &c->d_soff, &c->d_soffbase, &c->d_fxy_s, &c->d_flabel_s, &c->d_fcls,
                          &c->d_rawmin, &c->d_rawkeep, &c->d_geo, &c->d_cands, &c->d_counters, &c->d_out, &c->d_outcount,
-                         &c->d_scratch, &c->d_blm};
+                         &c->d_scratch, &c->d_blm, &c->d_nms_labels, &c->d_nms_scratch, &c->d_nms_out};
     for (DevBuf* b : singles) b->release();
     for (int l = 0; l < SBM_MAX_LEVELS; ++l) {
         c->d_img[l].release();
@@ -190,6 +191,7 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
     c->h_tid.swap(tid);
     c->have_thr = false;
     c->foff_dirty = true;
+    ++c->templates_gen;
     c->drop_graphs();
     return sbm_select_classes(c, nullptr, 0);
 }

@@ -10,6 +10,9 @@
 //       test.cpp:scale_test("train") (test.cpp:170-203): shapeInfo_producer::src_of / mask_of (cv::resize) + addTemplate
 //   demo nms <templ_fmt> <class_id> <image> <threshold> <num_features> [pad]
 //       test.cpp:noise_test (test.cpp:455-491): match, boxes from templ[0].width/height, NMSBoxes(boxes, scores, 0, 0.5f)
+//   demo nmsbatch <templ_fmt> <class_id[,class_id...]> <image> <threshold> <num_features> <n_frames> <score_thr> <nms_thr> <eta> <top_k>
+//       Detector::matchBatchNMS over n_frames copies of the image shifted 8 f columns (wrapping): the epilogue and
+//       NMSBoxes on the device; prints every frame's kept matches in NMS order
 //   demo latency <templ_fmt> <class_id> <image> <threshold> <num_features> <n> [pad]
 //       n timed calls of detector.match(img, threshold, ids) on one cv::Mat, as a test.cpp-style caller sees them
 //       also: the same call with the frame buffer pinned (Detector::pinBuffer) and matchBatch from pinned host frames
@@ -151,6 +154,47 @@ int main(int argc, char** argv)
                 printf("m %d %d %u %d %d %d\n", matches[i].x, matches[i].y, bits, matches[i].template_id, boxes[i].width, boxes[i].height);
             }
             for (int idx : idxs) printf("k %d\n", idx);
+            return 0;
+        }
+        if (mode == "nmsbatch") {
+            if (argc < 12) return usage();
+            const std::string fmt = argv[2], path = argv[4];
+            std::vector<std::string> ids;
+            for (const char* p = argv[3]; *p;) {
+                const char* q = p;
+                while (*q && *q != ',') ++q;
+                ids.push_back(std::string(p, q));
+                p = *q ? q + 1 : q;
+            }
+            const float threshold = (float)atof(argv[5]);
+            const int num_features = atoi(argv[6]), nf = atoi(argv[7]);
+            const float score_thr = (float)atof(argv[8]), nms_thr = (float)atof(argv[9]), eta = (float)atof(argv[10]);
+            const int top_k = atoi(argv[11]);
+            line2Dup::Detector detector(num_features, {4, 8});
+            detector.readClasses(ids, fmt);
+            Mat test_img = imread(path, IMREAD_UNCHANGED);
+            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
+            Mat img = test_img(Rect(0, 0, 16 * (test_img.cols / 16), 16 * (test_img.rows / 16))).clone();
+            std::vector<Mat> frames;
+            const int esz = img.channels();
+            for (int b = 0; b < nf; ++b) {
+                Mat f(img.rows, img.cols, img.type());
+                const int sh = (8 * b) % img.cols;
+                for (int y = 0; y < img.rows; ++y) {
+                    memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
+                    memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
+                }
+                frames.push_back(f);
+            }
+            const auto kept = detector.matchBatchNMS(frames, threshold, ids, score_thr, nms_thr, eta, top_k);
+            for (size_t f = 0; f < kept.size(); ++f) {
+                printf("frame %zu kept %zu\n", f, kept[f].size());
+                for (const auto& m : kept[f]) {
+                    uint32_t bits;
+                    memcpy(&bits, &m.similarity, 4);
+                    printf("k %d %d %u %s %d\n", m.x, m.y, bits, m.class_id.c_str(), m.template_id);
+                }
+            }
             return 0;
         }
         if (mode == "latency") {

@@ -7,6 +7,7 @@
 // file:line in ddcr/shape_based_matching).
 #include "../../include/line2Dup.h"
 #include "../../include/sbm.h"
+#include "../../include/nms.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -806,6 +807,106 @@ std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sou
         for (size_t f : redo) {
             const int64_t k = match_on_lane(single, sources[f], mask8, threshold);
             out[f] = to_matches(*flat, single.recs.data(), k);
+        }
+    }
+    return out;
+}
+
+// the NMS-kept records of one frame (already in epilogue order, walk order kept) as Matches
+static std::vector<Match> kept_to_matches(const Detector::Engine::Flat& flat, const sbm_match_rec* recs, int64_t n)
+{
+    std::vector<Match> matches;
+    matches.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        matches.push_back(Match(recs[i].x, recs[i].y, recs[i].similarity, flat.class_order[(size_t)recs[i].class_idx], recs[i].template_id));
+    return matches;
+}
+
+std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                                        float score_threshold, float nms_threshold, float eta, int top_k, const Mat mask) const
+{
+    if (sources.empty()) return std::vector<std::vector<Match>>();
+    const Mat& s0 = sources[0];
+    for (const Mat& m : sources) {
+        CV_Assert(!m.empty() && m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3));
+        CV_Assert(m.rows == s0.rows && m.cols == s0.cols && m.channels() == s0.channels() && m.step == s0.step);
+    }
+    CV_Assert(mask.empty() || (mask.size() == s0.size() && mask.type() == CV_8UC1));
+    Engine& e = *eng_;
+    LaneLease lease{&e, acquire_lane(e)};
+    const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
+    const std::shared_ptr<const Engine::Flat> flat = prepare_lane(*this, e, lease.idx, devs, class_templates, pyramid_levels, T_at_level,
+                                                                  modality->weak_threshold, class_ids, s0.rows, s0.cols, false);
+    std::vector<std::vector<Match>> out(sources.size());
+    if (!flat) return out;
+    Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
+    Mat mask8;
+    if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
+    const int D = (int)lane.ctxs.size(), n = (int)sources.size();
+    const int64_t cap = 1024, out_cap = cap; // the kept list is a subsequence of the raw list: out_cap = cap always fits
+    sbm_nms_params prm;
+    prm.score_threshold = score_threshold;
+    prm.nms_threshold = nms_threshold;
+    prm.eta = eta;
+    prm.top_k = top_k;
+    std::vector<int> first, count;
+    for (int d = 0; d < D; ++d) {
+        first.push_back((int)((int64_t)n * d / D));
+        count.push_back((int)((int64_t)n * (d + 1) / D) - first.back());
+    }
+    int begun = 0, bad = 0;
+    std::string msg;
+    for (int d = 0; d < D && !bad; ++d, ++begun) {
+        if (!count[d]) continue;
+        std::vector<const uint8_t*> ptrs;
+        for (int f = 0; f < count[d]; ++f) ptrs.push_back(sources[first[d] + f].data);
+        const int rc = sbm_match_batch_host_begin(lane.ctxs[d], ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(),
+                                                  mask8.empty() ? nullptr : mask8.data, threshold, cap, 0);
+        if (rc) {
+            bad = rc;
+            msg = std::string("sbm_match_batch_host_begin: ") + sbm_last_error();
+            break;
+        }
+    }
+    std::vector<size_t> redo;
+    for (int d = 0; d < begun; ++d) { // every context that began must end, whatever happened since
+        if (!count[d]) continue;
+        std::vector<sbm_match_rec> recs((size_t)count[d] * out_cap);
+        std::vector<int32_t> cnt((size_t)count[d] * 2);
+        const int rc = bad ? sbm_match_batch_host_end(lane.ctxs[d], recs.data(), cnt.data())
+                           : sbm_match_batch_host_end_nms(lane.ctxs[d], &prm, recs.data(), out_cap, cnt.data());
+        if (rc && rc != SBM_ERR_CAPACITY) {
+            if (!bad) {
+                bad = rc;
+                msg = std::string("sbm_match_batch_host_end_nms: ") + sbm_last_error();
+            }
+            continue;
+        }
+        if (bad) continue;
+        for (int f = 0; f < count[d]; ++f) { // flags 1 | 2: the raw list did not fit the batch's capacity
+            if (cnt[2 * f + 1] & 3) redo.push_back((size_t)(first[d] + f));
+            else out[(size_t)(first[d] + f)] = kept_to_matches(*flat, recs.data() + (size_t)f * out_cap, cnt[2 * f]);
+        }
+    }
+    if (bad) CV_Error(bad == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, msg);
+    if (!redo.empty()) {
+        // such frames are matched again one at a time (match() grows its buffer), then the reference's own loop: boxes of
+        // the level-0 template sizes and NMSBoxes (nms.hpp)
+        Engine::Lane single;
+        single.ctxs.assign(1, lane.ctxs[0]);
+        for (size_t f : redo) {
+            const int64_t k = match_on_lane(single, sources[f], mask8, threshold);
+            const std::vector<Match> all = to_matches(*flat, single.recs.data(), k);
+            std::vector<Rect> boxes;
+            std::vector<float> scores;
+            for (const Match& m : all) {
+                const std::vector<Template>& templ = class_templates.at(m.class_id)[(size_t)m.template_id];
+                boxes.push_back(Rect(m.x, m.y, templ[0].width, templ[0].height));
+                scores.push_back(m.similarity);
+            }
+            std::vector<int> idx;
+            cv_dnn::NMSBoxes(boxes, scores, score_threshold, nms_threshold, idx, eta, top_k);
+            for (int i : idx) out[f].push_back(all[(size_t)i]);
         }
     }
     return out;
