@@ -8,16 +8,16 @@
  * (shape_based_matching_amd/) never links, imports or calls it.
  *
  * Pinning status (details in DESIGN.md "Oracle"):
- *   - The reference cannot be built in this image (it needs OpenCV 4, absent),
- *     so this restatement is not checked against a compiled reference.
+ *   - The reference's gradient half cannot be built in this image (it needs
+ *     OpenCV 4, absent); its match half is (oracle/ref_match.mk).
  *   - computeResponseMaps: pinned against the literal SIMILARITY_LUT table.
  *   - quantizedOrientations / hysteresisGradient / pyrDown / extractTemplate /
  *     selectScatteredFeatures / cropTemplates / addTemplate_rotate: pinned by
  *     re-training the reference's committed template fixtures (test/case1,
  *     test/case2 template YAMLs) from the reference's training images.
  *   - spread / linearize / similarity* / matchClass: restated line by line from
- *     the source; the reference holds no golden vector for them:
- *     PARITY UNPINNED for these stages beyond the end-to-end case runs.
+ *     the source; pinned bit for bit against the reference's own line2Dup.cpp
+ *     compiled on stand-in headers (tests/test_reference_match_half.py).
  *
  * All citations are file:line in ddcr/shape_based_matching.
  */

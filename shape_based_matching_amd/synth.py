@@ -172,3 +172,25 @@ def embed(img: np.ndarray, rows: int, cols: int, top: int, left: int) -> np.ndar
     out = np.zeros(shape, np.uint8)
     out[top : top + img.shape[0], left : left + img.shape[1]] = img
     return out
+
+
+def templates_from_maps(qs, nf, box, n_templates, seed):
+    """templates cut out of the frame's own orientation maps (so each scores 100 where it was cut): nf[l] of the set
+    pixels of level l inside the box, at a random even offset"""
+    rs = np.random.RandomState(seed)
+    rows, cols = qs[0].shape
+    pyramids, got = [], [10 ** 9] * len(qs)
+    for t in range(n_templates):
+        px = 64 + (rs.randint(0, cols - box - 128) // 4) * 4
+        py = 64 + (rs.randint(0, rows - box - 128) // 4) * 4
+        tp = []
+        for l, q in enumerate(qs):
+            w = box >> l
+            sub = q[(py >> l) : (py >> l) + w + 1, (px >> l) : (px >> l) + w + 1]
+            ys, xs = np.nonzero(sub)
+            pick = rs.permutation(len(ys))[: nf[l]]
+            f = np.stack([xs[pick], ys[pick], np.log2(sub[ys[pick], xs[pick]]).astype(np.int64)], axis=1)
+            got[l] = min(got[l], len(pick))
+            tp.append({"width": w, "height": w, "tl_x": 0, "tl_y": 0, "pyramid_level": l, "features": f})
+        pyramids.append(tp)
+    return from_pyramids(pyramids, "cut"), got

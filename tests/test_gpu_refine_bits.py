@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from shape_based_matching_amd import capi, synth
+from shape_based_matching_amd.synth import templates_from_maps
 from shape_based_matching_amd.templates import MATCH_DTYPE
 
 pytestmark = pytest.mark.gpu
@@ -85,30 +86,6 @@ def test_geometries(oracle, ctx_form, case1, rows, cols):
         ctx = ctx_form(bits)
         ctx.upload_templates(ts)
         assert multiset(ctx.match(img, 70.0)) == want, (bits, rows, cols)
-
-
-def templates_from_maps(qs, nf, box, n_templates, seed):
-    """templates cut out of the frame's own orientation maps (so each scores 100 where it was cut): nf[l] of the set
-    pixels of level l inside the box, at a random even offset"""
-    from shape_based_matching_amd.templates import from_pyramids
-
-    rs = np.random.RandomState(seed)
-    rows, cols = qs[0].shape
-    pyramids, got = [], [10 ** 9] * len(qs)
-    for t in range(n_templates):
-        px = 64 + (rs.randint(0, cols - box - 128) // 4) * 4
-        py = 64 + (rs.randint(0, rows - box - 128) // 4) * 4
-        tp = []
-        for l, q in enumerate(qs):
-            w = box >> l
-            sub = q[(py >> l) : (py >> l) + w + 1, (px >> l) : (px >> l) + w + 1]
-            ys, xs = np.nonzero(sub)
-            pick = rs.permutation(len(ys))[: nf[l]]
-            f = np.stack([xs[pick], ys[pick], np.log2(sub[ys[pick], xs[pick]]).astype(np.int64)], axis=1)
-            got[l] = min(got[l], len(pick))
-            tp.append({"width": w, "height": w, "tl_x": 0, "tl_y": 0, "pyramid_level": l, "features": f})
-        pyramids.append(tp)
-    return from_pyramids(pyramids, "cut"), got
 
 
 @pytest.mark.parametrize("nf,box", [([100, 40], 200), ([124, 60], 200), ([125, 61], 200), ([600, 200], 400), ([1020, 500], 500),

@@ -14,6 +14,12 @@ Every output is DATA held by the reference's tests, re-encoded compactly:
   case0_circle_templ.yaml.gz, case1_test_templ.yaml.gz, case2_test_templ.yaml.gz
                              <- test/case*/{circle,test}_templ.yaml byte for byte, gzipped (the OpenCV-written
                                 files the YAML readers are checked against)
+With --ref, only:
+  ref_match_case1.npz        <- what the reference's own match half (oracle/_ref/ref_match_avx2, built by
+                                oracle/ref_match.mk) computes on the case1 test frame's quantized maps: matchClass's raw
+                                list and match()'s epilogue list at three thresholds, and the SHA-256 of one level's
+                                linear memories.  The maps (from the oracle's gradient stage) and the template subset
+                                are stored with it, so the GPU suite can hold the HIP kernels to it without the binary.
 No reference source text is copied.
 """
 import gzip
@@ -78,5 +84,32 @@ def reference_data_fixtures():
     np.save(f"{OUT}/similarity_lut.npy", parse_similarity_lut(f"{REF}/line2Dup.cpp"))
 
 
+def ref_match_fixture():
+    import hashlib
+
+    from oracle import oracle as O
+    from oracle import ref_match as R
+    from shape_based_matching_amd import synth
+    from shape_based_matching_amd.templates import TemplateSet
+
+    img = np.load(f"{OUT}/case1_test_bgr.npz")["bgr"]
+    pyr = O.Pyramid.build(synth.embed(img, 640, 768, 40, 60), [4, 8], 30.0)
+    qs = [pyr.quantized(0), pyr.quantized(1)]
+    idx = np.arange(0, 361, 3, dtype=np.int32)
+    ts = R.dense_ids(TemplateSet.load_npz(f"{OUT}/case1_templates.npz").subset(idx))
+    thresholds = [60.0, 75.0, 90.0]
+    out = {"q0": qs[0], "q1": qs[1], "template_index": idx, "thresholds": np.asarray(thresholds, np.float32)}
+    with R.Reference(qs, [4, 8], ts, "avx2") as ref:
+        out["lm_level"] = np.int32(1)
+        out["lm_sha256"] = np.array(hashlib.sha256(ref.lm()[1].tobytes()).hexdigest())
+        for k, thr in enumerate(thresholds):
+            out[f"raw{k}"], out[f"epi{k}"] = ref.match(thr)
+            print(f"ref_match_case1: threshold {thr}: {len(out[f'raw{k}'])} raw, {len(out[f'epi{k}'])} after the epilogue")
+    np.savez_compressed(f"{OUT}/ref_match_case1.npz", **out)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--ref"]:
+        ref_match_fixture()
+    else:
+        main()
