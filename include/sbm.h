@@ -92,7 +92,10 @@ int sbm_partition_templates(sbm_ctx* ctx, int32_t rows, int32_t cols, const int3
  * channels (BGR order as cv::imread gives), row stride in bytes; mask (rows x
  * cols, non-zero = keep) may be NULL.  rows/cols must satisfy the reference's
  * preconditions at every level (rows_l % T_l == 0, cols_l % T_l == 0,
- * (rows_l * cols_l) % 16 == 0; line2Dup.cpp:639, :751-752) else SBM_ERR_INVALID. */
+ * (rows_l * cols_l) % 16 == 0; line2Dup.cpp:639, :751-752) else SBM_ERR_INVALID.
+ * The host-memory entry points (sbm_match, sbm_match_batch_host*, sbm_build_pyramid, sbm_set_quantized,
+ * sbm_match_templates, the stage reads) are ordered after every device entry point enqueued before them on a caller's
+ * stream: the first one after such a call waits for the device. */
 int sbm_match(sbm_ctx* ctx, const uint8_t* img_host, int32_t rows, int32_t cols, int32_t stride,
               int32_t channels, const uint8_t* mask_host, float threshold, sbm_match_rec* out_host,
               int64_t cap, int64_t* n_out);

@@ -183,6 +183,7 @@ struct sbm_ctx {
     DevBuf d_geo; // T[L], W[L], H[L] as int32 then stride[L] as int64
     bool foff_dirty = true;
     bool counters_fresh = false; // the linear-memory launch of this frame already reset the counters
+    bool caller_work = false;    // a device entry point has enqueued on a caller's stream since the last device-wide wait
 
     // candidates / results
     DevBuf d_cands, d_counters, d_out, d_outcount;
@@ -951,6 +952,18 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     if (all_rows) // every level's linear memories (and the counter reset) in one launch
         if (int e = launch_lm(0, c->L - 1, true)) return e;
     c->levels_valid = c->L;
+    return 0;
+}
+
+// The host-memory entry points (sbm_match, sbm_match_batch_host*, sbm_build_pyramid, sbm_set_quantized,
+// sbm_match_templates, sbm_get_quantized) reuse the context's buffers on its own stream, which does not wait for a caller's
+// stream: a device entry point enqueued there just before may still be writing the same orientation maps, linear memories
+// and counters.  Only after such a call, wait for the device once; contexts that never see a caller's stream pay nothing.
+int order_after_caller_work(sbm_ctx* c)
+{
+    if (!c->caller_work) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    c->caller_work = false;
     return 0;
 }
 

@@ -293,6 +293,7 @@ int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, 
     if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (s != c->stream) c->caller_work = true;
     // anything the launches below are about to change may still be read by frames in flight
     const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L) ||
                        !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty;
@@ -322,7 +323,9 @@ int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, 
         c->lm_full[l] = true;
         c->lm_compact[l] = false;
     }
-    c->blm_valid = coarse_on_bits(c); // ... and packs the coarsest level's bit planes from them when the coarse pass reads bits
+    // ... and packs the coarsest level's bit planes from them when the coarse pass reads bits -- inside the coarse pass,
+    // which an empty template selection skips
+    c->blm_valid = coarse_on_bits(c) && !c->h_active.empty();
     return 0;
 }
 
@@ -336,6 +339,7 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
     if (n_frames > 1 && frame_stride < (int64_t)stride * rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (s != c->stream) c->caller_work = true;
     const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L &&
                          n_frames <= c->batch) ||
                        !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty;
@@ -370,7 +374,8 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
                 c->lm_compact[c->L - 1] = form == 2;
                 c->lm_strip[c->L - 1] = c->lm_bits[c->L - 1] = false;
             }
-            c->blm_valid = coarse_on_bits(c);
+            // (the bit planes of the 8-plane form are packed by the coarse pass, which an empty selection skips)
+            c->blm_valid = coarse_on_bits(c) && (coarse_build_form(c) != 0 || !c->h_active.empty());
             return 0;
         }
     }
@@ -384,6 +389,7 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
     if (!c || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (s != c->stream) c->caller_work = true;
     if (!c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty) HIP_TRY(hipDeviceSynchronize());
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (graph_wanted(c, -1)) {
@@ -391,9 +397,11 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
         // may synchronise or launch only now and then runs first, outside the capture
         if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
         if (int e = prepare_templates(c, s, threshold, cap)) return e;
-        if (int e = ensure_coarse_planes(c, c->stream)) return e;
-        if (int e = ensure_local_forms(c, c->stream)) return e;
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        // the forms rebuilt here read the orientation maps that the caller's stream may still be writing (a match call
+        // enqueued just before): launched on s, as enqueue_templates does, they are ordered after it without a host wait.
+        // (prepare_templates has synchronised the context's stream whenever it enqueued anything.)
+        if (int e = ensure_coarse_planes(c, s)) return e;
+        if (int e = ensure_local_forms(c, s)) return e;
         uint32_t thr_bits;
         memcpy(&thr_bits, &threshold, 4);
         const sbm_ctx::GraphEntry key{nullptr, c->rows[0], c->cols[0], 0, 0, nullptr, thr_bits, d_out, cap, d_count,
@@ -504,6 +512,7 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     for (int f = 0; f < n_frames; ++f)
         if (!frames[f]) return fail(SBM_ERR_INVALID, "frame %d is null", f);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     int sub = std::max(1, std::min(sub_batch > 0 ? sub_batch : 8, n_frames));
     {
         const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L && sub <= c->batch) ||
@@ -712,6 +721,7 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
 {
     if (!c || (!out && cap > 0) || !n_out) return fail(SBM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     bool l0_done = false;
     if (int e = upload_image_banded(c, img, rows, cols, stride, channels, mask, &l0_done)) return e;
@@ -797,6 +807,7 @@ int sbm_build_pyramid(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols
 {
     if (!c) return fail(SBM_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (int e = upload_image(c, img, rows, cols, stride, channels, mask)) return e;
     if (int e = enqueue_pyramid(c, c->stream, c->d_img[0].as<uint8_t>(), cols * channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr)) return e;
@@ -810,6 +821,7 @@ int sbm_set_quantized(sbm_ctx* c, int32_t level, const uint8_t* q, int32_t rows,
     if (!c || !q || level < 0 || level >= c->L) return fail(SBM_ERR_INVALID, "bad level");
     if (level > c->levels_valid) return fail(SBM_ERR_STATE, "levels must be set from 0 upwards");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     if (int e = ensure_level(c, level, rows, cols)) return e;
     if (c->profiling && !c->profiling_keep && level == 0) c->clear_timings();
     HIP_TRY(hipMemcpyAsync(c->d_quant[level].p, q, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
@@ -829,6 +841,7 @@ int sbm_get_quantized(sbm_ctx* c, int32_t level, uint8_t* out)
 {
     if (!c || !out || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, c->d_quant[level].p, (size_t)c->rows[level] * c->cols[level], hipMemcpyDeviceToHost));
     return 0;
@@ -874,6 +887,7 @@ int sbm_match_templates(sbm_ctx* c, float threshold, sbm_match_rec* out, int64_t
 {
     if (!c || (!out && cap > 0) || !n_out) return fail(SBM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (int e = enqueue_templates(c, c->stream, threshold, c->d_out.as<sbm_match_rec>(), c->cand_cap, c->d_outcount.as<int32_t>())) return e;
     int rc = fetch_results(c, c->stream, out, cap, n_out);
