@@ -18,6 +18,7 @@
 
 #include "../../include/sbm.h"
 #include "sbm_kernels.h"
+#include "sbm_level_forms.h"
 #include "sbm_quantize_stream.h"
 #include "sbm_train_kernels.h"
 #include "sbm_nms_kernels.h"

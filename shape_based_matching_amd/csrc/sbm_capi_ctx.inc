@@ -171,14 +171,12 @@ struct sbm_ctx {
     // planes, each lm_stride bits in the byte planes' flat order -- what the coarse pass reads (2 bits per position and
     // orientation instead of a byte)
     DevBuf d_blm;
-    bool blm_valid = false; // d_blm matches the coarsest level's current linear memories
-    bool lm_full[SBM_MAX_LEVELS]{}, lm_compact[SBM_MAX_LEVELS]{}; // which form of level l is current (frame 0 .. batch)
-    bool lm_strip[SBM_MAX_LEVELS]{}; // the compact plane of level l is strip-interleaved (lm_strip_offset)
     // Round 4: a T = 4 strip level that a match entry point builds is stored as BIT STRIPS instead (2 bits per cell and
-    // orientation, build_lm_strip4_allty) and refined by k_similarity_local<3> (sbm_local_bits.h).  lm_bits[l]: d_lbits[l]
-    // holds the current form of level l (with lm_compact[l] and lm_strip[l] set; d_lmc[l] is then stale).
+    // orientation, build_lm_strip4_allty) and refined by k_similarity_local_bits (sbm_local_bits.h)
     DevBuf d_lbits[SBM_MAX_LEVELS];
-    bool lm_bits[SBM_MAX_LEVELS]{};
+    // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
+    // (sbm_level_forms.h; per level, not per frame: the forms rebuilt on demand cover frame 0 only)
+    LevelForms forms[SBM_MAX_LEVELS];
     int refine_bits = -1; // sbm_set_refine_bits: -1 the process default (SBM_LOCAL_BITS, else on), 0 bytes, 1 bits
     DevBuf d_geo; // T[L], W[L], H[L] as int32 then stride[L] as int64
     bool foff_dirty = true;
@@ -399,11 +397,10 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             if (c->cfg.T[l] == 4)
                 if (int e = c->d_lbits[l].ensure(B * lbits_frame_bytes(c, l), true)) return e;
         }
-        c->lm_full[l] = c->lm_compact[l] = c->lm_strip[l] = c->lm_bits[l] = false;
+        c->forms[l].forget();
     }
     c->d_blm.release(); // fresh, zeroed: the tails of the bit planes must read as 0 too
     if (int e = c->d_blm.ensure(B * 2 * c->lm_stride[c->L - 1] + 256, true)) return e;
-    c->blm_valid = false;
     if (B > (size_t)c->batch) { // per-frame candidate lists and counters
         if (int e = c->d_cands.ensure(B * c->cand_cap * sizeof(Cand))) return e;
         c->d_counters.release();
@@ -430,11 +427,10 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
     if (int e = c->d_lm[l].ensure((size_t)8 * c->lm_stride[l], true)) return e;
     c->d_lmc[l].release();
     c->d_lbits[l].release();
-    c->lm_full[l] = c->lm_compact[l] = c->lm_bits[l] = false;
+    c->forms[l].forget();
     if (l == c->L - 1) {
         c->d_blm.release();
         if (int e = c->d_blm.ensure((size_t)2 * c->lm_stride[l] + 256, true)) return e;
-        c->blm_valid = false;
     }
     c->foff_dirty = true;
     // This level now holds ONE frame of a geometry the other per-level buffers (next level's image, mask, compact
@@ -595,50 +591,75 @@ bool lm_rows_ok(const uint8_t* d_q, int cols, int T)
     return (T == 4 || T == 8) && ((cols / T) & 3) == 0 && (cols & 15) == 0 && (((uintptr_t)d_q) & 15) == 0;
 }
 
-bool use_compact_lm() { return !tuning().full_lm; }
-
-int launch_build_lm(sbm_ctx* c, hipStream_t s, const uint8_t* d_q, int rows, int cols, int T, uint8_t* d_lm, int64_t lm_stride);
-
-// 8-plane linear memories of level l (frame 0) for the stage entry points, expanded from the compact plane if needed
-int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
+// every level takes the one-launch builder k_build_lm_rows
+bool all_rows_ok(const sbm_ctx* c)
 {
-    if (c->lm_full[l]) return 0;
-    const int T = c->cfg.T[l];
-    if (!c->lm_compact[l]) {
-        // the coarsest level after a match call that built its bit planes only: the 8 response planes of frame 0 from the
-        // orientation map, which is still resident
-        if (l != c->L - 1 || !c->blm_valid) return 0;
-        if (int e = launch_build_lm(c, s, c->d_quant[l].as<uint8_t>(), c->rows[l], c->cols[l], T, c->d_lm[l].as<uint8_t>(), c->lm_stride[l])) return e;
-        c->lm_full[l] = true;
-        return 0;
+    for (int l = 0; l < c->L; ++l)
+        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l])) return false;
+    return true;
+}
+
+// what the form of every level's linear memories follows from (sbm_level_forms.h)
+PlanInputs plan_inputs(const sbm_ctx* c)
+{
+    PlanInputs p;
+    p.L = c->L;
+    for (int l = 0; l < c->L; ++l) {
+        p.T[l] = c->cfg.T[l];
+        p.rows[l] = c->rows[l];
+        p.cols[l] = c->cols[l];
+        p.has_spread[l] = c->d_lmc[l].p != nullptr;
+        p.has_bit_strips[l] = c->d_lbits[l].p != nullptr;
     }
-    if (c->lm_bits[l]) { // bit strips: the 8 response planes of frame 0 from the orientation map, as above
-        if (int e = launch_build_lm(c, s, c->d_quant[l].as<uint8_t>(), c->rows[l], c->cols[l], T, c->d_lm[l].as<uint8_t>(), c->lm_stride[l])) return e;
-        c->lm_full[l] = true;
-        return 0;
-    }
-    const int64_t n = (int64_t)T * T * (c->cols[l] / T) * (c->rows[l] / T);
-    hipLaunchKernelGGL(k_expand_lm, dim3((unsigned)std::min<int64_t>((n / 4 + 255) / 256, 4096)), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(), n,
-                       c->d_lm[l].as<uint8_t>(), c->lm_stride[l], c->lm_strip[l] ? 1 : 0, c->cols[l] / T, c->rows[l] / T);
+    p.has_bit_planes = c->d_blm.p != nullptr;
+    p.coarse_mode = c->coarse_mode;
+    p.refine_bits = c->refine_bits;
+    p.have_thr = c->have_thr;
+    p.thr = c->thr_cached;
+    p.full_lm = tuning().full_lm;
+    p.strip_lm = tuning().strip_lm;
+    p.lm_allty = tuning().lm_allty;
+    p.fused_bits = tuning().fused_bits;
+    p.local_bits = tuning().local_bits;
+    return p;
+}
+bool coarse_on_bits(const sbm_ctx* c) { return coarse_on_bits(plan_inputs(c)); }
+
+// One level's share of a k_build_lm_rows launch that makes it in form f, from block `begin` on; *blocks: its 256-thread blocks
+LmLevelArgs lm_level_args(const sbm_ctx* c, int l, LmForm f, int frames, int begin, int* blocks)
+{
+    const int T = c->cfg.T[l], W = c->cols[l] / T, H = c->rows[l] / T;
+    const int64_t stride = c->lm_stride[l];
+    // few frames: shorter, more numerous work items
+    const LmWork w = lm_work(f, T, c->rows[l], W, H, frames < 4 ? LM_FULL_SPLIT : 1, tuning().lm_allty);
+    uint8_t* const lm = f == LM_PLANES8 ? c->d_lm[l].as<uint8_t>() : f == LM_BIT_PLANES ? c->d_blm.as<uint8_t>()
+                      : f == LM_BIT_STRIPS ? c->d_lbits[l].as<uint8_t>() : c->d_lmc[l].as<uint8_t>();
+    const int64_t lm_fs = f == LM_BIT_STRIPS ? lbits_frame_bytes(c, l) : (f == LM_PLANES8 ? 8 : f == LM_BIT_PLANES ? 2 : 1) * stride;
+    *blocks = (int)((w.items + 255) / 256);
+    return LmLevelArgs{c->d_quant[l].as<uint8_t>(), lm, stride, c->rows[l], c->cols[l], W, H, T, begin, (int64_t)c->rows[l] * c->cols[l], lm_fs, f, w.split, w.allty};
+}
+
+// level l alone (frame 0) in form f through the one-launch builder
+int launch_lm_level(sbm_ctx* c, hipStream_t s, int l, LmForm f)
+{
+    LmArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_levels = 1;
+    int blocks = 0;
+    a.lv[0] = lm_level_args(c, l, f, 1, 0, &blocks);
+    SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
-    c->lm_full[l] = true;
     return 0;
 }
 
-int launch_build_lm(sbm_ctx* c, hipStream_t s, const uint8_t* d_q, int rows, int cols, int T, uint8_t* d_lm,
-                    int64_t lm_stride)
+// the 8 response planes of level l (frame 0) from its resident orientation map
+int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
 {
-    const int W = cols / T, H = rows / T;
-    if (lm_rows_ok(d_q, cols, T)) {
-        LmArgs a;
-        memset(&a, 0, sizeof a);
-        a.n_levels = 1;
-        a.lv[0] = LmLevelArgs{d_q, d_lm, lm_stride, rows, cols, W, H, T, 0, 0, 0, 0, LM_FULL_SPLIT, 0};
-        const int64_t items = (int64_t)rows * (W >> 2) * LM_FULL_SPLIT;
-        SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
+    const uint8_t* d_q = c->d_quant[l].as<uint8_t>();
+    uint8_t* d_lm = c->d_lm[l].as<uint8_t>();
+    const int rows = c->rows[l], cols = c->cols[l], T = c->cfg.T[l], W = cols / T, H = rows / T;
+    const int64_t lm_stride = c->lm_stride[l];
+    if (lm_rows_ok(d_q, cols, T)) return launch_lm_level(c, s, l, LM_PLANES8);
     if (T <= 8) {
         const int tw = LM_GX * T, lw = tw + T - 1, lwp = (lw + 3) & ~3, lh = 2 * T - 1;
         const size_t smem = (size_t)lh * lwp + (size_t)lh * tw + (size_t)T * T * LM_GX;
@@ -659,6 +680,23 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, const uint8_t* d_q, int rows, int
     for (int o = 0; o < 8; ++o)
         hipLaunchKernelGGL(k_linearize, dim3(blocks), dim3(256), 0, s, maps + o * n, rows, cols, T, d_lm + o * lm_stride);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// 8-plane linear memories of level l (frame 0) for the stage entry points: expanded from the spread plane, or -- a level held
+// as bit strips or bit planes only -- from the orientation map, which is still resident
+int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
+{
+    const LmForm src = full_lm_source(c->forms[l]);
+    if (src == LM_PLANES8 || src == LM_NONE) return 0;
+    if (src == LM_SPREAD || src == LM_SPREAD_STRIP) {
+        const int T = c->cfg.T[l];
+        const int64_t n = (int64_t)T * T * (c->cols[l] / T) * (c->rows[l] / T);
+        hipLaunchKernelGGL(k_expand_lm, dim3((unsigned)std::min<int64_t>((n / 4 + 255) / 256, 4096)), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(), n,
+                           c->d_lm[l].as<uint8_t>(), c->lm_stride[l], src == LM_SPREAD_STRIP ? 1 : 0, c->cols[l] / T, c->rows[l] / T);
+        HIP_TRY(hipGetLastError());
+    } else if (int e = launch_build_lm(c, s, l)) return e;
+    c->forms[l].planes8 = true;
     return 0;
 }
 
@@ -753,45 +791,6 @@ int ensure_citems(sbm_ctx* c, hipStream_t s)
     return 0;
 }
 
-// Form of level l's linear memories when the one-launch builder makes them: the refinement-only levels are ONE plane of
-// spread bytes (compact), strip-interleaved when the grid width allows it (the refinement pass reads 16 x 16 cells per
-// feature: 2 - 4 cache lines instead of 16)
-void lm_form(const sbm_ctx* c, int l, bool* compact, bool* strip)
-{
-    const bool strip_ok = tuning().strip_lm;
-    *compact = l < c->L - 1 && c->d_lmc[l].p && use_compact_lm();
-    *strip = *compact && strip_ok && ((c->cols[l] / c->cfg.T[l]) & 15) == 0;
-}
-
-// ... and as bit strips when a match entry point builds a T = 4 strip level with the all-ty threads (sbm_local_bits.h)
-bool local_bits_wanted(const sbm_ctx* c, int l)
-{
-    const int mode = c->refine_bits >= 0 ? c->refine_bits : (tuning().local_bits >= 0 ? tuning().local_bits : 1);
-    const int T = c->cfg.T[l];
-    return l < c->L - 1 && use_compact_lm() && tuning().strip_lm && tuning().lm_allty && mode != 0 && T == 4 && ((c->cols[l] / T) & 15) == 0;
-}
-bool local_on_bits(const sbm_ctx* c, int l) { return local_bits_wanted(c, l) && c->d_lmc[l].p && c->d_lbits[l].p; }
-
-// the coarse pass of the current threshold runs on bit planes (sbm_coarse_bits.h): every raw_min >= 1, mode auto or bits
-bool coarse_on_bits(const sbm_ctx* c) { return (c->coarse_mode == 0 || c->coarse_mode == 3) && c->have_thr && c->thr_cached >= 0.f && c->d_blm.p; }
-
-// ... and the one-launch builder can make them directly (a wave's 256 positions must not straddle two sub-planes)
-bool build_bits_only(const sbm_ctx* c)
-{
-    const int lc = c->L - 1, Tc = c->cfg.T[lc];
-    const int64_t WHc = (int64_t)(c->cols[lc] / Tc) * (c->rows[lc] / Tc);
-    return coarse_on_bits(c) && (WHc & 255) == 0 && tuning().fused_bits;
-}
-
-// How a match entry point builds the coarsest level: 0 the 8 response planes (the bit planes, if the coarse pass reads them,
-// are packed from those), 1 bit planes only, inside the linear-memory launch, 2 one plane of spread bytes + k_pack_bitplanes_spread
-int coarse_build_form(const sbm_ctx* c)
-{
-    if (!coarse_on_bits(c) || !tuning().fused_bits) return 0;
-    if (build_bits_only(c)) return 1;
-    return c->d_lmc[c->L - 1].p ? 2 : 0;
-}
-
 // gradient stage + linear memories for every level; d_img0 may be external
 // reset_count != null: the linear-memory launch also zeroes the per-frame counters and *reset_count
 // (c->counters_fresh tells enqueue_coarse to skip its own k_reset launch).
@@ -831,83 +830,12 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     const uint8_t* img = d_img0;
     int stride = stride0;
     const uint8_t* mask = d_mask0;
-    bool all_rows = true;
-    for (int l = 0; l < c->L; ++l) all_rows = all_rows && lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l]);
+    const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
-    c->blm_valid = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
-    // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch (compact == 3 in k_build_lm_rows).
-    // The stage entry points keep the 8 response planes (the bit planes are then packed from them on demand).
-    const int lc_form = all_rows && reset_count ? coarse_build_form(c) : 0;
-    const bool bits_lc = lc_form == 1;
-    // linear memories of levels lo .. hi in one launch (block ranges coarsest level first: its blocks -- T * 8 / 4 stores per
-    // lane -- are the long ones, and a launch that dispatches its long blocks last ends with a few of them running alone);
-    // with_reset: the launch also zeroes the per-frame counters and *reset_count
-    auto launch_lm = [&](int lo, int hi, bool with_reset) -> int {
-        LmArgs a;
-        memset(&a, 0, sizeof a);
-        a.n_levels = hi - lo + 1;
-        int blocks = 0;
-        for (int l = hi; l >= lo; --l) {
-            const int T = c->cfg.T[l], W = c->cols[l] / T, H = c->rows[l] / T;
-            bool compact, strip;
-            lm_form(c, l, &compact, &strip);
-            if (l == c->L - 1 && bits_lc) {
-                // the coarsest level as 16 bit planes only (2 bytes per pixel instead of 8 response planes)
-                a.lv[l - lo] = LmLevelArgs{c->d_quant[l].as<uint8_t>(), c->d_blm.as<uint8_t>(), c->lm_stride[l], c->rows[l], c->cols[l], W, H, T,
-                                           blocks, (int64_t)c->rows[l] * c->cols[l], (int64_t)2 * c->lm_stride[l], 3, 1, 0};
-                c->lm_compact[l] = c->lm_strip[l] = c->lm_full[l] = false;
-                c->blm_valid = true;
-                blocks += (int)(((int64_t)c->rows[l] * (W >> 2) + 255) / 256);
-                continue;
-            }
-            if (l == c->L - 1 && lc_form == 2) {
-                // ... or as one plane of spread bytes, row-major (the flat order of the byte planes), packed into the bit planes below
-                a.lv[l - lo] = LmLevelArgs{c->d_quant[l].as<uint8_t>(), c->d_lmc[l].as<uint8_t>(), c->lm_stride[l], c->rows[l], c->cols[l], W, H, T,
-                                           blocks, (int64_t)c->rows[l] * c->cols[l], c->lm_stride[l], 1, 1, 0};
-                c->lm_compact[l] = true;
-                c->lm_strip[l] = c->lm_full[l] = c->lm_bits[l] = false;
-                blocks += (int)(((int64_t)c->rows[l] * (W >> 2) + 255) / 256);
-                continue;
-            }
-            const int split = frames < 4 ? LM_FULL_SPLIT : 1; // few frames: shorter, more numerous work items
-            const int allty = strip && T == 4 && tuning().lm_allty ? 1 : 0;
-            const bool bits_l = reset_count && local_on_bits(c, l); // a match entry point: the level as bit strips
-            if (bits_l)
-                a.lv[l - lo] = LmLevelArgs{c->d_quant[l].as<uint8_t>(), c->d_lbits[l].as<uint8_t>(), c->lm_stride[l], c->rows[l], c->cols[l], W, H, T,
-                                           blocks, (int64_t)c->rows[l] * c->cols[l], lbits_frame_bytes(c, l), 4, split, 1};
-            else
-            a.lv[l - lo] = LmLevelArgs{c->d_quant[l].as<uint8_t>(), compact ? c->d_lmc[l].as<uint8_t>() : c->d_lm[l].as<uint8_t>(),
-                                       c->lm_stride[l], c->rows[l], c->cols[l], W, H, T, blocks, (int64_t)c->rows[l] * c->cols[l],
-                                       (int64_t)(compact ? 1 : 8) * c->lm_stride[l], strip ? 2 : (compact ? 1 : 0), split, allty};
-            c->lm_compact[l] = compact;
-            c->lm_strip[l] = strip;
-            c->lm_bits[l] = bits_l;
-            c->lm_full[l] = !compact;
-            const int64_t items = bits_l    ? (int64_t)((W + 31) >> 5) * ((H + 31) >> 5) * 256
-                                  : allty   ? (int64_t)((W + 63) >> 6) * ((H + 15) >> 4) * 256
-                                  : strip   ? (int64_t)((W + 63) >> 6) * ((H + 15) >> 4) * T * 256
-                                  : compact ? (int64_t)c->rows[l] * (W >> 2)
-                                            : (int64_t)c->rows[l] * (W >> 2) * split;
-            blocks += (int)((items + 255) / 256);
-        }
-        if (with_reset && reset_count) {
-            a.counters = c->d_counters.as<int32_t>();
-            a.out_count = reset_count;
-            c->counters_fresh = true;
-        }
-        SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
-        HIP_TRY(hipGetLastError());
-        if (hi == c->L - 1 && lc_form == 2) {
-            const int l = c->L - 1;
-            const int n_dwords = (int)(((int64_t)c->rows[l] * c->cols[l] + 31) / 32);
-            SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
-                       c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
-            HIP_TRY(hipGetLastError());
-            c->blm_valid = true;
-        }
-        return 0;
-    };
+    // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch, and its T = 4 strip levels as bit strips.
+    // The stage entry points keep the 8 response planes there (the bit planes are then packed from them on demand).
+    const BuildPlan plan = plan_build(plan_inputs(c), all_rows, reset_count != nullptr);
     // (the linear memories of a level right behind its gradient launch -- two launches per batch, the orientation map still
     // in the caches -- measure the same as one launch for all levels at the end: tools/r03_lm_early.sh)
     for (int l = 0; l < c->L; ++l) {
@@ -939,18 +867,36 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
                 return e;
         }
         if (!all_rows && frames > 1) return fail(SBM_ERR_INVALID, "batched match needs T in {4, 8} and 16-column-aligned levels");
-        if (!all_rows) {
-            if (int e = launch_build_lm(c, s, c->d_quant[l].as<uint8_t>(), c->rows[l], c->cols[l], c->cfg.T[l],
-                                        c->d_lm[l].as<uint8_t>(), c->lm_stride[l]))
-                return e;
-            c->lm_full[l] = true;
-            c->lm_compact[l] = false;
-        }
+        if (!all_rows)
+            if (int e = launch_build_lm(c, s, l)) return e;
     }
     if (bands && bands->between)
         if (int e = bands->between(c, s, frames)) return e;
-    if (all_rows) // every level's linear memories (and the counter reset) in one launch
-        if (int e = launch_lm(0, c->L - 1, true)) return e;
+    if (all_rows) {
+        // every level's linear memories in one launch (block ranges coarsest level first: its blocks -- T * 8 / 4 stores per
+        // lane -- are the long ones, and a launch that dispatches its long blocks last ends with a few of them running alone),
+        // which also zeroes the per-frame counters and *reset_count
+        LmArgs a;
+        memset(&a, 0, sizeof a);
+        a.n_levels = c->L;
+        int blocks = 0;
+        for (int l = c->L - 1, n = 0; l >= 0; --l, blocks += n) a.lv[l] = lm_level_args(c, l, plan.form[l], frames, blocks, &n);
+        if (reset_count) {
+            a.counters = c->d_counters.as<int32_t>();
+            a.out_count = reset_count;
+            c->counters_fresh = true;
+        }
+        SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        if (plan.pack_spread) { // the spread plane is row-major, the flat order of the byte planes
+            const int l = c->L - 1;
+            const int n_dwords = (int)(((int64_t)c->rows[l] * c->cols[l] + 31) / 32);
+            SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
+                       c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    record_build(c->forms, c->L, plan);
     c->levels_valid = c->L;
     return 0;
 }
@@ -967,6 +913,23 @@ int order_after_caller_work(sbm_ctx* c)
     return 0;
 }
 
+// the stream a device entry point launches on: the caller's (remembered for order_after_caller_work), else the context's
+hipStream_t launch_stream(sbm_ctx* c, void* stream)
+{
+    if (stream && (hipStream_t)stream != c->stream) c->caller_work = true;
+    return stream ? (hipStream_t)stream : c->stream;
+}
+
+// the template tables of this threshold are not resident yet: frames in flight may still read the ones about to change
+bool templates_dirty(const sbm_ctx* c, float threshold) { return !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty; }
+
+// ... or the geometry, the batch size or the pyramid are about to change
+bool match_dirty(const sbm_ctx* c, int rows, int cols, int channels, int frames, float threshold)
+{
+    return !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L && frames <= c->batch) ||
+           templates_dirty(c, threshold);
+}
+
 // host-side preparation of the template loop: validation, integer thresholds, feature offsets.
 // May synchronise (only when something changed); never called inside a stream capture.
 // The tables are (re)built on the CONTEXT's stream and that stream is synchronised by the host, whatever stream the
@@ -981,21 +944,26 @@ int prepare_templates(sbm_ctx* c, hipStream_t, float threshold, int64_t cap)
     return ensure_citems(c, c->stream);
 }
 
+// the coarsest level's bit planes (of `frames` frames) packed from its 8 response planes
+int pack_bitplanes(sbm_ctx* c, hipStream_t s, int frames)
+{
+    const int lc = c->L - 1, T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
+    if (!c->forms[lc].planes8) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", lc);
+    const int n_dwords = (int)(((int64_t)T * T * W * H + 31) / 32);
+    SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes, dim3((n_dwords + 255) / 256, 8, frames), dim3(256), 0, s, c->d_lm[lc].as<uint8_t>(),
+               c->lm_stride[lc], (int64_t)8 * c->lm_stride[lc], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[lc]) / 4, n_dwords);
+    HIP_TRY(hipGetLastError());
+    c->forms[lc].bit_planes = true;
+    return 0;
+}
+
 // What the coarse pass of the current threshold reads, made current outside any capture: the bit planes packed from the
 // response planes (stage entry points: the pyramid was set level by level), or the response planes rebuilt after a
 // bits-only build when a byte kernel is asked for.
 int ensure_coarse_planes(sbm_ctx* c, hipStream_t s)
 {
-    const int lc = c->L - 1, T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
-    if (!coarse_on_bits(c)) return c->lm_full[lc] ? 0 : ensure_full_lm(c, lc, s);
-    if (c->blm_valid) return 0;
-    if (!c->lm_full[lc]) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", lc);
-    const int n_dwords = (int)(((int64_t)T * T * W * H + 31) / 32);
-    SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes, dim3((n_dwords + 255) / 256, 8, 1), dim3(256), 0, s, c->d_lm[lc].as<uint8_t>(),
-               c->lm_stride[lc], (int64_t)8 * c->lm_stride[lc], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[lc]) / 4, n_dwords);
-    HIP_TRY(hipGetLastError());
-    c->blm_valid = true;
-    return 0;
+    if (!coarse_on_bits(c)) return ensure_full_lm(c, c->L - 1, s);
+    return c->forms[c->L - 1].bit_planes ? 0 : pack_bitplanes(c, s, 1);
 }
 
 // coarse pass over the active templates (reset + k_similarity_coarse; single-level pyramids emit here)
@@ -1029,8 +997,9 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
         }
         // Round 4: the bit-plane kernel (sbm_coarse_bits.h) whenever every raw_min is >= 1 (threshold >= 0: positions past
         // a template's span are never candidates); SBM_COARSE / sbm_set_coarse_mode pick a byte kernel instead.
-        const bool bits = coarse_on_bits(c);
-        if (!bits && !c->lm_full[lc]) {
+        const PlanInputs pin = plan_inputs(c);
+        const bool bits = coarse_on_bits(pin);
+        if (!bits && !c->forms[lc].planes8) {
             // a byte kernel after a match call that built the bit planes only (the stage entry point with a threshold < 0)
             if (frames > 1) return fail(SBM_ERR_STATE, "the coarsest level's response planes are not built");
             if (int e = ensure_full_lm(c, lc, s)) return e;
@@ -1038,14 +1007,8 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
         int max_nf = 0, bits_dw = 1;
         if (bits) {
             for (int32_t t : c->h_active) max_nf = std::max(max_nf, c->h_tls[(size_t)t * L + lc].nf);
-            if (!c->blm_valid) {
-                if (!c->lm_full[lc]) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", lc);
-                const int n_dwords = (int)(((int64_t)T * T * W * H + 31) / 32);
-                SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes, dim3((n_dwords + 255) / 256, 8, frames), dim3(256), 0, s,
-                           c->d_lm[lc].as<uint8_t>(), c->lm_stride[lc], (int64_t)8 * c->lm_stride[lc], c->d_blm.as<uint32_t>(),
-                           (int64_t)(2 * c->lm_stride[lc]) / 4, n_dwords);
-                c->blm_valid = true;
-            }
+            if (coarse_packs_planes(pin, c->forms[lc], false))
+                if (int e = pack_bitplanes(c, s, frames)) return e;
             chunks = std::max(1, (std::min(std::max(bits_max_npos, 0), W * H) + CB_POS - 1) / CB_POS);
             // Two dwords (64 positions) per lane -- half as many, twice as long work items -- when the one-dword items would
             // not all be resident at once (8 waves per SIMD): a second round of waves starts only when the first ends, and the
@@ -1137,9 +1100,8 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
         int order = c->local_order >= 0 ? c->local_order : (planes > (32 << 20) ? 2 : 0);
         const dim3 local_dim = order == 2 ? dim3((unsigned)(std::min(frames, 64) * local_grid), (unsigned)((frames + 63) / 64))
                                           : dim3(frames, local_grid);
-        const bool bits_ok = c->lm_bits[l] && c->lm_compact[l]; // bit strips are current (whatever else is)
-        const bool compact = c->lm_compact[l] && !c->lm_full[l];
-        if (!bits_ok && !compact && !c->lm_full[l]) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", l);
+        const LmForm reads = refine_reads(c->forms[l]);
+        if (reads == LM_NONE) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", l);
         const int local_waves = tuning().local_waves; // 4 or 16
         const bool small_blocks = local_waves ? local_waves == 4 : frames >= 4;
 #define SBM_LOCAL(COMPACT_, LM_, FS_)                                                                                               \
@@ -1156,7 +1118,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
                    c->d_cands.as<Cand>(), counters, (int)c->cand_cap, l == 0 ? 1 : 0, d_out, d_count, (int)cap, c->mirror_out,     \
                    c->mirror_count, (c->profiling ? 1 : 0) | (raised ? 2 : 0), (int64_t)(FS_) * c->lm_stride[l],                                       \
                    (COMPACT_) == 2 ? c->d_flabel_s.as<uint8_t>() : c->d_flabel.as<uint8_t>(), c->d_fcls.as<uint16_t>(), frames)
-        if (bits_ok) {
+        if (reads == LM_BIT_STRIPS) {
             // bit strips: one wave per candidate (four times the slots of the four-wave byte form)
             const int slots = local_grid_env ? local_grid_env : 4 * local_grid;
             // batches whose strips exceed the L2s: the slot order with every XCD taking its frames one after the other (flag 4)
@@ -1175,8 +1137,8 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
             else SBM_LOCAL_BITS(0);
 #undef SBM_LOCAL_BITS
         }
-        else if (compact && c->lm_strip[l]) { SBM_LOCAL(2, c->d_lmc[l].as<uint8_t>(), 1); }
-        else if (compact) { SBM_LOCAL(1, c->d_lmc[l].as<uint8_t>(), 1); }
+        else if (reads == LM_SPREAD_STRIP) { SBM_LOCAL(2, c->d_lmc[l].as<uint8_t>(), 1); }
+        else if (reads == LM_SPREAD) { SBM_LOCAL(1, c->d_lmc[l].as<uint8_t>(), 1); }
         else { SBM_LOCAL(0, c->d_lm[l].as<uint8_t>(), 8); }
 #undef SBM_LOCAL
 #undef SBM_LOCAL_LW
@@ -1192,24 +1154,19 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
 // for the coarsest level's bit planes.  Outside any capture.
 int ensure_local_forms(sbm_ctx* c, hipStream_t s)
 {
+    const PlanInputs pin = plan_inputs(c);
     for (int l = 0; l < c->L - 1; ++l) {
-        if (c->lm_bits[l] && c->lm_compact[l]) {
+        LevelForms& f = c->forms[l];
+        if (f.bit_strips) {
             // strips are current.  Asked for the byte form since, and the response planes are there: read those
-            if (!local_bits_wanted(c, l) && c->lm_full[l]) c->lm_bits[l] = c->lm_compact[l] = c->lm_strip[l] = false;
+            if (!local_bits_wanted(pin, l) && f.planes8) f.bit_strips = false;
             continue;
         }
-        if (!local_bits_wanted(c, l) || !c->lm_full[l] || c->lm_compact[l]) continue; // only beside stage-built response planes
-        const int T = c->cfg.T[l], W = c->cols[l] / T, H = c->rows[l] / T;
-        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], T)) continue;
+        if (!local_bits_wanted(pin, l) || !f.planes8 || f.spread) continue; // only beside stage-built response planes
+        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l])) continue;
         if (int e = c->d_lbits[l].ensure((size_t)lbits_frame_bytes(c, l), true)) return e;
-        LmArgs a;
-        memset(&a, 0, sizeof a);
-        a.n_levels = 1;
-        a.lv[0] = LmLevelArgs{c->d_quant[l].as<uint8_t>(), c->d_lbits[l].as<uint8_t>(), c->lm_stride[l], c->rows[l], c->cols[l], W, H, T, 0, 0, 0, 4, 1, 1};
-        const int64_t items = (int64_t)((W + 31) >> 5) * ((H + 31) >> 5) * 256;
-        SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a);
-        HIP_TRY(hipGetLastError());
-        c->lm_bits[l] = c->lm_compact[l] = c->lm_strip[l] = true; // (d_lmc[l] is not: nothing reads it while lm_bits is set)
+        if (int e = launch_lm_level(c, s, l, LM_BIT_STRIPS)) return e;
+        f.bit_strips = true;
     }
     return 0;
 }
@@ -1236,17 +1193,6 @@ bool graph_wanted(const sbm_ctx* c, int kind)
     // call per step -- does not have; with several batches in flight the two otherwise measure the same.  A single frame
     // at a time is faster as plain launches.
     return kind != 0 && c->pipeline_depth >= 2 && !c->auto_graph_off;
-}
-
-// Which buffers hold the current form of every level's linear memories (response planes / spread plane / strip plane / bit
-// strips, the coarsest level's bit planes): part of the key of a captured template loop, whose kernels and operands follow
-// from it -- a stage entry point may have rebuilt a level in another form since the capture, at the same geometry.
-int64_t lm_form_signature(const sbm_ctx* c)
-{
-    int64_t sig = c->blm_valid ? 1 : 0;
-    for (int l = 0; l < c->L; ++l)
-        sig = sig * 16 + ((c->lm_full[l] ? 1 : 0) | (c->lm_compact[l] ? 2 : 0) | (c->lm_strip[l] ? 4 : 0) | (c->lm_bits[l] ? 8 : 0));
-    return sig;
 }
 
 bool graph_key_equal(const sbm_ctx::GraphEntry& g, const sbm_ctx::GraphEntry& k)
@@ -1310,6 +1256,27 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
     return 0;
 }
 
+// Ends the capture on stream m that recorded an entry point's launches with result rc: the graph, or rc's / the capture's error
+int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
+{
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(m, &g);
+    if (rc) {
+        if (g) (void)hipGraphDestroy(g);
+        return rc;
+    }
+    if (e != hipSuccess || !g) return fail(SBM_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
+    *graph = g;
+    return 0;
+}
+
+// what a match entry point leaves resident, for the calls that replay its launches as a captured graph
+void record_match(sbm_ctx* c, bool one_launch)
+{
+    record_match(c->forms, plan_inputs(c), one_launch, c->h_active.empty());
+    c->levels_valid = c->L;
+}
+
 // The whole match() as a DAG, recorded by stream capture on the context's two private streams:
 //   main: quantize(0) -> quantize(1) -> ... -> quantize(L-1) -> build_lm(L-1) -> coarse -> [join] -> local(L-2..0)
 //   side:          \-> build_lm(0)      \-> build_lm(1) ...                                  /
@@ -1322,7 +1289,6 @@ int capture_match_graph(sbm_ctx* c, const uint8_t* d_img0, int stride0, const ui
     hipStream_t m = c->stream, sd = c->side;
     HIP_TRY(hipStreamBeginCapture(m, hipStreamCaptureModeThreadLocal));
     int rc = 0;
-    c->blm_valid = false;
     const uint8_t* img = d_img0;
     int stride = stride0;
     const uint8_t* mask = d_mask0;
@@ -1348,30 +1314,19 @@ int capture_match_graph(sbm_ctx* c, const uint8_t* d_img0, int stride0, const ui
                 break;
             }
             forked = true;
-            rc = launch_build_lm(c, sd, c->d_quant[l].as<uint8_t>(), c->rows[l], c->cols[l], c->cfg.T[l], c->d_lm[l].as<uint8_t>(), c->lm_stride[l]);
+            rc = launch_build_lm(c, sd, l);
         } else {
-            rc = launch_build_lm(c, m, c->d_quant[l].as<uint8_t>(), c->rows[l], c->cols[l], c->cfg.T[l], c->d_lm[l].as<uint8_t>(), c->lm_stride[l]);
+            rc = launch_build_lm(c, m, l);
         }
     }
-    for (int l = 0; l < L; ++l) { // the captured build is the 8-plane form at every level
-        c->lm_full[l] = true;
-        c->lm_compact[l] = false;
-    }
+    record_build(c->forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
     if (!rc) rc = enqueue_coarse(c, m, d_out, cap, d_count);
     if (!rc && forked) {
         if (hipEventRecord(c->ev_join, sd) != hipSuccess || hipStreamWaitEvent(m, c->ev_join, 0) != hipSuccess)
             rc = fail(SBM_ERR_HIP, "graph join failed");
     }
     if (!rc) rc = enqueue_local(c, m, d_out, cap, d_count);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(m, &g);
-    if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    if (e != hipSuccess || !g) return fail(SBM_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-    *graph = g;
-    return 0;
+    return end_capture(m, rc, graph);
 }
 
 // The batched match loop (BASELINE config 5: "hipGraph-captured match loop") as one captured graph: the same five
@@ -1385,15 +1340,7 @@ int capture_batch_graph(sbm_ctx* c, const uint8_t* d_imgs, int64_t frame_stride,
     int rc = enqueue_pyramid(c, m, d_imgs, stride0, d_mask0, d_counts, frames, frame_stride);
     if (!rc) rc = enqueue_coarse(c, m, d_out, cap, d_counts, frames);
     if (!rc) rc = enqueue_local(c, m, d_out, cap, d_counts, frames);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(m, &g);
-    if (rc) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-    }
-    if (e != hipSuccess || !g) return fail(SBM_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-    *graph = g;
-    return 0;
+    return end_capture(m, rc, graph);
 }
 
 int fetch_results(sbm_ctx* c, hipStream_t s, sbm_match_rec* out_host, int64_t cap, int64_t* n_out)

@@ -292,12 +292,9 @@ int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, 
     if (!c || !d_img || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");
     if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
+    hipStream_t s = launch_stream(c, stream);
     // anything the launches below are about to change may still be read by frames in flight
-    const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L) ||
-                       !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty;
-    if (dirty) HIP_TRY(hipDeviceSynchronize());
+    if (match_dirty(c, rows, cols, channels, 1, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (!graph_wanted(c, 0)) {
         if (int e = ensure_geometry(c, rows, cols, channels)) return e;
         if (c->profiling && !c->profiling_keep) c->clear_timings();
@@ -318,14 +315,7 @@ int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, 
             return capture_match_graph(c, (const uint8_t*)d_img, stride, (const uint8_t*)d_mask, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, g);
         }))
         return e;
-    c->levels_valid = c->L;
-    for (int l = 0; l < c->L; ++l) { // the captured build writes the 8-plane form at every level
-        c->lm_full[l] = true;
-        c->lm_compact[l] = false;
-    }
-    // ... and packs the coarsest level's bit planes from them when the coarse pass reads bits -- inside the coarse pass,
-    // which an empty template selection skips
-    c->blm_valid = coarse_on_bits(c) && !c->h_active.empty();
+    record_match(c, false); // the captured build is the generic builder's
     return 0;
 }
 
@@ -338,12 +328,8 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
     if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
     if (n_frames > 1 && frame_stride < (int64_t)stride * rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
-    const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L &&
-                         n_frames <= c->batch) ||
-                       !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty;
-    if (dirty) HIP_TRY(hipDeviceSynchronize());
+    hipStream_t s = launch_stream(c, stream);
+    if (match_dirty(c, rows, cols, channels, n_frames, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (int e = ensure_geometry(c, rows, cols, channels, n_frames)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (int e = prepare_templates(c, s, threshold, cap)) return e;
@@ -360,22 +346,7 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
             }))
             return e;
         if (launched) {
-            c->levels_valid = c->L;
-            for (int l = 0; l < c->L; ++l) { // what the replay leaves resident (as enqueue_pyramid records it)
-                bool compact, strip;
-                lm_form(c, l, &compact, &strip);
-                c->lm_compact[l] = compact;
-                c->lm_full[l] = !compact;
-                c->lm_strip[l] = strip;
-                c->lm_bits[l] = local_on_bits(c, l);
-            }
-            if (const int form = coarse_build_form(c)) { // the captured launch made the coarsest level's bit planes only (1),
-                c->lm_full[c->L - 1] = false;            // or its plane of spread bytes and, from that, the bit planes (2)
-                c->lm_compact[c->L - 1] = form == 2;
-                c->lm_strip[c->L - 1] = c->lm_bits[c->L - 1] = false;
-            }
-            // (the bit planes of the 8-plane form are packed by the coarse pass, which an empty selection skips)
-            c->blm_valid = coarse_on_bits(c) && (coarse_build_form(c) != 0 || !c->h_active.empty());
+            record_match(c, true); // a batch is captured only where the one-launch builder takes every level
             return 0;
         }
     }
@@ -388,9 +359,8 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
 {
     if (!c || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
-    if (!c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty) HIP_TRY(hipDeviceSynchronize());
+    hipStream_t s = launch_stream(c, stream);
+    if (templates_dirty(c, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (graph_wanted(c, -1)) {
         // the template loop (counter reset, coarse pass, refinement per level) as one captured graph: the preparation that
@@ -405,22 +375,14 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
         uint32_t thr_bits;
         memcpy(&thr_bits, &threshold, 4);
         const sbm_ctx::GraphEntry key{nullptr, c->rows[0], c->cols[0], 0, 0, nullptr, thr_bits, d_out, cap, d_count,
-                                      (void*)c->mirror_out, (void*)c->mirror_count, -1, lm_form_signature(c), nullptr, nullptr, 0};
+                                      (void*)c->mirror_out, (void*)c->mirror_count, -1, forms_signature(c->forms, c->L), nullptr, nullptr, 0};
         bool launched = false;
         if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
                 hipStream_t m = c->stream;
                 HIP_TRY(hipStreamBeginCapture(m, hipStreamCaptureModeThreadLocal));
                 int rc = enqueue_coarse(c, m, (sbm_match_rec*)d_out, cap, (int32_t*)d_count);
                 if (!rc) rc = enqueue_local(c, m, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, true);
-                hipGraph_t gg = nullptr;
-                hipError_t he = hipStreamEndCapture(m, &gg);
-                if (rc) {
-                    if (gg) (void)hipGraphDestroy(gg);
-                    return rc;
-                }
-                if (he != hipSuccess || !gg) return fail(SBM_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(he));
-                *g = gg;
-                return 0;
+                return end_capture(m, rc, g);
             }))
             return e;
         if (launched) return 0;
@@ -514,16 +476,12 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = order_after_caller_work(c)) return e;
     int sub = std::max(1, std::min(sub_batch > 0 ? sub_batch : 8, n_frames));
-    {
-        const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L && sub <= c->batch) ||
-                           !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty || c->citems_dirty;
-        if (dirty) HIP_TRY(hipDeviceSynchronize()); // geometry / template state changes below; frames in flight read it
-    }
+    // geometry / template state changes below; frames in flight read it
+    if (match_dirty(c, rows, cols, channels, sub, threshold) || c->citems_dirty) HIP_TRY(hipDeviceSynchronize());
     if (int e = ensure_geometry(c, rows, cols, channels, sub)) return e;
     // geometries the one-launch linear-memory builder does not take (level widths that are not multiples of 16, other
     // strides): one frame per "sub-batch" through the generic kernels -- the uploads still overlap the kernels
-    for (int l = 0; l < c->L; ++l)
-        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l])) sub = 1;
+    if (!all_rows_ok(c)) sub = 1;
     if (!c->copy_stream) {
         HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
@@ -825,12 +783,8 @@ int sbm_set_quantized(sbm_ctx* c, int32_t level, const uint8_t* q, int32_t rows,
     if (int e = ensure_level(c, level, rows, cols)) return e;
     if (c->profiling && !c->profiling_keep && level == 0) c->clear_timings();
     HIP_TRY(hipMemcpyAsync(c->d_quant[level].p, q, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-    if (int e = launch_build_lm(c, c->stream, c->d_quant[level].as<uint8_t>(), rows, cols, c->cfg.T[level],
-                                c->d_lm[level].as<uint8_t>(), c->lm_stride[level]))
-        return e;
-    c->lm_full[level] = true;
-    c->lm_compact[level] = false;
-    if (level == c->L - 1) c->blm_valid = false;
+    if (int e = launch_build_lm(c, c->stream, level)) return e;
+    c->forms[level].set(LM_PLANES8);
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->levels_valid = std::max(c->levels_valid, level + 1);
     if (c->profiling) collect_timings(c);
@@ -870,7 +824,7 @@ int sbm_get_coarse_bitplanes(sbm_ctx* c, int32_t frame, uint8_t* out, int64_t ca
     if (cap_bytes < need) return fail(SBM_ERR_CAPACITY, "need %lld bytes", (long long)need);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     HIP_TRY(hipDeviceSynchronize());
-    if (!c->blm_valid || !c->d_blm.p) return fail(SBM_ERR_STATE, "the last call did not build the coarsest level's bit planes");
+    if (!c->forms[c->L - 1].bit_planes || !c->d_blm.p) return fail(SBM_ERR_STATE, "the last call did not build the coarsest level's bit planes");
     HIP_TRY(hipMemcpy(out, c->d_blm.as<uint8_t>() + (size_t)frame * need, (size_t)need, hipMemcpyDeviceToHost));
     return 0;
 }

@@ -116,8 +116,7 @@ extern "C" int sbm_match_templates_device_sharded(sbm_ctx* c, float threshold, v
 {
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
+    hipStream_t s = launch_stream(c, stream);
     const size_t bytes = (size_t)SBM_SHARD_HEADER_BYTES + (size_t)cap * sizeof(sbm_match_rec);
     if (int e = sbm_match_templates_device(c, threshold, (char*)d_local + SBM_SHARD_HEADER_BYTES, cap, d_local, s)) return e;
     return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
@@ -129,8 +128,7 @@ extern "C" int sbm_match_device_sharded(sbm_ctx* c, const void* d_img, int32_t r
 {
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
+    hipStream_t s = launch_stream(c, stream);
     const size_t bytes = (size_t)SBM_SHARD_HEADER_BYTES + (size_t)cap * sizeof(sbm_match_rec);
     // this rank's shard: {n_matches, overflow, 0, 0} header followed by the records
     if (int e = sbm_match_device(c, d_img, rows, cols, stride, channels, d_mask, threshold, (char*)d_local + SBM_SHARD_HEADER_BYTES, cap,
@@ -147,8 +145,7 @@ extern "C" int sbm_match_batch_device_sharded(sbm_ctx* c, const void* d_imgs, in
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
     if (n_frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
+    hipStream_t s = launch_stream(c, stream);
     // this rank's shard: n_frames {n_matches, overflow} pairs (padded to 16 bytes), then n_frames blocks of cap records
     const size_t header = ((size_t)n_frames * 8 + 15) / 16 * 16;
     const size_t bytes = header + (size_t)n_frames * (size_t)cap * sizeof(sbm_match_rec);
@@ -194,12 +191,8 @@ extern "C" int sbm_match_batch_device_banded(sbm_ctx* c, const void* d_imgs, int
     if (multi) n_bands = c->comm_world;
     if (n_bands < 1) return fail(SBM_ERR_INVALID, "n_bands must be >= 1 on a single GPU");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (s != c->stream) c->caller_work = true;
-    const bool dirty = !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L &&
-                         n_frames <= c->batch) ||
-                       !c->have_thr || memcmp(&threshold, &c->thr_cached, 4) != 0 || c->foff_dirty;
-    if (dirty) HIP_TRY(hipDeviceSynchronize());
+    hipStream_t s = launch_stream(c, stream);
+    if (match_dirty(c, rows, cols, channels, n_frames, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (int e = ensure_geometry(c, rows, cols, channels, n_frames)) return e;
     if (int e = check_bands(c, n_bands)) return e;
     // The linear memories of a level must be built AFTER the exchange of its bands.  Only the one-launch builder runs

@@ -1,5 +1,5 @@
 """-m gpu: call sequences on ONE context (tools/fuzz_sequence.py) and the regressions the sequences found or were written
-for: the form state machine of an sbm_ctx (lm_full / lm_compact / lm_strip / lm_bits, blm_valid), the forms rebuilt
+for: the form state machine of an sbm_ctx (the per-level ``LevelForms`` record of sbm_level_forms.h), the forms rebuilt
 lazily by the template loop, and the caller's stream next to the context's own.  Every list against the oracle."""
 import os
 import subprocess

@@ -2,7 +2,7 @@
 """Randomised call sequences on ONE engine context against the CPU oracle (GPU box; test infrastructure).
 
 tools/fuzz_match.py makes a fresh context per case, so it never reaches a state transition of an ``sbm_ctx``: the per-level
-form flags (lm_full / lm_compact / lm_strip / lm_bits, blm_valid), the forms rebuilt lazily by the stage and template-loop
+record of current forms (``LevelForms``, sbm_level_forms.h), the forms rebuilt lazily by the stage and template-loop
 entry points, the graph cache, cached thresholds and feature offsets, and the caller's stream next to the context's own.
 Here every sequence creates one context with a drawn pyramid, draws ``steps`` operations (match entry points, pyramid
 state, stage reads, template uploads and selections, mode switches, thresholds) and applies them to it.  Device entry
