@@ -22,16 +22,18 @@ int fail(int code, const char* fmt, ...)
             return fail(SBM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// grow-only device buffer
+// grow-only device buffer; frees itself, and cannot be copied
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     int ensure(size_t bytes, bool zero = false)
     {
         if (bytes <= cap && p) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         size_t want = bytes ? bytes : 16;
         hipError_t e = hipMalloc(&p, want);
         if (e != hipSuccess) return fail(SBM_ERR_HIP, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
@@ -819,14 +821,43 @@ int check_bands(const sbm_ctx* c, int n_bands)
     for (int l = 0; l < c->L; ++l)
         if (c->rows[l] % n_bands || ((c->rows[l] / n_bands) & 1))
             return fail(SBM_ERR_INVALID, "level %d: %d rows do not split into %d bands of an even number of rows", l, c->rows[l], n_bands);
+    // The linear memories of a level must be built AFTER the exchange of its bands.  Only the one-launch builder runs
+    // there (enqueue_pyramid: after bands->between); the generic per-level builder runs right behind the level's gradient
+    // launch, i.e. on a map that still lacks the other ranks' rows.  Refuse such geometries instead of matching them wrong.
+    for (int l = 0; l < c->L; ++l)
+        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l]))
+            return fail(SBM_ERR_INVALID, "build-sharded match needs T in {4, 8} and 16-column-aligned levels (level %d: %d columns, T = %d)", l,
+                        c->cols[l], c->cfg.T[l]);
     return 0;
+}
+
+// Rows [row_lo, row_hi) of level l's gradient stage, the one place it is launched from for a pyramid.  img / stride / mask
+// are the caller's cursor down the pyramid: level 0's at first, and the first launch of a level l > 0 (first: the caller
+// says so; further bands of the level find the cursor moved) moves them down -- the mask resized from level l-1's, the
+// image the one level l-1's launch produced (fused cv::pyrDown).  img_fs: bytes between the frames of this level's image.
+int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const uint8_t*& img, int& stride, const uint8_t*& mask, int frames,
+                           int64_t img_fs, int row_lo, int row_hi)
+{
+    const int ch = c->channels;
+    if (l > 0 && first) {
+        if (mask) {
+            const int n = c->rows[l] * c->cols[l];
+            SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, mask, c->rows[l - 1],
+                       c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l]);
+            HIP_TRY(hipGetLastError());
+            mask = c->d_mask[l].as<uint8_t>();
+        }
+        img = c->d_img[l].as<uint8_t>();
+        stride = c->cols[l] * ch;
+    }
+    return launch_quantize(c, s, img, c->rows[l], c->cols[l], stride, ch, mask, c->cfg.weak_threshold, c->d_quant[l].as<uint8_t>(), nullptr,
+                           nullptr, l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames, img_fs, row_lo, row_hi);
 }
 
 int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0,
                     int32_t* reset_count = nullptr, int frames = 1, int64_t img0_fs = 0, const Bands* bands = nullptr,
                     bool level0_gradient_done = false)
 {
-    const int ch = c->channels;
     const uint8_t* img = d_img0;
     int stride = stride0;
     const uint8_t* mask = d_mask0;
@@ -839,19 +870,6 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     // (the linear memories of a level right behind its gradient launch -- two launches per batch, the orientation map still
     // in the caches -- measure the same as one launch for all levels at the end: tools/r03_lm_early.sh)
     for (int l = 0; l < c->L; ++l) {
-        if (l > 0) {
-            const int pr = c->rows[l - 1], pc = c->cols[l - 1];
-            // the image of level l was produced by level l-1's quantize launch (fused cv::pyrDown)
-            if (mask) {
-                const int n = c->rows[l] * c->cols[l];
-                SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, mask, pr, pc,
-                                   c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l]);
-                HIP_TRY(hipGetLastError());
-                mask = c->d_mask[l].as<uint8_t>();
-            }
-            img = c->d_img[l].as<uint8_t>();
-            stride = c->cols[l] * ch;
-        }
         const int nb = (l == 0 && level0_gradient_done) ? 0 : (bands && bands->n > 1 ? bands->count : 1);
         for (int b = 0; b < nb; ++b) {
             int lo = 0, hi = c->rows[l];
@@ -860,11 +878,8 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
                 lo = std::max(0, (bands->first + b) * br - e);
                 hi = std::min(c->rows[l], (bands->first + b + 1) * br + e);
             }
-            if (int e = launch_quantize(c, s, img, c->rows[l], c->cols[l], stride, ch, mask, c->cfg.weak_threshold,
-                                        c->d_quant[l].as<uint8_t>(), nullptr, nullptr,
-                                        l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames,
-                                        l == 0 ? img0_fs : (int64_t)c->rows[l] * c->cols[l] * ch, lo, hi))
-                return e;
+            const int64_t img_fs = l == 0 ? img0_fs : (int64_t)c->rows[l] * c->cols[l] * c->channels;
+            if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, frames, img_fs, lo, hi)) return e;
         }
         if (!all_rows && frames > 1) return fail(SBM_ERR_INVALID, "batched match needs T in {4, 8} and 16-column-aligned levels");
         if (!all_rows)
@@ -935,13 +950,71 @@ bool match_dirty(const sbm_ctx* c, int rows, int cols, int channels, int frames,
 // The tables are (re)built on the CONTEXT's stream and that stream is synchronised by the host, whatever stream the
 // consumers will run on: the caller's stream is neither waited on nor given work here (ADVICE round 2: a host wait on
 // the caller's stream fails while that stream is being captured).  Nothing is enqueued when nothing changed.
-int prepare_templates(sbm_ctx* c, hipStream_t, float threshold, int64_t cap)
+int prepare_templates(sbm_ctx* c, float threshold, int64_t cap)
 {
     if (c->n_templates == 0) return fail(SBM_ERR_STATE, "no templates uploaded");
     if (cap < 0 || cap > INT32_MAX) return fail(SBM_ERR_INVALID, "bad output capacity");
     if (int e = ensure_thresholds(c, threshold, c->stream)) return e;
     if (int e = ensure_foff(c, c->stream)) return e;
     return ensure_citems(c, c->stream);
+}
+
+// One match call as every entry point describes it: frames of rows x cols x ch pixels, frame_stride bytes apart, against the
+// active templates; per frame up to cap records into out and a {n_matches, overflow} pair into counts (device memory)
+struct MatchCall {
+    const uint8_t* img;
+    int rows, cols, stride, ch;
+    const uint8_t* mask;
+    float thr;
+    sbm_match_rec* out;
+    int64_t cap;
+    int32_t* counts;
+    int frames;
+    int64_t frame_stride;
+};
+
+int check_stride(int stride, int cols, int ch)
+{
+    return stride < cols * ch ? fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride) : 0;
+}
+
+int check_match_call(const sbm_ctx* c, const MatchCall& m)
+{
+    if (!c || !m.img || !m.out || !m.counts) return fail(SBM_ERR_INVALID, "null argument");
+    if (m.frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
+    if (int e = check_stride(m.stride, m.cols, m.ch)) return e;
+    if (m.frames > 1 && m.frame_stride < (int64_t)m.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
+    return 0;
+}
+
+// The prologue of a match call, before anything of it is enqueued, once the device is set and the stream chosen.
+// Whatever the call is about to change (geometry, batch size, pyramid, template tables; also_dirty: anything else the
+// caller knows of) may still be read by frames in flight, so the device is waited for first; every later state change
+// of the call happens here too (it may synchronise), so that the launches can be replayed as a graph.
+int settle_match_state(sbm_ctx* c, const MatchCall& m, const Bands* bands, bool also_dirty)
+{
+    if (match_dirty(c, m.rows, m.cols, m.ch, m.frames, m.thr) || also_dirty) HIP_TRY(hipDeviceSynchronize());
+    if (int e = ensure_geometry(c, m.rows, m.cols, m.ch, m.frames)) return e;
+    if (bands)
+        if (int e = check_bands(c, bands->n)) return e;
+    if (c->profiling && !c->profiling_keep) c->clear_timings();
+    return prepare_templates(c, m.thr, m.cap);
+}
+
+// ... of a device entry point: on the caller's stream or the context's
+int begin_match(sbm_ctx* c, void* stream, const MatchCall& m, hipStream_t* s, const Bands* bands = nullptr)
+{
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    *s = launch_stream(c, stream);
+    return settle_match_state(c, m, bands, false);
+}
+
+// ... of a host entry point: on the context's own stream, behind whatever a device entry point left on a caller's
+int begin_host_match(sbm_ctx* c, const MatchCall& m, bool also_dirty = false)
+{
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
+    return settle_match_state(c, m, nullptr, also_dirty);
 }
 
 // the coarsest level's bit planes (of `frames` frames) packed from its 8 response planes
@@ -966,6 +1039,24 @@ int ensure_coarse_planes(sbm_ctx* c, hipStream_t s)
     return c->forms[c->L - 1].bit_planes ? 0 : pack_bitplanes(c, s, 1);
 }
 
+// positions of the coarsest level's W x H grid a template is scored at (the host's side of the device's template_positions)
+int host_template_npos(const DevTL& tl, int T, int W, int H)
+{
+    const int wf = (tl.width - 1) / T + 1, hf = (tl.height - 1) / T + 1;
+    return (H - hf) * W + (W - wf) + 1;
+}
+
+// features of a template level that lie inside a rows x cols level: the ones its coarse pass adds
+int64_t features_in_bounds(const sbm_ctx* c, const DevTL& tl, int rows, int cols)
+{
+    int64_t n = 0;
+    for (int k = 0; k < tl.nf; ++k) {
+        const uint32_t xy = c->h_fxy[tl.feat_off + k];
+        if ((int)(xy & 0xffff) < cols && (int)(xy >> 16) < rows) ++n;
+    }
+    return n;
+}
+
 // coarse pass over the active templates (reset + k_similarity_coarse; single-level pyramids emit here)
 int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames = 1)
 {
@@ -978,6 +1069,8 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
     if (n_active > 0) {
         const int T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
         int chunks = (W * H + COARSE_POS_PER_BLOCK - 1) / COARSE_POS_PER_BLOCK;
+        // chunks of `per` positions that cover the positions some template reaches
+        auto coarse_chunks = [W, H](int npos, int per) { return std::max(1, (std::min(std::max(npos, 0), W * H) + per - 1) / per); };
         int bits_max_npos = 0;
         if (c->thr_cached >= 0.f) {
             // every raw_min is >= 1, so positions past a template's span (score 0) are never candidates:
@@ -985,13 +1078,9 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             // each XCD a contiguous, equally loaded range of chunks (its L2 then holds one slice of the
             // linear memories)
             int max_npos = 0;
-            for (int32_t t : c->h_active) {
-                const DevTL& tl = c->h_tls[(size_t)t * L + lc];
-                const int wf = (tl.width - 1) / T + 1, hf = (tl.height - 1) / T + 1;
-                max_npos = std::max(max_npos, (H - hf) * W + (W - wf) + 1);
-            }
+            for (int32_t t : c->h_active) max_npos = std::max(max_npos, host_template_npos(c->h_tls[(size_t)t * L + lc], T, W, H));
             bits_max_npos = max_npos;
-            int need = std::max(1, (std::min(std::max(max_npos, 0), W * H) + COARSE_POS_PER_BLOCK - 1) / COARSE_POS_PER_BLOCK);
+            int need = coarse_chunks(max_npos, COARSE_POS_PER_BLOCK);
             if (need >= 8) need = (need + 7) / 8 * 8;
             chunks = std::min(need, (chunks + 7) / 8 * 8);
         }
@@ -1009,20 +1098,20 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             for (int32_t t : c->h_active) max_nf = std::max(max_nf, c->h_tls[(size_t)t * L + lc].nf);
             if (coarse_packs_planes(pin, c->forms[lc], false))
                 if (int e = pack_bitplanes(c, s, frames)) return e;
-            chunks = std::max(1, (std::min(std::max(bits_max_npos, 0), W * H) + CB_POS - 1) / CB_POS);
+            chunks = coarse_chunks(bits_max_npos, CB_POS);
             // Two dwords (64 positions) per lane -- half as many, twice as long work items -- when the one-dword items would
             // not all be resident at once (8 waves per SIMD): a second round of waves starts only when the first ends, and the
             // launch then takes two "longest waves" instead of one.  SBM_BITS_DW=1|2 forces either.
             bits_dw = tuning().bits_dw ? tuning().bits_dw
                                        : (max_nf < 1024 && (int64_t)chunks * n_active * frames > (int64_t)c->n_simd * 8 ? 2 : 1);
-            if (bits_dw == 2) chunks = std::max(1, (std::min(std::max(bits_max_npos, 0), W * H) + 2 * CB_POS - 1) / (2 * CB_POS));
+            if (bits_dw == 2) chunks = coarse_chunks(bits_max_npos, 2 * CB_POS);
         }
         // the latency form (eight waves per item, no pruning) for launches of a few hundred items: one frame, a few hundred templates
         const bool bits_block = bits && (tuning().bits_block < 0 ? (int64_t)chunks * n_active * frames <= 2048 : tuning().bits_block != 0);
         for (int first = 0; first < n_active; first += 65535) {
             const int cnt = std::min(65535, n_active - first);
             if (bits_block) {
-                const int chunks1 = std::max(1, (std::min(std::max(bits_max_npos, 0), W * H) + CB_POS - 1) / CB_POS);
+                const int chunks1 = coarse_chunks(bits_max_npos, CB_POS);
 #define SBM_COARSE_BITS_BLOCK(P_)                                                                                                    \
                 SBM_LAUNCH(c, "k_similarity_coarse", (k_similarity_coarse_bits_block<P_>), dim3(chunks1, cnt, frames), dim3(512), 0, s,   \
                            c->d_blm.as<uint32_t>(), c->lm_stride[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(), c->d_soff.as<int32_t>(),   \
@@ -1149,6 +1238,13 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
     return 0;
 }
 
+// the template loop: coarse pass, then the refinement passes
+int enqueue_loop(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames, bool raised)
+{
+    if (int e = enqueue_coarse(c, s, d_out, cap, d_count, frames)) return e;
+    return enqueue_local(c, s, d_out, cap, d_count, frames, raised);
+}
+
 // The template loop on a pyramid that the stage entry points built (response planes at every level): its T = 4 refinement
 // levels as bit strips too, built once per pyramid from the resident orientation map (frame 0) -- what ensure_coarse_planes is
 // for the coarsest level's bit planes.  Outside any capture.
@@ -1175,10 +1271,9 @@ int ensure_local_forms(sbm_ctx* c, hipStream_t s)
 int enqueue_templates(sbm_ctx* c, hipStream_t s, float threshold, sbm_match_rec* d_out, int64_t cap, int32_t* d_count)
 {
     if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
-    if (int e = prepare_templates(c, s, threshold, cap)) return e;
+    if (int e = prepare_templates(c, threshold, cap)) return e;
     if (int e = ensure_local_forms(c, s)) return e;
-    if (int e = enqueue_coarse(c, s, d_out, cap, d_count)) return e;
-    return enqueue_local(c, s, d_out, cap, d_count, 1, /* raised: no gradient launches around a template-loop-only call */ true);
+    return enqueue_loop(c, s, d_out, cap, d_count, 1, /* raised: no gradient launches around a template-loop-only call */ true);
 }
 
 // ---- hipGraph replay of an entry point's launches -----------------------------------------------------------------
@@ -1277,70 +1372,85 @@ void record_match(sbm_ctx* c, bool one_launch)
     c->levels_valid = c->L;
 }
 
-// The whole match() as a DAG, recorded by stream capture on the context's two private streams:
+// every launch of a match call, in order
+int enqueue_match(sbm_ctx* c, hipStream_t s, const MatchCall& m, const Bands* bands = nullptr, bool level0_gradient_done = false)
+{
+    if (int e = enqueue_pyramid(c, s, m.img, m.stride, m.mask, m.counts, m.frames, m.frame_stride, bands, level0_gradient_done)) return e;
+    return enqueue_loop(c, s, m.out, m.cap, m.counts, m.frames, false);
+}
+
+// The whole match() of one frame as a DAG, recorded by stream capture on the context's two private streams:
 //   main: quantize(0) -> quantize(1) -> ... -> quantize(L-1) -> build_lm(L-1) -> coarse -> [join] -> local(L-2..0)
 //   side:          \-> build_lm(0)      \-> build_lm(1) ...                                  /
 // The linear memories of the finer levels are only needed by the refinement passes, so their
 // construction overlaps the coarse-level chain.
-int capture_match_graph(sbm_ctx* c, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0, sbm_match_rec* d_out,
-                        int64_t cap, int32_t* d_count, hipGraph_t* graph)
+int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
 {
-    const int ch = c->channels, L = c->L;
-    hipStream_t m = c->stream, sd = c->side;
-    HIP_TRY(hipStreamBeginCapture(m, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    const uint8_t* img = d_img0;
-    int stride = stride0;
-    const uint8_t* mask = d_mask0;
+    const int L = c->L;
+    hipStream_t st = c->stream, sd = c->side;
+    const uint8_t* img = m.img;
+    int stride = m.stride;
+    const uint8_t* mask = m.mask;
     bool forked = false;
-    for (int l = 0; l < L && !rc; ++l) {
-        if (l > 0) {
-            if (mask) {
-                const int n = c->rows[l] * c->cols[l];
-                hipLaunchKernelGGL(k_resize_mask, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, m, mask, c->rows[l - 1],
-                                   c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l]);
-                mask = c->d_mask[l].as<uint8_t>();
-            }
-            img = c->d_img[l].as<uint8_t>();
-            stride = c->cols[l] * ch;
-        }
-        rc = launch_quantize(c, m, img, c->rows[l], c->cols[l], stride, ch, mask, c->cfg.weak_threshold, c->d_quant[l].as<uint8_t>(),
-                             nullptr, nullptr, l + 1 < L ? c->d_img[l + 1].as<uint8_t>() : nullptr);
-        if (rc) break;
-        const bool use_fork = tuning().graph_fork;
-        if (l < L - 1 && use_fork) {
-            if (hipEventRecord(c->ev_fork[l], m) != hipSuccess || hipStreamWaitEvent(sd, c->ev_fork[l], 0) != hipSuccess) {
-                rc = fail(SBM_ERR_HIP, "graph fork failed");
-                break;
-            }
-            forked = true;
-            rc = launch_build_lm(c, sd, l);
-        } else {
-            rc = launch_build_lm(c, m, l);
-        }
+    for (int l = 0; l < L; ++l) {
+        if (int e = enqueue_gradient_level(c, st, l, true, img, stride, mask, 1, 0, 0, c->rows[l])) return e; // one frame: no frame stride
+        const bool fork = l < L - 1 && tuning().graph_fork;
+        if (fork && (hipEventRecord(c->ev_fork[l], st) != hipSuccess || hipStreamWaitEvent(sd, c->ev_fork[l], 0) != hipSuccess))
+            return fail(SBM_ERR_HIP, "graph fork failed");
+        forked = forked || fork;
+        if (int e = launch_build_lm(c, fork ? sd : st, l)) return e;
     }
     record_build(c->forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
-    if (!rc) rc = enqueue_coarse(c, m, d_out, cap, d_count);
-    if (!rc && forked) {
-        if (hipEventRecord(c->ev_join, sd) != hipSuccess || hipStreamWaitEvent(m, c->ev_join, 0) != hipSuccess)
-            rc = fail(SBM_ERR_HIP, "graph join failed");
-    }
-    if (!rc) rc = enqueue_local(c, m, d_out, cap, d_count);
-    return end_capture(m, rc, graph);
+    if (int e = enqueue_coarse(c, st, m.out, m.cap, m.counts)) return e;
+    if (forked && (hipEventRecord(c->ev_join, sd) != hipSuccess || hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess))
+        return fail(SBM_ERR_HIP, "graph join failed");
+    return enqueue_local(c, st, m.out, m.cap, m.counts);
 }
 
-// The batched match loop (BASELINE config 5: "hipGraph-captured match loop") as one captured graph: the same five
-// launches sbm_match_batch_device enqueues (gradient stage per level, linear memories + counter reset, coarse pass,
-// refinement per level), recorded once per distinct argument tuple and replayed with one hipGraphLaunch per batch.
-int capture_batch_graph(sbm_ctx* c, const uint8_t* d_imgs, int64_t frame_stride, int frames, int stride0, const uint8_t* d_mask0,
-                        sbm_match_rec* d_out, int64_t cap, int32_t* d_counts, hipGraph_t* graph)
+// kind: 0 single frame, > 0 frames of a batch, -1 the template loop alone (graph_wanted).  The key of the call's captured graph:
+sbm_ctx::GraphEntry graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
 {
-    hipStream_t m = c->stream;
-    HIP_TRY(hipStreamBeginCapture(m, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_pyramid(c, m, d_imgs, stride0, d_mask0, d_counts, frames, frame_stride);
-    if (!rc) rc = enqueue_coarse(c, m, d_out, cap, d_counts, frames);
-    if (!rc) rc = enqueue_local(c, m, d_out, cap, d_counts, frames);
-    return end_capture(m, rc, graph);
+    uint32_t thr_bits;
+    memcpy(&thr_bits, &m.thr, 4);
+    // (the template loop has no frame stride: what its launches depend on instead is the form every level is held in)
+    return sbm_ctx::GraphEntry{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
+                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, nullptr, nullptr, 0};
+}
+
+// The launches of a match call on stream s: a replay of the graph captured for its argument tuple where one is wanted --
+// the single frame as the forked DAG, a batch (BASELINE config 5: "hipGraph-captured match loop") and the template loop as
+// the plain launches recorded once on the context's stream -- else the plain launches themselves.  Every state change of
+// the call has happened (begin_match; here, what only the template loop still lacks): it may synchronise, a capture cannot.
+int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
+{
+    if (kind != 1 && graph_wanted(c, kind)) {
+        if (kind < 0) {
+            if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
+            if (int e = prepare_templates(c, m.thr, m.cap)) return e;
+            // the forms rebuilt here read the orientation maps that the caller's stream may still be writing (a match call
+            // enqueued just before): launched on s, as enqueue_templates does, they are ordered after it without a host wait.
+            // (prepare_templates has synchronised the context's stream whenever it enqueued anything.)
+            if (int e = ensure_coarse_planes(c, s)) return e;
+            if (int e = ensure_local_forms(c, s)) return e;
+        }
+        bool launched = false;
+        if (int e = graph_replay(c, graph_key(c, m, kind), s, &launched, [&](hipGraph_t* g) {
+                hipStream_t st = c->stream;
+                HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                const int rc = kind == 0  ? enqueue_match_forked(c, m)
+                               : kind < 0 ? enqueue_loop(c, st, m.out, m.cap, m.counts, 1, true)
+                                          : enqueue_match(c, st, m);
+                return end_capture(st, rc, g);
+            }))
+            return e;
+        if (launched) {
+            // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is captured only
+            // where the one-launch builder takes every level; the template loop builds nothing
+            if (kind >= 0) record_match(c, kind > 0);
+            return 0;
+        }
+    }
+    return kind < 0 ? enqueue_templates(c, s, m.thr, m.out, m.cap, m.counts) : enqueue_match(c, s, m);
 }
 
 int fetch_results(sbm_ctx* c, hipStream_t s, sbm_match_rec* out_host, int64_t cap, int64_t* n_out)

@@ -64,9 +64,7 @@ void sbm_destroy(sbm_ctx* c)
     for (int i = 0; i < 2; ++i) {
         if (c->ev_up[i]) (void)hipEventDestroy(c->ev_up[i]);
         if (c->ev_free[i]) (void)hipEventDestroy(c->ev_free[i]);
-        c->d_in[i].release();
     }
-    c->d_bout.release();
     if (c->h_bout) (void)hipHostFree(c->h_bout);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->h_res) (void)hipHostFree(c->h_res);
@@ -78,20 +76,8 @@ void sbm_destroy(sbm_ctx* c)
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->side) (void)hipStreamDestroy(c->side);
     c->clear_timings();
-    DevBuf* singles[] = {&c->d_tls, &c->d_fxy, &c->d_flabel, &c->d_flevel, &c->d_foff, &c->d_class, &c->d_tid, &c->d_active, &c->d_citems, &c->d_cfoff, &c->d_soff, &c->d_soffbase, &c->d_fxy_s, &c->d_flabel_s, &c->d_fcls,
-                         &c->d_rawmin, &c->d_rawkeep, &c->d_geo, &c->d_cands, &c->d_counters, &c->d_out, &c->d_outcount,
-                         &c->d_scratch, &c->d_blm, &c->d_nms_labels, &c->d_nms_scratch, &c->d_nms_out};
-    for (DevBuf* b : singles) b->release();
-    for (int l = 0; l < SBM_MAX_LEVELS; ++l) {
-        c->d_img[l].release();
-        c->d_mask[l].release();
-        c->d_quant[l].release();
-        c->d_lm[l].release();
-        c->d_lmc[l].release();
-        c->d_lbits[l].release();
-    }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // every device buffer frees itself (DevBuf): nothing reads them after the device-wide wait above
 }
 
 int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_level* levels, const sbm_feature* features,
@@ -261,14 +247,8 @@ int sbm_partition_templates(sbm_ctx* c, int32_t rows, int32_t cols, const int32_
         const int32_t t = list[i];
         if (t < 0 || t >= c->n_templates) return fail(SBM_ERR_INVALID, "template index %d out of range", t);
         const DevTL& tl = c->h_tls[(size_t)t * L + lc];
-        const int wf = (tl.width - 1) / T + 1, hf = (tl.height - 1) / T + 1;
-        const int npos = (H - hf) * W + (W - wf) + 1;
-        int64_t inb = 0;
-        if (npos > 0)
-            for (int k = 0; k < tl.nf; ++k) {
-                const uint32_t xy = c->h_fxy[tl.feat_off + k];
-                if ((int)(xy & 0xffff) < cl && (int)(xy >> 16) < rl) ++inb;
-            }
+        const int npos = host_template_npos(tl, T, W, H);
+        const int64_t inb = npos > 0 ? features_in_bounds(c, tl, rl, cl) : 0;
         cum[i + 1] = cum[i] + std::max<double>(1.0, (double)inb * std::max(npos, 0));
     }
     int prev = 0;
@@ -289,70 +269,22 @@ int sbm_partition_templates(sbm_ctx* c, int32_t rows, int32_t cols, const int32_
 int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, int32_t stride, int32_t channels,
                      const void* d_mask, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
 {
-    if (!c || !d_img || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");
-    if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
-    HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = launch_stream(c, stream);
-    // anything the launches below are about to change may still be read by frames in flight
-    if (match_dirty(c, rows, cols, channels, 1, threshold)) HIP_TRY(hipDeviceSynchronize());
-    if (!graph_wanted(c, 0)) {
-        if (int e = ensure_geometry(c, rows, cols, channels)) return e;
-        if (c->profiling && !c->profiling_keep) c->clear_timings();
-        if (int e = prepare_templates(c, s, threshold, cap)) return e;
-        if (int e = enqueue_pyramid(c, s, (const uint8_t*)d_img, stride, (const uint8_t*)d_mask, (int32_t*)d_count)) return e;
-        if (int e = enqueue_coarse(c, s, (sbm_match_rec*)d_out, cap, (int32_t*)d_count)) return e;
-        return enqueue_local(c, s, (sbm_match_rec*)d_out, cap, (int32_t*)d_count);
-    }
-    // graph path: all state changes happen up front (they may synchronise), then one hipGraphLaunch
-    uint32_t thr_bits;
-    memcpy(&thr_bits, &threshold, 4);
-    if (int e = ensure_geometry(c, rows, cols, channels)) return e;
-    if (int e = prepare_templates(c, c->stream, threshold, cap)) return e;
-    const sbm_ctx::GraphEntry key{d_img, rows, cols, stride, channels, d_mask, thr_bits, d_out, cap, d_count,
-                                  (void*)c->mirror_out, (void*)c->mirror_count, 0, 0, nullptr, nullptr, 0};
-    bool launched = false;
-    if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
-            return capture_match_graph(c, (const uint8_t*)d_img, stride, (const uint8_t*)d_mask, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, g);
-        }))
-        return e;
-    record_match(c, false); // the captured build is the generic builder's
-    return 0;
+    const MatchCall m{(const uint8_t*)d_img, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, 0};
+    if (int e = check_match_call(c, m)) return e;
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s)) return e;
+    return match_or_replay(c, s, m, 0);
 }
 
 int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows, int32_t cols,
                            int32_t stride, int32_t channels, const void* d_mask, float threshold, void* d_out, int64_t cap,
                            void* d_counts, void* stream)
 {
-    if (!c || !d_imgs || !d_out || !d_counts) return fail(SBM_ERR_INVALID, "null argument");
-    if (n_frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
-    if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
-    if (n_frames > 1 && frame_stride < (int64_t)stride * rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
-    HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = launch_stream(c, stream);
-    if (match_dirty(c, rows, cols, channels, n_frames, threshold)) HIP_TRY(hipDeviceSynchronize());
-    if (int e = ensure_geometry(c, rows, cols, channels, n_frames)) return e;
-    if (c->profiling && !c->profiling_keep) c->clear_timings();
-    if (int e = prepare_templates(c, s, threshold, cap)) return e;
-    if (n_frames > 1 && graph_wanted(c, n_frames)) {
-        // graph path: every state change happened above (they may synchronise); now one hipGraphLaunch per batch
-        uint32_t thr_bits;
-        memcpy(&thr_bits, &threshold, 4);
-        const sbm_ctx::GraphEntry key{d_imgs, rows, cols, stride, channels, d_mask, thr_bits, d_out, cap, d_counts,
-                                      (void*)c->mirror_out, (void*)c->mirror_count, n_frames, frame_stride, nullptr, nullptr, 0};
-        bool launched = false;
-        if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
-                return capture_batch_graph(c, (const uint8_t*)d_imgs, frame_stride, n_frames, stride, (const uint8_t*)d_mask, (sbm_match_rec*)d_out,
-                                           cap, (int32_t*)d_counts, g);
-            }))
-            return e;
-        if (launched) {
-            record_match(c, true); // a batch is captured only where the one-launch builder takes every level
-            return 0;
-        }
-    }
-    if (int e = enqueue_pyramid(c, s, (const uint8_t*)d_imgs, stride, (const uint8_t*)d_mask, (int32_t*)d_counts, n_frames, frame_stride)) return e;
-    if (int e = enqueue_coarse(c, s, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames)) return e;
-    return enqueue_local(c, s, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames);
+    const MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames, frame_stride};
+    if (int e = check_match_call(c, m)) return e;
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s)) return e;
+    return match_or_replay(c, s, m, n_frames);
 }
 
 int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
@@ -362,32 +294,9 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
     hipStream_t s = launch_stream(c, stream);
     if (templates_dirty(c, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (c->profiling && !c->profiling_keep) c->clear_timings();
-    if (graph_wanted(c, -1)) {
-        // the template loop (counter reset, coarse pass, refinement per level) as one captured graph: the preparation that
-        // may synchronise or launch only now and then runs first, outside the capture
-        if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
-        if (int e = prepare_templates(c, s, threshold, cap)) return e;
-        // the forms rebuilt here read the orientation maps that the caller's stream may still be writing (a match call
-        // enqueued just before): launched on s, as enqueue_templates does, they are ordered after it without a host wait.
-        // (prepare_templates has synchronised the context's stream whenever it enqueued anything.)
-        if (int e = ensure_coarse_planes(c, s)) return e;
-        if (int e = ensure_local_forms(c, s)) return e;
-        uint32_t thr_bits;
-        memcpy(&thr_bits, &threshold, 4);
-        const sbm_ctx::GraphEntry key{nullptr, c->rows[0], c->cols[0], 0, 0, nullptr, thr_bits, d_out, cap, d_count,
-                                      (void*)c->mirror_out, (void*)c->mirror_count, -1, forms_signature(c->forms, c->L), nullptr, nullptr, 0};
-        bool launched = false;
-        if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
-                hipStream_t m = c->stream;
-                HIP_TRY(hipStreamBeginCapture(m, hipStreamCaptureModeThreadLocal));
-                int rc = enqueue_coarse(c, m, (sbm_match_rec*)d_out, cap, (int32_t*)d_count);
-                if (!rc) rc = enqueue_local(c, m, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, true);
-                return end_capture(m, rc, g);
-            }))
-            return e;
-        if (launched) return 0;
-    }
-    return enqueue_templates(c, s, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count);
+    // no image: the pyramid is the resident one
+    const MatchCall m{nullptr, c->rows[0], c->cols[0], 0, 0, nullptr, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, 0};
+    return match_or_replay(c, s, m, -1);
 }
 
 int sbm_set_quantize_mode(sbm_ctx* c, int32_t mode, int32_t rows_per_wave)
@@ -452,10 +361,34 @@ int sbm_graph_count(sbm_ctx* c, int32_t* n)
     return 0;
 }
 
+// the copy stream of the host pipelines and the events that order its two input buffers against the kernels' stream
+static int ensure_copy_stream(sbm_ctx* c)
+{
+    if (c->copy_stream) return 0;
+    HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_up[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
+    }
+    return 0;
+}
+
+// The result mirror pointed elsewhere for the length of a scope (a host entry point's own pinned block): the caller's
+// mirror (sbm_set_result_mirror) is back on every way out
+struct MirrorScope {
+    sbm_ctx* c;
+    sbm_match_rec* const out;
+    int32_t* const count;
+    explicit MirrorScope(sbm_ctx* c_) : c(c_), out(c_->mirror_out), count(c_->mirror_count) {}
+    MirrorScope(const MirrorScope&) = delete;
+    void to(sbm_match_rec* o, int32_t* n) { c->mirror_out = o, c->mirror_count = n; }
+    ~MirrorScope() { to(out, count); }
+};
+
 static int upload_image(sbm_ctx* c, const uint8_t* img, int rows, int cols, int stride, int ch, const uint8_t* mask)
 {
     if (!img) return fail(SBM_ERR_INVALID, "null image");
-    if (stride < cols * ch) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
+    if (int e = check_stride(stride, cols, ch)) return e;
     if (int e = ensure_geometry(c, rows, cols, ch)) return e;
     // No implicit pinning: whether the copy below is a direct DMA (the frame lies in memory the caller pinned with
     // sbm_pin_host_buffer / hipHostMalloc / hipHostRegister) or a staged pageable copy is decided by the runtime from
@@ -470,26 +403,18 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
 {
     if (!c || !frames || n_frames < 1 || cap < 1) return fail(SBM_ERR_INVALID, "bad batch arguments");
     if (c->pending.active) return fail(SBM_ERR_STATE, "a host batch is already in flight (call sbm_match_batch_host_end)");
-    if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
+    if (int e = check_stride(stride, cols, channels)) return e;
     for (int f = 0; f < n_frames; ++f)
         if (!frames[f]) return fail(SBM_ERR_INVALID, "frame %d is null", f);
-    HIP_TRY(hipSetDevice(c->cfg.device_id));
-    if (int e = order_after_caller_work(c)) return e;
     int sub = std::max(1, std::min(sub_batch > 0 ? sub_batch : 8, n_frames));
-    // geometry / template state changes below; frames in flight read it
-    if (match_dirty(c, rows, cols, channels, sub, threshold) || c->citems_dirty) HIP_TRY(hipDeviceSynchronize());
-    if (int e = ensure_geometry(c, rows, cols, channels, sub)) return e;
+    const size_t frame_bytes = (size_t)rows * cols * channels;
+    // one sub-batch: frames from an input buffer of the pipeline, packed; image, results and frame count follow per sub-batch
+    MatchCall m{nullptr, rows, cols, cols * channels, channels, nullptr, threshold, nullptr, cap, nullptr, sub, (int64_t)frame_bytes};
+    if (int e = begin_host_match(c, m, c->citems_dirty)) return e;
     // geometries the one-launch linear-memory builder does not take (level widths that are not multiples of 16, other
     // strides): one frame per "sub-batch" through the generic kernels -- the uploads still overlap the kernels
     if (!all_rows_ok(c)) sub = 1;
-    if (!c->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_up[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
-        }
-    }
-    const size_t frame_bytes = (size_t)rows * cols * channels;
+    if (int e = ensure_copy_stream(c)) return e;
     for (int i = 0; i < 2; ++i)
         if (int e = c->d_in[i].ensure((size_t)sub * frame_bytes)) return e;
     // results: n_frames blocks of cap records, then n_frames {n_matches, overflow} pairs -- on the device and in pinned memory
@@ -504,11 +429,11 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     }
     int32_t* h_counts = (int32_t*)(c->h_bout + rec_bytes);
     for (int f = 0; f < n_frames; ++f) h_counts[2 * f] = -1, h_counts[2 * f + 1] = 0;
-    if (c->profiling && !c->profiling_keep) c->clear_timings();
-    if (int e = prepare_templates(c, c->stream, threshold, cap)) return e;
-    if (mask) HIP_TRY(hipMemcpyAsync(c->d_mask[0].p, mask, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-    sbm_match_rec* const user_mo = c->mirror_out;
-    int32_t* const user_mc = c->mirror_count;
+    if (mask) {
+        HIP_TRY(hipMemcpyAsync(c->d_mask[0].p, mask, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
+        m.mask = c->d_mask[0].as<uint8_t>();
+    }
+    MirrorScope mirror(c);
     int rc = 0;
     for (int f0 = 0, k = 0; f0 < n_frames && !rc; f0 += sub, ++k) {
         const int nf = std::min(sub, n_frames - f0), buf = k & 1;
@@ -534,18 +459,14 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
             rc = fail(SBM_ERR_HIP, "event record / wait failed");
             break;
         }
-        sbm_match_rec* d_out = c->d_bout.as<sbm_match_rec>() + (size_t)f0 * cap;
-        int32_t* d_cnt = (int32_t*)((char*)c->d_bout.p + rec_bytes) + 2 * f0;
-        c->mirror_out = (sbm_match_rec*)c->h_bout + (size_t)f0 * cap;
-        c->mirror_count = h_counts + 2 * f0;
-        rc = enqueue_pyramid(c, c->stream, c->d_in[buf].as<uint8_t>(), cols * channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr, d_cnt, nf,
-                             (int64_t)frame_bytes);
-        if (!rc) rc = enqueue_coarse(c, c->stream, d_out, cap, d_cnt, nf);
-        if (!rc) rc = enqueue_local(c, c->stream, d_out, cap, d_cnt, nf);
+        m.img = c->d_in[buf].as<uint8_t>();
+        m.out = c->d_bout.as<sbm_match_rec>() + (size_t)f0 * cap;
+        m.counts = (int32_t*)((char*)c->d_bout.p + rec_bytes) + 2 * f0;
+        m.frames = nf;
+        mirror.to((sbm_match_rec*)c->h_bout + (size_t)f0 * cap, h_counts + 2 * f0);
+        rc = enqueue_match(c, c->stream, m);
         if (!rc && hipEventRecord(c->ev_free[buf], c->stream) != hipSuccess) rc = fail(SBM_ERR_HIP, "event record failed");
     }
-    c->mirror_out = user_mo;
-    c->mirror_count = user_mc;
     if (rc) {
         (void)hipDeviceSynchronize();
         return rc;
@@ -640,15 +561,9 @@ static int upload_image_banded(sbm_ctx* c, const uint8_t* img, int rows, int col
     const int n_tile_rows = (rows + QT_R - 1) / QT_R;
     if (NB < 2 || n_tile_rows < 4 * NB || quantize_stream_rows(c, rows, cols, ch, 1, false, 0, cols * ch) != 0) return 0;
     if (!img) return fail(SBM_ERR_INVALID, "null image");
-    if (stride < cols * ch) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
+    if (int e = check_stride(stride, cols, ch)) return e;
     if (int e = ensure_geometry(c, rows, cols, ch)) return e;
-    if (!c->copy_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_up[i], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&c->ev_free[i], hipEventDisableTiming));
-        }
-    }
+    if (int e = ensure_copy_stream(c)) return e;
     for (int j = 0; j < NB; ++j)
         if (!c->ev_band[j]) HIP_TRY(hipEventCreateWithFlags(&c->ev_band[j], hipEventDisableTiming));
     if (mask) HIP_TRY(hipMemcpyAsync(c->d_mask[0].p, mask, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
@@ -685,16 +600,11 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
     if (int e = upload_image_banded(c, img, rows, cols, stride, channels, mask, &l0_done)) return e;
     if (!l0_done)
         if (int e = upload_image(c, img, rows, cols, stride, channels, mask)) return e;
-    if (int e = prepare_templates(c, c->stream, threshold, c->cand_cap)) return e;
-    if (int e = enqueue_pyramid(c, c->stream, c->d_img[0].as<uint8_t>(), cols * channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr,
-                                c->d_outcount.as<int32_t>(), 1, 0, nullptr, l0_done))
-        return e;
+    if (int e = prepare_templates(c, threshold, c->cand_cap)) return e;
     // results: the emitting kernel also stores every record and the final {count, overflow} pair into pinned host
     // memory, so one stream synchronisation ends the call; lists longer than the pinned buffer take the copy path
-    sbm_match_rec* const user_mo = c->mirror_out;
-    int32_t* const user_mc = c->mirror_count;
     bool own_mirror = false;
-    if (!user_mo) {
+    if (!c->mirror_out) {
         if (!c->h_res) {
             c->h_res_cap = 4096;
             if (hipHostMalloc((void**)&c->h_res, (size_t)c->h_res_cap * sizeof(sbm_match_rec), hipHostMallocDefault) != hipSuccess ||
@@ -705,21 +615,21 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
                 c->h_res_count = nullptr;
             }
         }
-        if (c->h_res && c->h_res_count) {
-            c->h_res_count[0] = -1;
-            c->h_res_count[1] = 0;
-            c->mirror_out = c->h_res;
-            c->mirror_count = c->h_res_count;
-            own_mirror = true;
-        }
+        own_mirror = c->h_res && c->h_res_count;
     }
     // with the pinned mirror the emitting kernel's record capacity is the pinned buffer's (it bounds both copies)
     const int64_t dev_cap = own_mirror ? std::min<int64_t>(c->cand_cap, c->h_res_cap) : c->cand_cap;
-    int rc = enqueue_coarse(c, c->stream, c->d_out.as<sbm_match_rec>(), dev_cap, c->d_outcount.as<int32_t>());
-    if (!rc) rc = enqueue_local(c, c->stream, c->d_out.as<sbm_match_rec>(), dev_cap, c->d_outcount.as<int32_t>());
-    c->mirror_out = user_mo;
-    c->mirror_count = user_mc;
-    if (rc) return rc;
+    const MatchCall m{c->d_img[0].as<uint8_t>(), rows, cols, cols * channels, channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr, threshold,
+                      c->d_out.as<sbm_match_rec>(), dev_cap, c->d_outcount.as<int32_t>(), 1, 0};
+    {
+        MirrorScope mirror(c);
+        if (own_mirror) {
+            c->h_res_count[0] = -1;
+            c->h_res_count[1] = 0;
+            mirror.to(c->h_res, c->h_res_count);
+        }
+        if (int e = enqueue_match(c, c->stream, m, nullptr, l0_done)) return e;
+    }
     if (own_mirror) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         const int n = c->h_res_count[0];
@@ -732,10 +642,9 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
         }
         // more records than the pinned buffer holds (or a candidate overflow to report): run the template loop again on
         // the resident pyramid with the full device capacity and take the copy path
-        if ((rc = enqueue_coarse(c, c->stream, c->d_out.as<sbm_match_rec>(), c->cand_cap, c->d_outcount.as<int32_t>()))) return rc;
-        if ((rc = enqueue_local(c, c->stream, c->d_out.as<sbm_match_rec>(), c->cand_cap, c->d_outcount.as<int32_t>()))) return rc;
+        if (int e = enqueue_loop(c, c->stream, m.out, c->cand_cap, m.counts, 1, false)) return e;
     }
-    rc = fetch_results(c, c->stream, out, cap, n_out);
+    const int rc = fetch_results(c, c->stream, out, cap, n_out);
     if (c->profiling) collect_timings(c);
     return rc;
 }

@@ -97,15 +97,20 @@ extern "C" int sbm_comm_count(sbm_ctx* c, int32_t* n_ranks)
 }
 
 // the exchange step every sharded entry point ends with: every rank's shard to every rank (ncclAllGather over xGMI on the
-// kernels' stream), optionally copied on into device-visible host memory
+// kernels' stream; without a communicator the local shard is all there is), optionally copied on into device-visible host memory
 static int gather_shards(sbm_ctx* c, hipStream_t s, const void* d_local, size_t bytes, void* d_gathered, void* gathered_mirror)
 {
-    int rc = g_rccl.AllGather(d_local, d_gathered, bytes, /* ncclUint8 */ 1, c->comm, s);
-    if (rc) return fail(SBM_ERR_HIP, "ncclAllGather: %s", rccl_err(rc));
+    const void* result = d_local;
+    size_t total = bytes;
+    if (c->comm) {
+        int rc = g_rccl.AllGather(d_local, d_gathered, bytes, /* ncclUint8 */ 1, c->comm, s);
+        if (rc) return fail(SBM_ERR_HIP, "ncclAllGather: %s", rccl_err(rc));
+        result = d_gathered;
+        total = bytes * (size_t)c->comm_world;
+    }
     if (gathered_mirror) {
-        const size_t total = bytes * (size_t)c->comm_world;
         hipLaunchKernelGGL(k_copy_bytes, dim3((unsigned)std::min<size_t>((total / 16 + 255) / 256 + 1, 1024)), dim3(256), 0, s,
-                           (const uint8_t*)d_gathered, (uint8_t*)gathered_mirror, total);
+                           (const uint8_t*)result, (uint8_t*)gathered_mirror, total);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -116,10 +121,9 @@ extern "C" int sbm_match_templates_device_sharded(sbm_ctx* c, float threshold, v
 {
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
-    hipStream_t s = launch_stream(c, stream);
     const size_t bytes = (size_t)SBM_SHARD_HEADER_BYTES + (size_t)cap * sizeof(sbm_match_rec);
-    if (int e = sbm_match_templates_device(c, threshold, (char*)d_local + SBM_SHARD_HEADER_BYTES, cap, d_local, s)) return e;
-    return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
+    if (int e = sbm_match_templates_device(c, threshold, (char*)d_local + SBM_SHARD_HEADER_BYTES, cap, d_local, stream)) return e;
+    return gather_shards(c, launch_stream(c, stream), d_local, bytes, d_gathered, gathered_mirror);
 }
 
 extern "C" int sbm_match_device_sharded(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, int32_t stride, int32_t channels,
@@ -128,14 +132,13 @@ extern "C" int sbm_match_device_sharded(sbm_ctx* c, const void* d_img, int32_t r
 {
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
-    hipStream_t s = launch_stream(c, stream);
     const size_t bytes = (size_t)SBM_SHARD_HEADER_BYTES + (size_t)cap * sizeof(sbm_match_rec);
     // this rank's shard: {n_matches, overflow, 0, 0} header followed by the records
     if (int e = sbm_match_device(c, d_img, rows, cols, stride, channels, d_mask, threshold, (char*)d_local + SBM_SHARD_HEADER_BYTES, cap,
-                                 d_local, s))
+                                 d_local, stream))
         return e;
     // the one exchange step of the path: every rank's list to every rank, over xGMI, on the same stream
-    return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
+    return gather_shards(c, launch_stream(c, stream), d_local, bytes, d_gathered, gathered_mirror);
 }
 
 extern "C" int sbm_match_batch_device_sharded(sbm_ctx* c, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows,
@@ -145,14 +148,13 @@ extern "C" int sbm_match_batch_device_sharded(sbm_ctx* c, const void* d_imgs, in
     if (!c || !d_local || !d_gathered) return fail(SBM_ERR_INVALID, "null argument");
     if (!c->comm) return fail(SBM_ERR_STATE, "sbm_comm_init has not been called on this context");
     if (n_frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
-    hipStream_t s = launch_stream(c, stream);
     // this rank's shard: n_frames {n_matches, overflow} pairs (padded to 16 bytes), then n_frames blocks of cap records
     const size_t header = ((size_t)n_frames * 8 + 15) / 16 * 16;
     const size_t bytes = header + (size_t)n_frames * (size_t)cap * sizeof(sbm_match_rec);
     if (int e = sbm_match_batch_device(c, d_imgs, frame_stride, n_frames, rows, cols, stride, channels, d_mask, threshold,
-                                       (char*)d_local + header, cap, d_local, s))
+                                       (char*)d_local + header, cap, d_local, stream))
         return e;
-    return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
+    return gather_shards(c, launch_stream(c, stream), d_local, bytes, d_gathered, gathered_mirror);
 }
 
 // the exchange of the build-sharded step: every rank's row band of every level's orientation map, in place
@@ -179,10 +181,13 @@ extern "C" int sbm_match_batch_device_banded(sbm_ctx* c, const void* d_imgs, int
                                              void* d_local, int64_t cap, void* d_gathered, void* gathered_mirror, int32_t n_bands,
                                              void* stream)
 {
-    if (!c || !d_imgs || !d_local) return fail(SBM_ERR_INVALID, "null argument");
-    if (n_frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
-    if (stride < cols * channels) return fail(SBM_ERR_INVALID, "stride %d < cols*channels", stride);
-    if (n_frames > 1 && frame_stride < (int64_t)stride * rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
+    if (!c || !d_local) return fail(SBM_ERR_INVALID, "null argument");
+    MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_local, cap, (int32_t*)d_local, n_frames, frame_stride};
+    if (int e = check_match_call(c, m)) return e;
+    // this rank's shard, as sbm_match_batch_device_sharded lays it out: the records follow the header of counts
+    const size_t header = ((size_t)n_frames * 8 + 15) / 16 * 16;
+    const size_t bytes = header + (size_t)n_frames * (size_t)cap * sizeof(sbm_match_rec);
+    m.out = (sbm_match_rec*)((char*)d_local + header);
     const bool comm = c->comm != nullptr;
     if (comm && !d_gathered) return fail(SBM_ERR_INVALID, "d_gathered is required with a communicator");
     const bool multi = comm && c->comm_world > 1;
@@ -190,47 +195,17 @@ extern "C" int sbm_match_batch_device_banded(sbm_ctx* c, const void* d_imgs, int
         return fail(SBM_ERR_INVALID, "n_bands %d != communicator size %d", n_bands, c->comm_world);
     if (multi) n_bands = c->comm_world;
     if (n_bands < 1) return fail(SBM_ERR_INVALID, "n_bands must be >= 1 on a single GPU");
-    HIP_TRY(hipSetDevice(c->cfg.device_id));
-    hipStream_t s = launch_stream(c, stream);
-    if (match_dirty(c, rows, cols, channels, n_frames, threshold)) HIP_TRY(hipDeviceSynchronize());
-    if (int e = ensure_geometry(c, rows, cols, channels, n_frames)) return e;
-    if (int e = check_bands(c, n_bands)) return e;
-    // The linear memories of a level must be built AFTER the exchange of its bands.  Only the one-launch builder runs
-    // there (enqueue_pyramid: after bands->between); the generic per-level builder runs right behind the level's gradient
-    // launch, i.e. on a map that still lacks the other ranks' rows.  Refuse such geometries instead of matching them wrong.
-    for (int l = 0; l < c->L; ++l)
-        if (!lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l]))
-            return fail(SBM_ERR_INVALID, "build-sharded match needs T in {4, 8} and 16-column-aligned levels (level %d: %d columns, T = %d)", l,
-                        c->cols[l], c->cfg.T[l]);
-    if (c->profiling && !c->profiling_keep) c->clear_timings();
-    if (int e = prepare_templates(c, s, threshold, cap)) return e;
-    const size_t header = ((size_t)n_frames * 8 + 15) / 16 * 16;
-    const size_t bytes = header + (size_t)n_frames * (size_t)cap * sizeof(sbm_match_rec);
-    sbm_match_rec* out = (sbm_match_rec*)((char*)d_local + header);
-    int32_t* counts = (int32_t*)d_local;
     Bands b;
     b.n = n_bands;
     b.first = multi ? c->comm_rank : 0;  // several ranks: this rank's band, then the exchange
     b.count = multi ? 1 : n_bands;       // one GPU: every band, one launch each (rehearsal of the band launches; with a
     b.between = comm ? gather_bands : nullptr; // one-rank communicator also of the grouped in-place all-gathers)
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s, &b)) return e;
     // a result mirror set on the context would be written by the last kernel; the gathered mirror below replaces it
-    if (int e = enqueue_pyramid(c, s, (const uint8_t*)d_imgs, stride, (const uint8_t*)d_mask, counts, n_frames, frame_stride, &b)) return e;
-    if (int e = enqueue_coarse(c, s, out, cap, counts, n_frames)) return e;
-    if (int e = enqueue_local(c, s, out, cap, counts, n_frames)) return e;
-    const void* result = d_local;
-    size_t total = bytes;
-    if (comm) { // the second exchange of the step: the per-rank match lists (as sbm_match_batch_device_sharded)
-        int rc = g_rccl.AllGather(d_local, d_gathered, bytes, /* ncclUint8 */ 1, c->comm, s);
-        if (rc) return fail(SBM_ERR_HIP, "ncclAllGather: %s", rccl_err(rc));
-        result = d_gathered;
-        total = bytes * (size_t)c->comm_world;
-    }
-    if (gathered_mirror) {
-        hipLaunchKernelGGL(k_copy_bytes, dim3((unsigned)std::min<size_t>((total / 16 + 255) / 256 + 1, 1024)), dim3(256), 0, s,
-                           (const uint8_t*)result, (uint8_t*)gathered_mirror, total);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    if (int e = enqueue_match(c, s, m, &b)) return e;
+    // the second exchange of the step: the per-rank match lists
+    return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
 }
 
 // Single-process multi-GPU match (SURVEY.md 8b: sbm_match_sharded(ctxs[], n_gpus, ...)): the analogue of the reference's
@@ -287,13 +262,8 @@ int sbm_coarse_bytes(sbm_ctx* c, int64_t* bytes)
     int64_t total = 0;
     for (int32_t t : c->h_active) {
         const DevTL& tl = c->h_tls[(size_t)t * c->L + lc];
-        const int wf = (tl.width - 1) / T + 1, hf = (tl.height - 1) / T + 1;
-        const int npos = (H - hf) * W + (W - wf) + 1;
-        if (npos <= 0) continue;
-        for (int i = 0; i < tl.nf; ++i) {
-            const uint32_t xy = c->h_fxy[tl.feat_off + i];
-            if ((int)(xy & 0xffff) < c->cols[lc] && (int)(xy >> 16) < c->rows[lc]) total += npos;
-        }
+        const int npos = host_template_npos(tl, T, W, H);
+        if (npos > 0) total += npos * features_in_bounds(c, tl, c->rows[lc], c->cols[lc]);
     }
     *bytes = total;
     return 0;

@@ -12,24 +12,17 @@ int sbm_quantized_orientations(sbm_ctx* c, const uint8_t* img, int32_t rows, int
     int rc = 0;
     if ((rc = d_in.ensure(npx * ch)) || (rc = d_q.ensure(npx)) || (magnitude && (rc = d_mag.ensure(npx * 4))) ||
         (angle_ori && (rc = d_ori.ensure(npx * 4))))
-        goto done;
-    if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "image upload failed");
-        goto done;
-    }
+        return rc;
+    if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "image upload failed");
     if ((rc = launch_quantize(c, c->stream, d_in.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, weak, d_q.as<uint8_t>(),
                               magnitude ? d_mag.as<float>() : nullptr, angle_ori ? d_ori.as<float>() : nullptr, nullptr)))
-        goto done;
+        return rc;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(angle, d_q.p, npx, hipMemcpyDeviceToHost) != hipSuccess ||
         (magnitude && hipMemcpy(magnitude, d_mag.p, npx * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
         (angle_ori && hipMemcpy(angle_ori, d_ori.p, npx * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        rc = fail(SBM_ERR_HIP, "quantize kernel or download failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    d_in.release();
-    d_q.release();
-    d_mag.release();
-    d_ori.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "quantize kernel or download failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_extract_local_maxima(sbm_ctx* c, const float* magnitude, const uint8_t* mask, int32_t rows, int32_t cols, float strong_threshold,
@@ -44,58 +37,43 @@ int sbm_extract_local_maxima(sbm_ctx* c, const float* magnitude, const uint8_t* 
     std::vector<int32_t> pts;
     int rc = 0;
     int64_t dev_cap = std::max<int64_t>(4096, std::min<int64_t>((int64_t)npx / 8, 1 << 22));
-    if ((rc = d_mag.ensure(npx * 4)) || (mask && (rc = d_mask.ensure(npx))) || (rc = d_cnt.ensure(16))) goto done;
+    if ((rc = d_mag.ensure(npx * 4)) || (mask && (rc = d_mask.ensure(npx))) || (rc = d_cnt.ensure(16))) return rc;
     if (hipMemcpy(d_mag.p, magnitude, npx * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (mask && hipMemcpy(d_mask.p, mask, npx, hipMemcpyHostToDevice) != hipSuccess)) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+        (mask && hipMemcpy(d_mask.p, mask, npx, hipMemcpyHostToDevice) != hipSuccess))
+        return fail(SBM_ERR_HIP, "upload failed");
     for (;;) {
         int32_t n = 0;
-        if ((rc = d_xy.ensure((size_t)dev_cap * 4))) goto done;
-        if (hipMemsetAsync(d_cnt.p, 0, 16, c->stream) != hipSuccess) {
-            rc = fail(SBM_ERR_HIP, "memset failed");
-            goto done;
-        }
+        if ((rc = d_xy.ensure((size_t)dev_cap * 4))) return rc;
+        if (hipMemsetAsync(d_cnt.p, 0, 16, c->stream) != hipSuccess) return fail(SBM_ERR_HIP, "memset failed");
         hipLaunchKernelGGL(k_local_maxima5, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 8192)), dim3(256), 0, c->stream, d_mag.as<float>(),
                            mask ? d_mask.as<uint8_t>() : nullptr, rows, cols, strong_threshold * strong_threshold, d_xy.as<int32_t>(),
                            d_cnt.as<int32_t>(), (int)dev_cap);
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, d_cnt.p, 4, hipMemcpyDeviceToHost) != hipSuccess) {
-            rc = fail(SBM_ERR_HIP, "k_local_maxima5 failed: %s", hipGetErrorString(hipGetLastError()));
-            goto done;
-        }
+        if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&n, d_cnt.p, 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(SBM_ERR_HIP, "k_local_maxima5 failed: %s", hipGetErrorString(hipGetLastError()));
         if (n > dev_cap) { // more maxima than the buffer holds: once more with room for all of them
             dev_cap = n;
             continue;
         }
         pts.resize((size_t)n);
-        if (n && hipMemcpy(pts.data(), d_xy.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(SBM_ERR_HIP, "download failed");
+        if (n && hipMemcpy(pts.data(), d_xy.p, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(SBM_ERR_HIP, "download failed");
         break;
     }
-    if (!rc) {
-        // row-major order, then the reference's invalidation among equal-score neighbours: a maximum is dropped when an
-        // earlier kept one lies within its 5x5 window (sbm_train_kernels.h).  y << 16 | x sorts row-major as an integer.
-        std::sort(pts.begin(), pts.end());
-        std::vector<int32_t> kept;
-        size_t lo = 0; // first kept point that can still be within two rows of the current one
-        for (int32_t p : pts) {
-            const int y = p >> 16, x = p & 0xffff;
-            while (lo < kept.size() && (kept[lo] >> 16) < y - 2) ++lo;
-            bool ok = true;
-            for (size_t i = lo; i < kept.size() && ok; ++i) ok = std::abs((kept[i] & 0xffff) - x) > 2;
-            if (ok) kept.push_back(p);
-        }
-        *n_out = (int64_t)kept.size();
-        if ((int64_t)kept.size() > cap) rc = fail(SBM_ERR_CAPACITY, "%zu local maxima exceed the capacity %lld", kept.size(), (long long)cap);
-        else
-            for (size_t i = 0; i < kept.size(); ++i) xy[i] = kept[i];
+    // row-major order, then the reference's invalidation among equal-score neighbours: a maximum is dropped when an
+    // earlier kept one lies within its 5x5 window (sbm_train_kernels.h).  y << 16 | x sorts row-major as an integer.
+    std::sort(pts.begin(), pts.end());
+    std::vector<int32_t> kept;
+    size_t lo = 0; // first kept point that can still be within two rows of the current one
+    for (int32_t p : pts) {
+        const int y = p >> 16, x = p & 0xffff;
+        while (lo < kept.size() && (kept[lo] >> 16) < y - 2) ++lo;
+        bool ok = true;
+        for (size_t i = lo; i < kept.size() && ok; ++i) ok = std::abs((kept[i] & 0xffff) - x) > 2;
+        if (ok) kept.push_back(p);
     }
-done:
-    d_mag.release();
-    d_mask.release();
-    d_xy.release();
-    d_cnt.release();
-    return rc;
+    *n_out = (int64_t)kept.size();
+    if ((int64_t)kept.size() > cap) return fail(SBM_ERR_CAPACITY, "%zu local maxima exceed the capacity %lld", kept.size(), (long long)cap);
+    for (size_t i = 0; i < kept.size(); ++i) xy[i] = kept[i];
+    return 0;
 }
 
 int sbm_orientation_bins(sbm_ctx* c, const int16_t* gx, const int16_t* gy, int64_t n, uint8_t* q16)
@@ -104,20 +82,14 @@ int sbm_orientation_bins(sbm_ctx* c, const int16_t* gx, const int16_t* gy, int64
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     DevBuf a, b, o;
     int rc = 0;
-    if ((rc = a.ensure((size_t)n * 2)) || (rc = b.ensure((size_t)n * 2)) || (rc = o.ensure((size_t)n))) goto done;
-    if (hipMemcpy(a.p, gx, (size_t)n * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(b.p, gy, (size_t)n * 2, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+    if ((rc = a.ensure((size_t)n * 2)) || (rc = b.ensure((size_t)n * 2)) || (rc = o.ensure((size_t)n))) return rc;
+    if (hipMemcpy(a.p, gx, (size_t)n * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(b.p, gy, (size_t)n * 2, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_orientation_bins, dim3((unsigned)std::min<int64_t>((n + 255) / 256 + 1, 8192)), dim3(256), 0, c->stream,
                        a.as<int16_t>(), b.as<int16_t>(), n, o.as<uint8_t>());
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(q16, o.p, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "orientation_bins failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    a.release();
-    b.release();
-    o.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "orientation_bins failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_pyrdown(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t ch, uint8_t* out)
@@ -127,19 +99,14 @@ int sbm_pyrdown(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int3
     DevBuf d_in, d_out;
     int rc = 0;
     const size_t nout = (size_t)(rows / 2) * (cols / 2) * ch;
-    if ((rc = d_in.ensure((size_t)rows * cols * ch)) || (rc = d_out.ensure(nout))) goto done;
-    if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+    if ((rc = d_in.ensure((size_t)rows * cols * ch)) || (rc = d_out.ensure(nout))) return rc;
+    if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_pyrdown, dim3((unsigned)std::min<size_t>((nout / ch + 255) / 256, 4096)), dim3(256), 0, c->stream,
                        d_in.as<uint8_t>(), rows, cols, ch, cols * ch, d_out.as<uint8_t>());
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, d_out.p, nout, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "pyrdown failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    d_in.release();
-    d_out.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "pyrdown failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_resize_linear(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_t stride, int32_t ch, double fx, double fy,
@@ -164,28 +131,19 @@ int sbm_resize_linear(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols
     int rc = 0;
     if ((rc = d_in.ensure((size_t)rows * cols * ch)) || (rc = d_out.ensure(nout)) || (rc = d_xi.ensure(xi.size() * 4)) ||
         (rc = d_xa.ensure(xa.size() * 2)) || (rc = d_yi.ensure(yi.size() * 4)) || (rc = d_ya.ensure(ya.size() * 2)))
-        goto done;
+        return rc;
     if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_xi.p, xi.data(), xi.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_xa.p, xa.data(), xa.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(d_yi.p, yi.data(), yi.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ya.p, ya.data(), ya.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+        hipMemcpy(d_ya.p, ya.data(), ya.size() * 2, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_resize_linear_u8, dim3((unsigned)std::min<size_t>((nout + 255) / 256, 4096)), dim3(256), 0, c->stream,
                        d_in.as<uint8_t>(), rows, cols, ch, cols * ch, d_xi.as<int32_t>(), d_xa.as<int16_t>(), d_yi.as<int32_t>(),
                        d_ya.as<int16_t>(), d_out.as<uint8_t>(), dr, dc);
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, d_out.p, nout, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "resize failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    d_in.release();
-    d_out.release();
-    d_xi.release();
-    d_xa.release();
-    d_yi.release();
-    d_ya.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "resize failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_spread(sbm_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32_t T, uint8_t* dst)
@@ -195,19 +153,14 @@ int sbm_spread(sbm_ctx* c, const uint8_t* src, int32_t rows, int32_t cols, int32
     const size_t n = (size_t)rows * cols;
     DevBuf a, b;
     int rc = 0;
-    if ((rc = a.ensure(n)) || (rc = b.ensure(n))) goto done;
-    if (hipMemcpy(a.p, src, n, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+    if ((rc = a.ensure(n)) || (rc = b.ensure(n))) return rc;
+    if (hipMemcpy(a.p, src, n, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_spread, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream,
                        a.as<uint8_t>(), rows, cols, T, b.as<uint8_t>());
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(dst, b.p, n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "spread failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    a.release();
-    b.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "spread failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_compute_response_maps(sbm_ctx* c, const uint8_t* spread, int32_t rows, int32_t cols, uint8_t* maps)
@@ -218,19 +171,14 @@ int sbm_compute_response_maps(sbm_ctx* c, const uint8_t* spread, int32_t rows, i
     const size_t n = (size_t)rows * cols;
     DevBuf a, b;
     int rc = 0;
-    if ((rc = a.ensure(n)) || (rc = b.ensure(8 * n))) goto done;
-    if (hipMemcpy(a.p, spread, n, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+    if ((rc = a.ensure(n)) || (rc = b.ensure(8 * n))) return rc;
+    if (hipMemcpy(a.p, spread, n, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_response, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream,
                        a.as<uint8_t>(), (int64_t)n, b.as<uint8_t>());
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(maps, b.p, 8 * n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "response failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    a.release();
-    b.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "response failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_linearize(sbm_ctx* c, const uint8_t* map, int32_t rows, int32_t cols, int32_t T, uint8_t* lm)
@@ -241,19 +189,14 @@ int sbm_linearize(sbm_ctx* c, const uint8_t* map, int32_t rows, int32_t cols, in
     const size_t n = (size_t)rows * cols;
     DevBuf a, b;
     int rc = 0;
-    if ((rc = a.ensure(n)) || (rc = b.ensure(n))) goto done;
-    if (hipMemcpy(a.p, map, n, hipMemcpyHostToDevice) != hipSuccess) {
-        rc = fail(SBM_ERR_HIP, "upload failed");
-        goto done;
-    }
+    if ((rc = a.ensure(n)) || (rc = b.ensure(n))) return rc;
+    if (hipMemcpy(a.p, map, n, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(SBM_ERR_HIP, "upload failed");
     hipLaunchKernelGGL(k_linearize, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, c->stream,
                        a.as<uint8_t>(), rows, cols, T, b.as<uint8_t>());
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(lm, b.p, n, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "linearize failed: %s", hipGetErrorString(hipGetLastError()));
-done:
-    a.release();
-    b.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "linearize failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_similarity(sbm_ctx* c, int32_t t, uint16_t* dst)
@@ -270,11 +213,9 @@ int sbm_similarity(sbm_ctx* c, int32_t t, uint16_t* dst)
     hipLaunchKernelGGL(k_similarity_map, dim3((W * H + SIM_POS_PER_BLOCK - 1) / SIM_POS_PER_BLOCK), dim3(256), 0, c->stream,
                        c->d_lm[lc].as<uint8_t>(), c->lm_stride[lc], c->rows[lc], c->cols[lc], T, W, H, c->h_tls[(size_t)t * c->L + lc],
                        c->d_fxy.as<uint32_t>(), c->d_foff.as<int32_t>(), d.as<uint16_t>());
-    int rc = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(dst, d.p, (size_t)W * H * 2, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "similarity failed: %s", hipGetErrorString(hipGetLastError()));
-    d.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "similarity failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_similarity_local(sbm_ctx* c, int32_t level, int32_t t, int32_t cx, int32_t cy, uint16_t* dst)
@@ -291,11 +232,9 @@ int sbm_similarity_local(sbm_ctx* c, int32_t level, int32_t t, int32_t cx, int32
     hipLaunchKernelGGL(k_similarity_local_patch, dim3(1), dim3(64 * LOCAL_WAVES), 0, c->stream, c->d_lm[level].as<uint8_t>(),
                        c->lm_stride[level], c->rows[level], c->cols[level], T, W, H, c->h_tls[(size_t)t * c->L + level], c->d_fxy.as<uint32_t>(),
                        c->d_foff.as<int32_t>(), cx, cy, d.as<uint16_t>());
-    int rc = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(dst, d.p, 512, hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(SBM_ERR_HIP, "similarity_local failed: %s", hipGetErrorString(hipGetLastError()));
-    d.release();
-    return rc;
+        return fail(SBM_ERR_HIP, "similarity_local failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 int sbm_set_profiling(sbm_ctx* c, int32_t enabled)
