@@ -240,6 +240,18 @@ public:
                                                   const cv::Mat mask = cv::Mat()) const;
     void matchAsync(const std::vector<cv::Mat>& sources, float threshold,
                     const std::vector<std::string>& class_ids = std::vector<std::string>(), const cv::Mat mask = cv::Mat()) const;
+    /* One mask per frame: the mask of Detector::match belongs to the call (line2Dup.cpp:1078), so a loop of
+     *   match(frame_i, thr, ids, mask_i) becomes one batch.  masks is empty, or holds one entry per frame; an empty Mat means
+     *   no mask for that frame; the others are CV_8UC1 of the frames' size (copied if not continuous).  Element f is exactly
+     *   what match(sources[f], threshold, class_ids, masks[f]) returns (sbm_match_batch_host_begin_masked).  For
+     *   matchAsync the masks, like the frames, must stay alive and unchanged until wait(). */
+    std::vector<std::vector<Match>> matchBatch(const std::vector<cv::Mat>& sources, float threshold,
+                                               const std::vector<std::string>& class_ids, const std::vector<cv::Mat>& masks) const;
+    std::vector<std::vector<Match>> matchBatchNMS(const std::vector<cv::Mat>& sources, float threshold,
+                                                  const std::vector<std::string>& class_ids, float score_threshold,
+                                                  float nms_threshold, float eta, int top_k, const std::vector<cv::Mat>& masks) const;
+    void matchAsync(const std::vector<cv::Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                    const std::vector<cv::Mat>& masks) const;
     std::vector<std::vector<Match>> wait() const;
     void pinBuffer(const cv::Mat& frame) const;
     void unpinBuffer(const cv::Mat& frame) const;
@@ -272,6 +284,16 @@ private:
     int device_id_;
     std::vector<int> device_ids_;
     void dropContext();
+    /* the batch entry points under one shared mask (masks == NULL) or one mask per frame */
+    std::vector<std::vector<Match>> matchBatchImpl(const std::vector<cv::Mat>& sources, float threshold,
+                                                   const std::vector<std::string>& class_ids, const cv::Mat& mask,
+                                                   const std::vector<cv::Mat>* masks) const;
+    std::vector<std::vector<Match>> matchBatchNMSImpl(const std::vector<cv::Mat>& sources, float threshold,
+                                                      const std::vector<std::string>& class_ids, float score_threshold,
+                                                      float nms_threshold, float eta, int top_k, const cv::Mat& mask,
+                                                      const std::vector<cv::Mat>* masks) const;
+    void matchAsyncImpl(const std::vector<cv::Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                        const cv::Mat& mask, const std::vector<cv::Mat>* masks) const;
 };
 
 } // namespace line2Dup

@@ -117,8 +117,9 @@ int sbm_match_sharded(sbm_ctx* const* ctxs, int32_t n_ctx, const uint8_t* img_ho
  * records of frame f at out + f * cap, {n_matches, overflow} at counts + 2 * f.  _begin enqueues everything and
  * returns (uploads from memory that is not pinned are staged by the runtime and may block meanwhile); _end waits and
  * copies the lists out; one batch in flight per context.  The frames and the mask must stay mapped and unchanged
- * from _begin until _end has returned (pinned memory is read by the copy engine during that time).  SBM_ERR_CAPACITY if a frame has more than cap matches (its
- * first cap records are still returned). */
+ * from _begin until _end has returned (pinned memory is read by the copy engine during that time).
+ * SBM_ERR_CAPACITY if a frame has more than cap matches (its first cap records are still returned).
+ * The mask, if any, is shared by the frames; the _masked forms below take one per frame. */
 int sbm_match_batch_host_begin(sbm_ctx* ctx, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols,
                                int32_t stride, int32_t channels, const uint8_t* mask_host, float threshold, int64_t cap,
                                int32_t sub_batch);
@@ -126,6 +127,18 @@ int sbm_match_batch_host_end(sbm_ctx* ctx, sbm_match_rec* out_host, int32_t* cou
 int sbm_match_batch_host(sbm_ctx* ctx, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols,
                          int32_t stride, int32_t channels, const uint8_t* mask_host, float threshold,
                          sbm_match_rec* out_host, int64_t cap, int32_t* counts, int32_t sub_batch);
+/* The same pipeline with one mask per frame: the mask argument of Detector::match belongs to the call (line2Dup.cpp:1078;
+ * quantize() applies it at every level, :446-450), so frame f is matched under masks[f] (rows x cols bytes, non-zero =
+ * keep) exactly as sbm_match(frames[f], ..., masks[f], ...) would.  A NULL entry means no mask for that frame (the
+ * library supplies an all-255 one).  The masks travel with their sub-batch into a second pair of device buffers on the
+ * copy stream and must stay mapped and unchanged until _end, like the frames.  sbm_match_batch_host_end and
+ * sbm_match_batch_host_end_nms end either form. */
+int sbm_match_batch_host_begin_masked(sbm_ctx* ctx, const uint8_t* const* frames, int32_t n_frames, int32_t rows,
+                                      int32_t cols, int32_t stride, int32_t channels, const uint8_t* const* masks_host,
+                                      float threshold, int64_t cap, int32_t sub_batch);
+int sbm_match_batch_host_masked(sbm_ctx* ctx, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols,
+                                int32_t stride, int32_t channels, const uint8_t* const* masks_host, float threshold,
+                                sbm_match_rec* out_host, int64_t cap, int32_t* counts, int32_t sub_batch);
 
 /* Optional: pin a caller-owned host buffer (hipHostRegister) so that sbm_match / sbm_build_pyramid upload frames that
  * lie inside it with one asynchronous DMA instead of the runtime's staged pageable copy (a camera loop that re-uses
@@ -154,11 +167,24 @@ int sbm_match_device(sbm_ctx* ctx, const void* d_img, int32_t rows, int32_t cols
  * the per-launch cost is shared by n_frames frames.  Results of frame f: records at d_out + f * cap,
  * {n_matches, overflow} at d_counts + 2 * f (int32); a result mirror (sbm_set_result_mirror) must hold
  * n_frames * cap records and n_frames * 2 int32, laid out the same way.  The mask, if any, is shared by
- * the frames.  Needs the register-only linear-memory kernel: T in {4, 8}, level widths multiples of 16.
+ * the frames (one mask per frame: sbm_match_batch_device_masked).  Needs the register-only linear-memory kernel: T in {4, 8}, level widths multiples of 16.
  * Each frame's list is what sbm_match_device returns for that frame alone. */
 int sbm_match_batch_device(sbm_ctx* ctx, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows,
                            int32_t cols, int32_t stride, int32_t channels, const void* d_mask, float threshold,
                            void* d_out, int64_t cap, void* d_counts, void* stream);
+
+/* sbm_match_batch_device with one mask per frame: frame f is gradient-quantised under the mask at d_masks +
+ * f * mask_stride bytes (rows x cols, non-zero = keep), as Detector::match(source_f, threshold, class_ids, mask_f)
+ * (line2Dup.cpp:1078) does -- quantize() applies the mask at every level (:446-450) and pyrDown() resizes it to the next
+ * level with nearest-neighbour sampling (:439), level l's mask from level l-1's, frame by frame.  Frame f's list is what
+ * sbm_match_device returns for frame f under mask f.  d_masks must not be NULL.  mask_stride == 0 is exactly
+ * sbm_match_batch_device with that one mask; any other stride must be >= rows * cols (SBM_ERR_INVALID otherwise).  A
+ * replayed graph reads the masks from d_masks at replay time, as it reads the frames; the same pointer with another
+ * stride is another graph. */
+int sbm_match_batch_device_masked(sbm_ctx* ctx, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows,
+                                  int32_t cols, int32_t stride, int32_t channels, const void* d_masks,
+                                  int64_t mask_stride, float threshold, void* d_out, int64_t cap, void* d_counts,
+                                  void* stream);
 
 /* hipGraph replay of an entry point's launches: the kernel sequence of a call is recorded once per distinct argument
  * tuple (stream capture) and replayed with one hipGraphLaunch.
@@ -348,6 +374,10 @@ int sbm_set_quantized(sbm_ctx* ctx, int32_t level, const uint8_t* quantized_host
 /* Read back what a level holds: its one-hot map (rows*cols) and its flat
  * linear memories ([8][lm_stride] bytes; lm_stride >= T*T*W*H, zero tail). */
 int sbm_get_quantized(sbm_ctx* ctx, int32_t level, uint8_t* out_host);
+/* The one-hot map (ColorGradientPyramid::quantize, line2Dup.cpp:446-450: the orientations under the frame's mask) of
+ * frame `frame` of the last batch at `level`; frame 0 is what sbm_get_quantized reads.  SBM_ERR_INVALID for a frame
+ * outside the last batch.  A parity-test accessor, like sbm_get_coarse_bitplanes. */
+int sbm_get_quantized_frame(sbm_ctx* ctx, int32_t level, int32_t frame, uint8_t* out_host);
 int sbm_get_linear_memories(sbm_ctx* ctx, int32_t level, uint8_t* out_host, int64_t cap_bytes,
                             int64_t* lm_stride);
 /* The coarsest level's linear memories as BIT planes (round 4): what the coarse pass reads instead of the reference's

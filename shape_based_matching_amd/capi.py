@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "sbm_set_pipeline_depth", "sbm_set_coarse_mode", "sbm_set_refine_order", "sbm_set_refine_bits", "sbm_get_coarse_bitplanes",
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
+    "sbm_match_batch_device_masked", "sbm_match_batch_host_begin_masked", "sbm_match_batch_host_masked", "sbm_get_quantized_frame",
 ]
 
 
@@ -166,6 +167,10 @@ def lib() -> C.CDLL:
     L.sbm_match.argtypes = [vp, vp, i32, i32, i32, i32, vp, f32, vp, i64, C.POINTER(i64)]
     L.sbm_match_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp]
     L.sbm_match_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp]
+    L.sbm_match_batch_device_masked.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, f32, vp, i64, vp, vp]
+    L.sbm_match_batch_host_begin_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, i64, i32]
+    L.sbm_match_batch_host_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, i32]
+    L.sbm_get_quantized_frame.argtypes = [vp, i32, i32, vp]
     L.sbm_canonicalize.argtypes = [vp, i64]
     L.sbm_canonicalize.restype = i64
     L.sbm_build_pyramid.argtypes = [vp, vp, i32, i32, i32, i32, vp]
@@ -322,6 +327,16 @@ class Context:
                                             C.c_void_p(d_out), cap, C.c_void_p(d_counts),
                                             C.c_void_p(stream) if stream else None))
 
+    def match_batch_device_masked(self, d_imgs: int, frame_stride: int, n_frames: int, rows: int, cols: int, stride: int,
+                                  channels: int, d_masks: int, mask_stride: int, threshold: float, d_out: int, cap: int,
+                                  d_counts: int, stream: int = 0):
+        """match_batch_device with one mask per frame: frame f's mask at d_masks + f*mask_stride bytes (mask_stride 0: one
+        mask shared by the frames)"""
+        _check(lib().sbm_match_batch_device_masked(self._h, C.c_void_p(d_imgs), frame_stride, n_frames, rows, cols, stride,
+                                                   channels, C.c_void_p(d_masks) if d_masks else None, mask_stride,
+                                                   C.c_float(threshold), C.c_void_p(d_out), cap, C.c_void_p(d_counts),
+                                                   C.c_void_p(stream) if stream else None))
+
     def nms_batch_device(self, d_recs: int, d_counts: int, cap: int, n_frames: int, d_out: int, out_cap: int, d_out_counts: int,
                          score_threshold: float, nms_threshold: float, eta: float = 1.0, top_k: int = 0, n_parts: int = 1,
                          part_stride: int = 0, stream: int = 0):
@@ -462,6 +477,34 @@ class Context:
                                               _p(counts), sub_batch))
         return [out[f, : counts[f, 0]].copy() for f in range(len(arrs))]
 
+    def match_batch_host_masked(self, frames: Sequence[np.ndarray], masks: Sequence[Optional[np.ndarray]], threshold: float,
+                                cap: int = 1024, sub_batch: int = 0, split: bool = False, nms: Optional[SbmNmsParams] = None,
+                                out_cap: int = 256):
+        """match_batch_host with one mask per frame (None: no mask for that frame).  Arrays that are already contiguous
+        uint8 are passed as they are (pinned ones stay pinned).  nms: end with sbm_match_batch_host_end_nms instead and
+        return (kept lists, {n_kept, flags} pairs)."""
+        arrs = [_img(f) for f in frames]
+        r, c, ch = arrs[0][1:]
+        assert all(a[1:] == (r, c, ch) for a in arrs) and len(masks) == len(arrs)
+        ms = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in masks]
+        assert all(m is None or m.shape == (r, c) for m in ms)
+        ptrs = (C.c_void_p * len(arrs))(*[a[0].ctypes.data for a in arrs])
+        mptrs = (C.c_void_p * len(arrs))(*[None if m is None else m.ctypes.data for m in ms])
+        counts = np.zeros((len(arrs), 2), np.int32)
+        if nms is not None:
+            out = np.zeros((len(arrs), out_cap), MATCH_DTYPE)
+            _check(lib().sbm_match_batch_host_begin_masked(self._h, ptrs, len(arrs), r, c, c * ch, ch, mptrs, C.c_float(threshold), cap, sub_batch))
+            _check(lib().sbm_match_batch_host_end_nms(self._h, C.byref(nms), _p(out), out_cap, _p(counts)))
+            return [out[f, : counts[f, 0]].copy() for f in range(len(arrs))], counts
+        out = np.zeros((len(arrs), cap), MATCH_DTYPE)
+        if split:
+            _check(lib().sbm_match_batch_host_begin_masked(self._h, ptrs, len(arrs), r, c, c * ch, ch, mptrs, C.c_float(threshold), cap, sub_batch))
+            _check(lib().sbm_match_batch_host_end(self._h, _p(out), _p(counts)))
+        else:
+            _check(lib().sbm_match_batch_host_masked(self._h, ptrs, len(arrs), r, c, c * ch, ch, mptrs, C.c_float(threshold), _p(out), cap,
+                                                     _p(counts), sub_batch))
+        return [out[f, : counts[f, 0]].copy() for f in range(len(arrs))]
+
     def pin_host_buffer(self, a: np.ndarray):
         """explicit opt-in: frames inside ``a`` are uploaded by direct DMA until unpin_host_buffer(a) / close()"""
         _check(lib().sbm_pin_host_buffer(self._h, C.c_void_p(a.ctypes.data), a.nbytes))
@@ -519,6 +562,13 @@ class Context:
         r, c = self.level_dims(level)
         out = np.empty((r, c), np.uint8)
         _check(lib().sbm_get_quantized(self._h, level, _p(out)))
+        return out
+
+    def get_quantized_frame(self, level: int, frame: int) -> np.ndarray:
+        """the one-hot orientation map of frame ``frame`` of the last batch at ``level``"""
+        r, c = self.level_dims(level)
+        out = np.empty((r, c), np.uint8)
+        _check(lib().sbm_get_quantized_frame(self._h, level, frame, _p(out)))
         return out
 
     def get_linear_memories(self, level: int) -> np.ndarray:

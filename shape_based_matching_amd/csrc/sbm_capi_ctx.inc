@@ -162,6 +162,8 @@ struct sbm_ctx {
     int rows[SBM_MAX_LEVELS]{}, cols[SBM_MAX_LEVELS]{};
     int channels = 0;
     int batch = 1;        // frames the per-level buffers, candidate lists and counters are allocated for
+    int mask_frames = 1;  // masks d_mask[l], l >= 1, is allocated for: the batch's frames once a call brought a mask per frame
+    int last_frames = 1;  // frames of the last pyramid built (sbm_get_quantized_frame)
     int levels_valid = 0; // number of levels whose linear memories are resident
     int64_t lm_stride[SBM_MAX_LEVELS]{};
     DevBuf d_img[SBM_MAX_LEVELS], d_mask[SBM_MAX_LEVELS], d_quant[SBM_MAX_LEVELS], d_lm[SBM_MAX_LEVELS];
@@ -208,6 +210,7 @@ struct sbm_ctx {
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_band[8] = {}; // sbm_match: the frame's upload in row bands, one event each
     DevBuf d_in[2], d_bout;
+    DevBuf d_min[2]; // ... and the sub-batch's masks beside its frames (sbm_match_batch_host_begin_masked)
     hipEvent_t ev_up[2] = {}, ev_free[2] = {};
     uint8_t* h_bout = nullptr;
     size_t h_bout_bytes = 0;
@@ -240,6 +243,7 @@ struct sbm_ctx {
         void* mc;
         int frames;       // 0: single-frame graph (sbm_match_device), else the batch size
         int64_t frame_stride;
+        int64_t mask_stride; // bytes between the frames' masks; 0: one shared mask (a different launch for the same pointer)
         hipGraph_t graph;
         hipGraphExec_t exec;
         uint64_t last_use;
@@ -360,11 +364,13 @@ int64_t lbits_frame_bytes(const sbm_ctx* c, int l)
 }
 
 // (re)allocate the per-level buffers for a level-0 geometry
-int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1)
+// frame_masks: the call brings one mask per frame, so levels >= 1 hold `frames` resized masks (else one)
+int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1, bool frame_masks = false)
 {
     if (channels != 1 && channels != 3) return fail(SBM_ERR_INVALID, "channels must be 1 or 3, got %d", channels);
     if (frames < 1 || frames > 65535) return fail(SBM_ERR_INVALID, "batch of %d frames out of range", frames);
-    bool same = c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->d_lm[c->L - 1].p && frames <= c->batch;
+    bool same = c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->d_lm[c->L - 1].p && frames <= c->batch &&
+                (frame_masks ? frames : 1) <= c->mask_frames;
     int r = rows, cc = cols;
     for (int l = 0; l < c->L; ++l) {
         if (l > 0) {
@@ -376,6 +382,7 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
     }
     if (same) return 0;
     const size_t B = (size_t)std::max(frames, c->batch);
+    const size_t MB = (size_t)std::max(frame_masks ? frames : 1, c->mask_frames);
     r = rows;
     cc = cols;
     for (int l = 0; l < c->L; ++l) {
@@ -387,7 +394,7 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
         c->cols[l] = cc;
         c->lm_stride[l] = lm_stride_for(r, cc, c->cfg.T[l]);
         if (int e = c->d_img[l].ensure(B * r * cc * channels)) return e;
-        if (int e = c->d_mask[l].ensure((size_t)r * cc)) return e;
+        if (int e = c->d_mask[l].ensure((l ? MB : 1) * r * cc)) return e; // level 0's: a host entry point's one uploaded mask
         if (int e = c->d_quant[l].ensure(B * r * cc)) return e;
         c->d_lm[l].release(); // fresh, zeroed: the tail past T*T*W*H must read as 0
         if (int e = c->d_lm[l].ensure(B * 8 * c->lm_stride[l], true)) return e;
@@ -409,6 +416,7 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
         if (int e = c->d_counters.ensure(B * CTR_STRIDE * sizeof(int32_t) + 256, true)) return e;
         c->batch = (int)B;
     }
+    c->mask_frames = (int)MB;
     c->channels = channels;
     c->foff_dirty = true;
     c->levels_valid = 0;
@@ -466,9 +474,9 @@ int upload_geo(sbm_ctx* c, hipStream_t s)
 // per Mpixel) and the only one with the float outputs and arbitrary widths.  SBM_QUANTIZE=tile|stream forces one for
 // A/B runs, SBM_QS_HS sets the rows per wave.
 // segment lanes of the packed last strip (0: none); SBM_QS_PACK=0 is the A/B knob
-static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs, int stride)
+static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs, int stride, int64_t mask_fs)
 {
-    const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, ch, frames) : 0;
+    const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, ch, frames, mask_fs) : 0;
     if (!lanes) return 0;
     // the frames of a group are addressed by 32-bit per-lane offsets from the group's first frame: the caller's frame
     // stride (any value, also negative or zero) must keep them within 2 GiB
@@ -479,7 +487,8 @@ static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs,
 
 // rows = the image's rows; band_rows = the output rows of this launch (rows for a whole level; a row band of a
 // build-sharded step otherwise, which always takes the streaming kernel: the tile kernel has no row-range form)
-int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frames, bool wf, int64_t img_fs, int stride, int band_rows = 0)
+int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frames, bool wf, int64_t img_fs, int stride, int band_rows = 0,
+                         int64_t mask_fs = 0)
 {
     const bool band = band_rows > 0 && band_rows < rows;
     const int out_rows = band ? band_rows : rows;
@@ -494,7 +503,7 @@ int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frame
     // takes about  ceil(waves / resident slots) x (hs + 10 halo rows).  Choose the rows per wave that minimise it.
     const int64_t slots = (int64_t)c->n_simd * (ch == 3 ? 3 : 6); // resident waves: 3 per SIMD at the BGR kernel's registers, 6 gray
     // waves per row block: one per strip and frame, except that a narrow last strip is shared by several frames
-    const int pack = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride);
+    const int pack = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride, mask_fs);
     const int64_t per_rb = pack ? (strips - 1) * frames + (frames + 64 / pack - 1) / (64 / pack) : strips * frames;
     int hs = 0;
     int64_t best = INT64_MAX;
@@ -526,8 +535,9 @@ int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frame
 
 int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, int cols, int stride, int ch,
                     const uint8_t* d_mask, float weak, uint8_t* d_out, float* d_mag, float* d_ori, uint8_t* d_pyr,
-                    int frames = 1, int64_t img_fs = 0, int row_lo = 0, int row_hi = -1, bool tile_band = false)
+                    int frames = 1, int64_t img_fs = 0, int row_lo = 0, int row_hi = -1, bool tile_band = false, int64_t mask_fs = 0)
 {
+    if (!d_mask) mask_fs = 0; // mask_fs: bytes between the frames' masks, 0 = one mask for all frames
     if (row_hi < 0) row_hi = rows;
     const bool band = row_lo > 0 || row_hi < rows;
     // tile_band: rows [row_lo, row_hi) as a band of whole rows of 16 x 64 TILES (row_lo a multiple of 16, row_hi too or the
@@ -537,7 +547,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     const float thr_sq = weak * weak;
     const bool wf = d_mag || d_ori;
     const int64_t out_fs = (int64_t)rows * cols, pyr_fs = (int64_t)(rows / 2) * (cols / 2) * ch; // the context's own per-frame buffers
-    if (const int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0)) {
+    if (const int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0, mask_fs)) {
         QSArgs a;
         memset(&a, 0, sizeof a);
         a.img = d_img;
@@ -547,6 +557,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.img_fs = img_fs;
         a.out_fs = out_fs;
         a.pyr_fs = pyr_fs;
+        a.mask_fs = mask_fs;
         a.rows = rows;
         a.cols = cols;
         a.stride = stride;
@@ -557,7 +568,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.n_strips = (cols + QS_USEFUL - 1) / QS_USEFUL;
         a.n_rblocks = (row_hi - row_lo + hs - 1) / hs;
         a.frames = frames;
-        a.pack_lanes = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride);
+        a.pack_lanes = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride, mask_fs);
         a.pack_groups = a.pack_lanes ? (frames + 64 / a.pack_lanes - 1) / (64 / a.pack_lanes) : 0;
         const dim3 g((unsigned)((quantize_stream_items(a) + 3) / 4));
         if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<1>), g, dim3(256), 0, s, a);
@@ -573,10 +584,10 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     do {                                                                                                                    \
         if (many)                                                                                                           \
             SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_THROUGHPUT>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, \
-                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0);              \
+                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);     \
         else                                                                                                                \
             SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
-                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0);                      \
+                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);             \
     } while (0)
     if (ch == 1 && !wf) SBM_QUANTIZE(1, false);
     else if (ch == 1) SBM_QUANTIZE(1, true);
@@ -835,32 +846,39 @@ int check_bands(const sbm_ctx* c, int n_bands)
 // are the caller's cursor down the pyramid: level 0's at first, and the first launch of a level l > 0 (first: the caller
 // says so; further bands of the level find the cursor moved) moves them down -- the mask resized from level l-1's, the
 // image the one level l-1's launch produced (fused cv::pyrDown).  img_fs: bytes between the frames of this level's image.
-int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const uint8_t*& img, int& stride, const uint8_t*& mask, int frames,
-                           int64_t img_fs, int row_lo, int row_hi)
+// mask_fs: bytes between the frames' masks at the cursor's level, 0 = one mask for all frames; a mask per frame stays a mask
+// per frame down the pyramid (pyrDown(), line2Dup.cpp:439: level l's from level l-1's, frame by frame).
+int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const uint8_t*& img, int& stride, const uint8_t*& mask, int64_t& mask_fs,
+                           int frames, int64_t img_fs, int row_lo, int row_hi)
 {
     const int ch = c->channels;
     if (l > 0 && first) {
         if (mask) {
             const int n = c->rows[l] * c->cols[l];
-            SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, mask, c->rows[l - 1],
-                       c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l]);
+            const int64_t dst_fs = mask_fs ? (int64_t)n : 0;
+            if (mask_fs && frames > c->mask_frames) return fail(SBM_ERR_STATE, "level %d holds %d masks, the batch has %d frames", l, c->mask_frames, frames);
+            SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096), mask_fs ? frames : 1), dim3(256), 0, s, mask,
+                       c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l], mask_fs, dst_fs);
             HIP_TRY(hipGetLastError());
             mask = c->d_mask[l].as<uint8_t>();
+            mask_fs = dst_fs;
         }
         img = c->d_img[l].as<uint8_t>();
         stride = c->cols[l] * ch;
     }
     return launch_quantize(c, s, img, c->rows[l], c->cols[l], stride, ch, mask, c->cfg.weak_threshold, c->d_quant[l].as<uint8_t>(), nullptr,
-                           nullptr, l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames, img_fs, row_lo, row_hi);
+                           nullptr, l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames, img_fs, row_lo, row_hi, false, mask_fs);
 }
 
 int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0,
                     int32_t* reset_count = nullptr, int frames = 1, int64_t img0_fs = 0, const Bands* bands = nullptr,
-                    bool level0_gradient_done = false)
+                    bool level0_gradient_done = false, int64_t mask0_fs = 0)
 {
     const uint8_t* img = d_img0;
     int stride = stride0;
     const uint8_t* mask = d_mask0;
+    int64_t mask_fs = d_mask0 ? mask0_fs : 0;
+    c->last_frames = frames;
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
@@ -879,7 +897,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
                 hi = std::min(c->rows[l], (bands->first + b + 1) * br + e);
             }
             const int64_t img_fs = l == 0 ? img0_fs : (int64_t)c->rows[l] * c->cols[l] * c->channels;
-            if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, frames, img_fs, lo, hi)) return e;
+            if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, mask_fs, frames, img_fs, lo, hi)) return e;
         }
         if (!all_rows && frames > 1) return fail(SBM_ERR_INVALID, "batched match needs T in {4, 8} and 16-column-aligned levels");
         if (!all_rows)
@@ -971,6 +989,7 @@ struct MatchCall {
     int32_t* counts;
     int frames;
     int64_t frame_stride;
+    int64_t mask_stride = 0; // bytes from frame f's mask to frame f + 1's; 0: the mask, if any, is shared by the frames
 };
 
 int check_stride(int stride, int cols, int ch)
@@ -984,6 +1003,7 @@ int check_match_call(const sbm_ctx* c, const MatchCall& m)
     if (m.frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
     if (int e = check_stride(m.stride, m.cols, m.ch)) return e;
     if (m.frames > 1 && m.frame_stride < (int64_t)m.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
+    if (m.mask_stride && (!m.mask || m.mask_stride < (int64_t)m.rows * m.cols)) return fail(SBM_ERR_INVALID, "mask_stride smaller than one mask");
     return 0;
 }
 
@@ -993,8 +1013,9 @@ int check_match_call(const sbm_ctx* c, const MatchCall& m)
 // of the call happens here too (it may synchronise), so that the launches can be replayed as a graph.
 int settle_match_state(sbm_ctx* c, const MatchCall& m, const Bands* bands, bool also_dirty)
 {
-    if (match_dirty(c, m.rows, m.cols, m.ch, m.frames, m.thr) || also_dirty) HIP_TRY(hipDeviceSynchronize());
-    if (int e = ensure_geometry(c, m.rows, m.cols, m.ch, m.frames)) return e;
+    const bool frame_masks = m.mask_stride != 0;
+    if (match_dirty(c, m.rows, m.cols, m.ch, m.frames, m.thr) || also_dirty || (frame_masks && m.frames > c->mask_frames)) HIP_TRY(hipDeviceSynchronize());
+    if (int e = ensure_geometry(c, m.rows, m.cols, m.ch, m.frames, frame_masks)) return e;
     if (bands)
         if (int e = check_bands(c, bands->n)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
@@ -1294,7 +1315,7 @@ bool graph_key_equal(const sbm_ctx::GraphEntry& g, const sbm_ctx::GraphEntry& k)
 {
     return g.img == k.img && g.rows == k.rows && g.cols == k.cols && g.stride == k.stride && g.ch == k.ch && g.mask == k.mask &&
            g.thr_bits == k.thr_bits && g.out == k.out && g.cap == k.cap && g.count == k.count && g.mo == k.mo && g.mc == k.mc &&
-           g.frames == k.frames && g.frame_stride == k.frame_stride;
+           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride;
 }
 
 constexpr size_t GRAPH_CACHE = 16;
@@ -1375,7 +1396,7 @@ void record_match(sbm_ctx* c, bool one_launch)
 // every launch of a match call, in order
 int enqueue_match(sbm_ctx* c, hipStream_t s, const MatchCall& m, const Bands* bands = nullptr, bool level0_gradient_done = false)
 {
-    if (int e = enqueue_pyramid(c, s, m.img, m.stride, m.mask, m.counts, m.frames, m.frame_stride, bands, level0_gradient_done)) return e;
+    if (int e = enqueue_pyramid(c, s, m.img, m.stride, m.mask, m.counts, m.frames, m.frame_stride, bands, level0_gradient_done, m.mask_stride)) return e;
     return enqueue_loop(c, s, m.out, m.cap, m.counts, m.frames, false);
 }
 
@@ -1391,9 +1412,10 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
     const uint8_t* img = m.img;
     int stride = m.stride;
     const uint8_t* mask = m.mask;
+    int64_t mask_fs = 0; // one frame
     bool forked = false;
     for (int l = 0; l < L; ++l) {
-        if (int e = enqueue_gradient_level(c, st, l, true, img, stride, mask, 1, 0, 0, c->rows[l])) return e; // one frame: no frame stride
+        if (int e = enqueue_gradient_level(c, st, l, true, img, stride, mask, mask_fs, 1, 0, 0, c->rows[l])) return e; // one frame: no frame stride
         const bool fork = l < L - 1 && tuning().graph_fork;
         if (fork && (hipEventRecord(c->ev_fork[l], st) != hipSuccess || hipStreamWaitEvent(sd, c->ev_fork[l], 0) != hipSuccess))
             return fail(SBM_ERR_HIP, "graph fork failed");
@@ -1414,7 +1436,7 @@ sbm_ctx::GraphEntry graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     memcpy(&thr_bits, &m.thr, 4);
     // (the template loop has no frame stride: what its launches depend on instead is the form every level is held in)
     return sbm_ctx::GraphEntry{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
-                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, nullptr, nullptr, 0};
+                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0};
 }
 
 // The launches of a match call on stream s: a replay of the graph captured for its argument tuple where one is wanted --
@@ -1446,7 +1468,10 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
         if (launched) {
             // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is captured only
             // where the one-launch builder takes every level; the template loop builds nothing
-            if (kind >= 0) record_match(c, kind > 0);
+            if (kind >= 0) {
+                record_match(c, kind > 0);
+                c->last_frames = m.frames;
+            }
             return 0;
         }
     }

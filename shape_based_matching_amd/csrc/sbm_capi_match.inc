@@ -287,6 +287,18 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
     return match_or_replay(c, s, m, n_frames);
 }
 
+int sbm_match_batch_device_masked(sbm_ctx* c, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows, int32_t cols,
+                                  int32_t stride, int32_t channels, const void* d_masks, int64_t mask_stride, float threshold, void* d_out,
+                                  int64_t cap, void* d_counts, void* stream)
+{
+    if (!d_masks) return fail(SBM_ERR_INVALID, "null masks (sbm_match_batch_device matches without one)");
+    const MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_masks, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames, frame_stride, mask_stride};
+    if (int e = check_match_call(c, m)) return e;
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s)) return e;
+    return match_or_replay(c, s, m, n_frames);
+}
+
 int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
 {
     if (!c || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");
@@ -398,8 +410,12 @@ static int upload_image(sbm_ctx* c, const uint8_t* img, int rows, int cols, int 
     return 0;
 }
 
-int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
-                               int32_t channels, const uint8_t* mask, float threshold, int64_t cap, int32_t sub_batch)
+} // extern "C"
+
+// sbm_match_batch_host_begin (mask: one for all frames, or NULL) and sbm_match_batch_host_begin_masked (masks: one pointer per
+// frame, a NULL entry = no mask for that frame)
+static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                            int32_t channels, const uint8_t* mask, const uint8_t* const* masks, float threshold, int64_t cap, int32_t sub_batch)
 {
     if (!c || !frames || n_frames < 1 || cap < 1) return fail(SBM_ERR_INVALID, "bad batch arguments");
     if (c->pending.active) return fail(SBM_ERR_STATE, "a host batch is already in flight (call sbm_match_batch_host_end)");
@@ -407,9 +423,11 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     for (int f = 0; f < n_frames; ++f)
         if (!frames[f]) return fail(SBM_ERR_INVALID, "frame %d is null", f);
     int sub = std::max(1, std::min(sub_batch > 0 ? sub_batch : 8, n_frames));
-    const size_t frame_bytes = (size_t)rows * cols * channels;
+    const size_t frame_bytes = (size_t)rows * cols * channels, mask_bytes = (size_t)rows * cols;
     // one sub-batch: frames from an input buffer of the pipeline, packed; image, results and frame count follow per sub-batch
-    MatchCall m{nullptr, rows, cols, cols * channels, channels, nullptr, threshold, nullptr, cap, nullptr, sub, (int64_t)frame_bytes};
+    // (and its masks, one per frame, from the mask buffer beside that input buffer)
+    MatchCall m{nullptr, rows, cols, cols * channels, channels, nullptr, threshold, nullptr, cap, nullptr, sub, (int64_t)frame_bytes,
+                masks ? (int64_t)mask_bytes : 0};
     if (int e = begin_host_match(c, m, c->citems_dirty)) return e;
     // geometries the one-launch linear-memory builder does not take (level widths that are not multiples of 16, other
     // strides): one frame per "sub-batch" through the generic kernels -- the uploads still overlap the kernels
@@ -417,6 +435,8 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     if (int e = ensure_copy_stream(c)) return e;
     for (int i = 0; i < 2; ++i)
         if (int e = c->d_in[i].ensure((size_t)sub * frame_bytes)) return e;
+    for (int i = 0; i < 2 && masks; ++i)
+        if (int e = c->d_min[i].ensure((size_t)sub * mask_bytes)) return e;
     // results: n_frames blocks of cap records, then n_frames {n_matches, overflow} pairs -- on the device and in pinned memory
     const size_t rec_bytes = (size_t)n_frames * (size_t)cap * sizeof(sbm_match_rec), total = rec_bytes + (size_t)n_frames * 8;
     if (int e = c->d_bout.ensure(total)) return e;
@@ -454,12 +474,20 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
             if (he != hipSuccess) rc = fail(SBM_ERR_HIP, "frame upload failed: %s", hipGetErrorString(he));
             f += run;
         }
+        // the sub-batch's masks travel with it; a frame without one gets an all-255 mask (quantize() keeps every pixel)
+        for (int f = 0; f < nf && !rc && masks; ++f) {
+            uint8_t* dst = c->d_min[buf].as<uint8_t>() + (size_t)f * mask_bytes;
+            const hipError_t he = masks[f0 + f] ? hipMemcpyAsync(dst, masks[f0 + f], mask_bytes, hipMemcpyHostToDevice, c->copy_stream)
+                                                : hipMemsetAsync(dst, 255, mask_bytes, c->copy_stream);
+            if (he != hipSuccess) rc = fail(SBM_ERR_HIP, "mask upload failed: %s", hipGetErrorString(he));
+        }
         if (rc) break;
         if (hipEventRecord(c->ev_up[buf], c->copy_stream) != hipSuccess || hipStreamWaitEvent(c->stream, c->ev_up[buf], 0) != hipSuccess) {
             rc = fail(SBM_ERR_HIP, "event record / wait failed");
             break;
         }
         m.img = c->d_in[buf].as<uint8_t>();
+        if (masks) m.mask = c->d_min[buf].as<uint8_t>();
         m.out = c->d_bout.as<sbm_match_rec>() + (size_t)f0 * cap;
         m.counts = (int32_t*)((char*)c->d_bout.p + rec_bytes) + 2 * f0;
         m.frames = nf;
@@ -475,6 +503,21 @@ int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t
     c->pending.n_frames = n_frames;
     c->pending.cap = cap;
     return 0;
+}
+
+extern "C" {
+
+int sbm_match_batch_host_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                               int32_t channels, const uint8_t* mask, float threshold, int64_t cap, int32_t sub_batch)
+{
+    return host_batch_begin(c, frames, n_frames, rows, cols, stride, channels, mask, nullptr, threshold, cap, sub_batch);
+}
+
+int sbm_match_batch_host_begin_masked(sbm_ctx* c, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                      int32_t channels, const uint8_t* const* masks, float threshold, int64_t cap, int32_t sub_batch)
+{
+    if (!masks) return fail(SBM_ERR_INVALID, "null mask list (sbm_match_batch_host_begin matches without one)");
+    return host_batch_begin(c, frames, n_frames, rows, cols, stride, channels, nullptr, masks, threshold, cap, sub_batch);
 }
 
 int sbm_match_batch_host_end(sbm_ctx* c, sbm_match_rec* out, int32_t* counts)
@@ -508,6 +551,15 @@ int sbm_match_batch_host(sbm_ctx* c, const uint8_t* const* frames, int32_t n_fra
 {
     if (!out || !counts) return fail(SBM_ERR_INVALID, "null argument");
     if (int e = sbm_match_batch_host_begin(c, frames, n_frames, rows, cols, stride, channels, mask, threshold, cap, sub_batch)) return e;
+    return sbm_match_batch_host_end(c, out, counts);
+}
+
+int sbm_match_batch_host_masked(sbm_ctx* c, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                int32_t channels, const uint8_t* const* masks, float threshold, sbm_match_rec* out, int64_t cap,
+                                int32_t* counts, int32_t sub_batch)
+{
+    if (!out || !counts) return fail(SBM_ERR_INVALID, "null argument");
+    if (int e = sbm_match_batch_host_begin_masked(c, frames, n_frames, rows, cols, stride, channels, masks, threshold, cap, sub_batch)) return e;
     return sbm_match_batch_host_end(c, out, counts);
 }
 
@@ -707,6 +759,18 @@ int sbm_get_quantized(sbm_ctx* c, int32_t level, uint8_t* out)
     if (int e = order_after_caller_work(c)) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, c->d_quant[level].p, (size_t)c->rows[level] * c->cols[level], hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sbm_get_quantized_frame(sbm_ctx* c, int32_t level, int32_t frame, uint8_t* out)
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    if (level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
+    if (frame < 0 || frame >= c->last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->last_frames);
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    HIP_TRY(hipDeviceSynchronize()); // the batch may have been built on the caller's stream
+    const size_t n = (size_t)c->rows[level] * c->cols[level];
+    HIP_TRY(hipMemcpy(out, c->d_quant[level].as<uint8_t>() + (size_t)frame * n, n, hipMemcpyDeviceToHost));
     return 0;
 }
 

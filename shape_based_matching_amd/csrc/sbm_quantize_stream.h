@@ -55,7 +55,7 @@ constexpr int QS_PREFETCH = 4;                                   // source rows 
 
 struct QSArgs {
     const uint8_t* img;  // frame 0, level image, `stride` bytes per row, CH interleaved channels
-    const uint8_t* mask; // rows x cols, may be null
+    const uint8_t* mask; // frame 0's, rows x cols, may be null
     uint8_t* out;        // rows x cols one-hot orientation bytes
     uint8_t* pyr;        // (rows/2) x (cols/2) x CH, may be null
     int64_t img_fs, out_fs, pyr_fs; // bytes from one frame of the batch to the next
@@ -75,6 +75,7 @@ struct QSArgs {
     // Same rows, same columns, so every scalar decision of the row loop is unchanged; only the per-lane column and
     // the per-lane frame offset of loads and stores differ.  pack_groups = frame groups per row block.
     int32_t pack_lanes, pack_groups;
+    int64_t mask_fs;     // bytes from one frame's mask to the next; 0: the frames share one mask (and 0 when mask is null)
 };
 
 // Gaussian / pyrDown weights as packed pairs (lo | hi << 16)
@@ -133,6 +134,9 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
     uint8_t* out = a.out + (int64_t)frame * a.out_fs;
     uint8_t* pyr = a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;
+    // the frame's own mask (quantize(): one mask per match() call).  No select on a.mask: without a mask mask_fs is 0, so the
+    // sum is the null pointer itself and takes the argument's place in the scalar registers -- nothing more stays live
+    const uint8_t* mask = a.mask + (int64_t)frame * a.mask_fs;
     const int drows = rows >> 1, dcols = cols >> 1;
 
     // ---- per-lane constants ----
@@ -148,6 +152,9 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     const V c0 = splat((uint32_t)cb) + (lseg << 2);       // first column of this lane (may be negative / >= cols)
     const V lcol = clamp_i(c0, 0, cols - 4);              // column actually loaded (BORDER_REPLICATE)
     const V ld_off = (CH == 3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs; // byte offset from the frame's source row
+    // ... from the mask row of the group's first frame: segment g reads frame f0 + g's own mask; idle segments (segc = 0)
+    // re-read the first frame's, never a mask past the last frame.  Once per work item, not per row.
+    const V mk_off = lcol + segc * (uint32_t)a.mask_fs;
     const P left_out = lt_i(c0, splat(0u)), right_out = ge_i(c0, splat((uint32_t)cols));
     const P outside = p_or(left_out, right_out);
     const bool border_strip = nseg || cb < 0 || cb + 256 > cols; // some lane replicates the first / last pixel
@@ -475,8 +482,8 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
                     w[j] = qs_vote_word(bv[j], p_and(real_col[j], ne(bv[j], splat(0u))));
                     smc[j] = select(gt_i(bm[j], splat((uint32_t)a.thr_i)), cm[j], 0u);
                 }
-                if (a.mask) { // quantize(): angle.copyTo(dst, mask)
-                    const V mw = load_u32(a.mask + (int64_t)ys * cols, lcol);
+                if (mask) { // quantize(): angle.copyTo(dst, mask), the frame's own mask (one per match() call)
+                    const V mw = load_u32(mask + (int64_t)ys * cols, mk_off);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) smc[j] = select(ne(mw & (0xffu << (8 * j)), splat(0u)), smc[j], 0u);
                 }
@@ -562,13 +569,16 @@ __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
 }
 
 // segment lanes of a packed last strip for this geometry, 0 = the last strip gets a wave per frame like the others
-__host__ __device__ inline int quantize_stream_pack_lanes(int rows, int cols, int ch, int frames)
+// mask_fs: bytes between the frames' masks (0: none, or one shared mask)
+__host__ __device__ inline int quantize_stream_pack_lanes(int rows, int cols, int ch, int frames, int64_t mask_fs = 0)
 {
     const int n_strips = (cols + QS_USEFUL - 1) / QS_USEFUL;
     const int lanes = (cols - QS_USEFUL * (n_strips - 1)) / QS_LANE_PX + 2 * QS_HALO_LANES;
     const int per = 64 / lanes;
     // per-lane offsets are 32-bit: the frames of a group must lie within 2 GiB of the first
     if (frames < 2 || per < 2 || (long long)per * rows * cols * ch >= 0x7ff00000ll) return 0;
+    // ... and so must their masks
+    if (mask_fs < 0 || mask_fs >= 0x7ff00000ll / per) return 0;
     return lanes;
 }
 

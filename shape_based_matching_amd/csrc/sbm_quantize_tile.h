@@ -175,9 +175,11 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
                                                   float thr_sq, uint8_t* __restrict__ out,
                                                   float* __restrict__ mag_out, float* __restrict__ ori_out,
                                                   uint8_t* __restrict__ pyr_out, int64_t img_fs, int64_t out_fs,
-                                                  int64_t pyr_fs, int tile_row0)
+                                                  int64_t pyr_fs, int tile_row0, int64_t mask_fs)
 {
-    // a batch of frames of one geometry: frame = blockIdx.z, *_fs = bytes from one frame to the next
+    // a batch of frames of one geometry: frame = blockIdx.z, *_fs = bytes from one frame to the next (mask_fs = 0: the
+    // frames share one mask)
+    if (mask) mask += (int64_t)blockIdx.z * mask_fs;
     img += (size_t)blockIdx.z * img_fs;
     out += (size_t)blockIdx.z * out_fs;
     if (pyr_out) pyr_out += (size_t)blockIdx.z * pyr_fs;
@@ -691,10 +693,13 @@ __global__ __launch_bounds__(256) void k_resize_linear_u8(const uint8_t* __restr
     }
 }
 
+// frame = blockIdx.y: one mask per frame, src_fs / dst_fs bytes apart (a shared mask is a grid of one frame)
 __global__ __launch_bounds__(256) void k_resize_mask(const uint8_t* __restrict__ src, int rows, int cols,
-                                                     uint8_t* __restrict__ dst, int drows, int dcols)
+                                                     uint8_t* __restrict__ dst, int drows, int dcols, int64_t src_fs, int64_t dst_fs)
 {
     top_wave_priority(); // a small kernel between two gradient launches of its batch
+    src += (int64_t)blockIdx.y * src_fs;
+    dst += (int64_t)blockIdx.y * dst_fs;
     const double fx = (double)cols / dcols, fy = (double)rows / drows;
     const int n = drows * dcols;
     for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {

@@ -19,6 +19,10 @@
 //   demo batch <templ_fmt> <class_id> <image> <threshold> <num_features> <n_frames> <pad> <devices>
 //       MI355X extensions: matchBatch / matchAsync+wait over n_frames shifted copies of the image against per-frame match(),
 //       and match() with setDevices(<devices>, e.g. 0,0) against the single-context match()
+//   demo maskbatch <templ_fmt> <class_id> <image> <threshold> <num_features> <n_frames> <pad> <devices>
+//       one mask per frame: matchBatch / matchAsync+wait / matchBatchNMS / setDevices + matchBatch with a vector of masks
+//       against per-frame match(frame_f, threshold, ids, mask_f); the frames of `batch`, masks that contain the object, cut it,
+//       are absent (empty Mat) or are a non-continuous view, in turn
 //   demo instance <config.yaml> <image> <threshold>
 //       Detector::getInstance(path) (line2Dup.cpp:1366-1393) + match over the classes the config lists
 #include <chrono>
@@ -332,6 +336,86 @@ int main(int argc, char** argv)
                 memcpy(&bits, &m.similarity, 4);
                 printf("%d %d %u %s %d\n", m.x, m.y, bits, m.class_id.c_str(), m.template_id);
             }
+            return 0;
+        }
+        if (mode == "maskbatch") {
+            if (argc < 10) return usage();
+            const std::string fmt = argv[2], class_id = argv[3], path = argv[4];
+            const float threshold = (float)atof(argv[5]);
+            const int num_features = atoi(argv[6]), nf = atoi(argv[7]), pad = atoi(argv[8]);
+            std::vector<int> devices;
+            for (const char* p = argv[9]; *p;) {
+                devices.push_back(atoi(p));
+                while (*p && *p != ',') ++p;
+                if (*p == ',') ++p;
+            }
+            line2Dup::Detector detector(num_features, {4, 8});
+            std::vector<std::string> ids{class_id};
+            detector.readClasses(ids, fmt);
+            Mat test_img = imread(path, IMREAD_UNCHANGED);
+            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
+            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
+            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
+            Mat img = padded(Rect(0, 0, 16 * (padded.cols / 16), 16 * (padded.rows / 16))).clone();
+            // frame b = the image shifted 8 b columns to the right (wrapping), as in `batch`
+            std::vector<Mat> frames, masks;
+            const int esz = img.channels();
+            Mat wide(img.rows, img.cols + 24, CV_8UC1, Scalar::all(255)); // the parent of the non-continuous masks
+            for (int y = img.rows / 2; y < img.rows; ++y) memset(wide.ptr(y), 0, (size_t)wide.cols);
+            for (int b = 0; b < nf; ++b) {
+                Mat f(img.rows, img.cols, img.type());
+                const int sh = (8 * b) % img.cols;
+                for (int y = 0; y < img.rows; ++y) {
+                    memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
+                    memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
+                }
+                frames.push_back(f);
+                Mat m(img.rows, img.cols, CV_8UC1, Scalar::all(0));
+                if (b % 4 == 0) { // contains the object
+                    for (int y = pad / 2; y < img.rows - pad / 2; ++y) memset(m.ptr(y), 255, (size_t)m.cols);
+                } else if (b % 4 == 1) { // cuts it: the left two thirds of the frame
+                    for (int y = 0; y < img.rows; ++y) memset(m.ptr(y), 1, (size_t)(2 * m.cols / 3));
+                } else if (b % 4 == 2) { // no mask for this frame
+                    m = Mat();
+                } else { // a view that is not continuous: the upper half
+                    m = wide(Rect(12, 0, img.cols, img.rows));
+                }
+                masks.push_back(m);
+            }
+            auto same = [](const std::vector<line2Dup::Match>& a, const std::vector<line2Dup::Match>& b) {
+                if (a.size() != b.size()) return false;
+                for (size_t i = 0; i < a.size(); ++i)
+                    if (!(a[i] == b[i]) || a[i].template_id != b[i].template_id) return false;
+                return true;
+            };
+            std::vector<std::vector<line2Dup::Match>> single;
+            for (size_t f = 0; f < frames.size(); ++f) single.push_back(detector.match(frames[f], threshold, ids, masks[f]));
+            const auto batch = detector.matchBatch(frames, threshold, ids, masks);
+            detector.matchAsync(frames, threshold, ids, masks);
+            const auto async = detector.wait();
+            // thresholds that keep every record: the device epilogue alone, which match() has applied already
+            const auto nms = detector.matchBatchNMS(frames, threshold, ids, -1.f, 1.f, 1.f, 0, masks);
+            line2Dup::Detector multi(num_features, {4, 8});
+            multi.readClasses(ids, fmt);
+            multi.setDevices(devices);
+            const auto mb = multi.matchBatch(frames, threshold, ids, masks);
+            // no masks at all through the new overload = the batch without a mask
+            const auto plain = detector.matchBatch(frames, threshold, ids, std::vector<Mat>());
+            int ok_batch = batch.size() == single.size(), ok_async = async.size() == single.size(), ok_nms = nms.size() == single.size(),
+                ok_dev = mb.size() == single.size(), ok_plain = plain.size() == single.size(), distinct = 0;
+            size_t total = 0;
+            for (size_t f = 0; f < single.size(); ++f) {
+                ok_batch = ok_batch && same(batch[f], single[f]);
+                ok_async = ok_async && same(async[f], single[f]);
+                ok_nms = ok_nms && same(nms[f], single[f]);
+                ok_dev = ok_dev && same(mb[f], single[f]);
+                ok_plain = ok_plain && same(plain[f], detector.match(frames[f], threshold, ids));
+                distinct += !same(single[f], plain[f]); // frames whose mask changes their list
+                total += single[f].size();
+            }
+            printf("maskbatch frames %d matches %zu masks_matter %d batch_same %d async_same %d nms_same %d devices %zu devices_batch_same %d no_masks_same %d\n",
+                   nf, total, distinct, ok_batch, ok_async, ok_nms, devices.size(), ok_dev, ok_plain);
+            for (size_t f = 0; f < single.size(); ++f) printf("frame %zu matches %zu\n", f, single[f].size());
             return 0;
         }
         if (mode == "threads") {

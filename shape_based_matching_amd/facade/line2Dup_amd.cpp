@@ -320,6 +320,7 @@ struct Detector::Engine {
         size_t n_frames = 0;
         std::vector<Mat> sources;
         Mat mask8;
+        std::vector<Mat> masks8; // one per frame (the overloads that take a vector of masks), else empty
         float threshold = 0.f;
         std::shared_ptr<const Flat> flat;
     } async;
@@ -614,7 +615,53 @@ std::vector<Match> Detector::match(Mat source, float threshold, const std::vecto
 }
 
 // ---- throughput path: batches of frames from host memory, uploads overlapped with the kernels ----------------------
+// One mask per frame (the overloads that take a vector of masks: the mask of Detector::match belongs to the call,
+// line2Dup.cpp:1078): empty, or one entry per frame; an entry is empty (no mask for that frame) or CV_8UC1 of the frames'
+// size, and is copied if it is not continuous.
+static std::vector<Mat> frame_masks8(const std::vector<Mat>* masks, const Mat& s0, size_t n_frames)
+{
+    std::vector<Mat> out;
+    if (!masks || masks->empty()) return out;
+    CV_Assert(masks->size() == n_frames);
+    for (const Mat& m : *masks) {
+        CV_Assert(m.empty() || (m.size() == s0.size() && m.type() == CV_8UC1));
+        out.push_back(m.empty() || m.isContinuous() ? m : m.clone());
+    }
+    return out;
+}
+
+// the mask frame f is matched under
+static const Mat& mask_of_frame(const Mat& mask8, const std::vector<Mat>& masks8, size_t f) { return masks8.empty() ? mask8 : masks8[f]; }
+
+// sbm_match_batch_host_begin for the frames [first, first + count) of a batch (one context's share): under the one shared
+// mask, or each frame under its own
+static int begin_frames(sbm_ctx* ctx, const std::vector<Mat>& sources, int first, int count, const Mat& mask8, const std::vector<Mat>& masks8,
+                        float threshold, int64_t cap)
+{
+    const Mat& s0 = sources[0];
+    std::vector<const uint8_t*> ptrs, mptrs;
+    for (int f = 0; f < count; ++f) ptrs.push_back(sources[(size_t)(first + f)].data);
+    if (masks8.empty())
+        return sbm_match_batch_host_begin(ctx, ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(),
+                                          mask8.empty() ? nullptr : mask8.data, threshold, cap, 0);
+    for (int f = 0; f < count; ++f) mptrs.push_back(masks8[(size_t)(first + f)].empty() ? nullptr : masks8[(size_t)(first + f)].data);
+    return sbm_match_batch_host_begin_masked(ctx, ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(), mptrs.data(),
+                                             threshold, cap, 0);
+}
+
 void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids, const Mat mask) const
+{
+    matchAsyncImpl(sources, threshold, class_ids, mask, nullptr);
+}
+
+void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                          const std::vector<Mat>& masks) const
+{
+    matchAsyncImpl(sources, threshold, class_ids, Mat(), &masks);
+}
+
+void Detector::matchAsyncImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids, const Mat& mask,
+                              const std::vector<Mat>* masks) const
 {
     CV_Assert(!sources.empty());
     const Mat& s0 = sources[0];
@@ -653,6 +700,7 @@ void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, cons
         // when it is not continuous) are kept until wait(): the uploads enqueued below read them after this call returns
         as.sources = sources;
         if (!mask.empty()) as.mask8 = mask.isContinuous() ? mask : mask.clone();
+        as.masks8 = frame_masks8(masks, s0, sources.size());
         // frames dealt over the devices in contiguous groups (frames are independent: Detector::match keeps no state)
         const int D = (int)lane.ctxs.size(), n = (int)sources.size();
         as.cap = 1024;
@@ -662,10 +710,7 @@ void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, cons
         }
         for (int d = 0; d < D; ++d) {
             if (!as.count[d]) continue;
-            std::vector<const uint8_t*> ptrs;
-            for (int f = 0; f < as.count[d]; ++f) ptrs.push_back(sources[as.first[d] + f].data);
-            const int rc = sbm_match_batch_host_begin(lane.ctxs[d], ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(),
-                                                      as.mask8.empty() ? nullptr : as.mask8.data, threshold, as.cap, 0);
+            const int rc = begin_frames(lane.ctxs[d], sources, as.first[d], as.count[d], as.mask8, as.masks8, threshold, as.cap);
             if (rc) {
                 const std::string msg = sbm_last_error();
                 for (int k = 0; k < d; ++k) { // drain what was started
@@ -731,7 +776,7 @@ std::vector<std::vector<Match>> Detector::wait() const
         Engine::Lane single;
         single.ctxs.assign(1, lane.ctxs[0]);
         for (size_t f : redo) {
-            const int64_t n = match_on_lane(single, as.sources[f], as.mask8, as.threshold);
+            const int64_t n = match_on_lane(single, as.sources[f], mask_of_frame(as.mask8, as.masks8, f), as.threshold);
             out[f] = to_matches(*as.flat, single.recs.data(), n);
         }
     }
@@ -740,6 +785,18 @@ std::vector<std::vector<Match>> Detector::wait() const
 
 std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                      const Mat mask) const
+{
+    return matchBatchImpl(sources, threshold, class_ids, mask, nullptr);
+}
+
+std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                                     const std::vector<Mat>& masks) const
+{
+    return matchBatchImpl(sources, threshold, class_ids, Mat(), &masks);
+}
+
+std::vector<std::vector<Match>> Detector::matchBatchImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                                         const Mat& mask, const std::vector<Mat>* masks) const
 {
     if (sources.empty()) return std::vector<std::vector<Match>>();
     // not matchAsync + wait: several threads may run batches on one detector at once, each on a lane of its own, while
@@ -760,6 +817,7 @@ std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sou
     Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
     Mat mask8;
     if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
+    const std::vector<Mat> masks8 = frame_masks8(masks, s0, sources.size());
     const int D = (int)lane.ctxs.size(), n = (int)sources.size();
     const int64_t cap = 1024;
     std::vector<int> first, count;
@@ -771,10 +829,7 @@ std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sou
     std::string msg;
     for (int d = 0; d < D && !bad; ++d, ++begun) {
         if (!count[d]) continue;
-        std::vector<const uint8_t*> ptrs;
-        for (int f = 0; f < count[d]; ++f) ptrs.push_back(sources[first[d] + f].data);
-        const int rc = sbm_match_batch_host_begin(lane.ctxs[d], ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(),
-                                                  mask8.empty() ? nullptr : mask8.data, threshold, cap, 0);
+        const int rc = begin_frames(lane.ctxs[d], sources, first[d], count[d], mask8, masks8, threshold, cap);
         if (rc) {
             bad = rc;
             msg = std::string("sbm_match_batch_host_begin: ") + sbm_last_error();
@@ -805,7 +860,7 @@ std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sou
         Engine::Lane single;
         single.ctxs.assign(1, lane.ctxs[0]);
         for (size_t f : redo) {
-            const int64_t k = match_on_lane(single, sources[f], mask8, threshold);
+            const int64_t k = match_on_lane(single, sources[f], mask_of_frame(mask8, masks8, f), threshold);
             out[f] = to_matches(*flat, single.recs.data(), k);
         }
     }
@@ -825,6 +880,20 @@ static std::vector<Match> kept_to_matches(const Detector::Engine::Flat& flat, co
 std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                         float score_threshold, float nms_threshold, float eta, int top_k, const Mat mask) const
 {
+    return matchBatchNMSImpl(sources, threshold, class_ids, score_threshold, nms_threshold, eta, top_k, mask, nullptr);
+}
+
+std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                                        float score_threshold, float nms_threshold, float eta, int top_k,
+                                                        const std::vector<Mat>& masks) const
+{
+    return matchBatchNMSImpl(sources, threshold, class_ids, score_threshold, nms_threshold, eta, top_k, Mat(), &masks);
+}
+
+std::vector<std::vector<Match>> Detector::matchBatchNMSImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                                            float score_threshold, float nms_threshold, float eta, int top_k, const Mat& mask,
+                                                            const std::vector<Mat>* masks) const
+{
     if (sources.empty()) return std::vector<std::vector<Match>>();
     const Mat& s0 = sources[0];
     for (const Mat& m : sources) {
@@ -842,6 +911,7 @@ std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& 
     Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
     Mat mask8;
     if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
+    const std::vector<Mat> masks8 = frame_masks8(masks, s0, sources.size());
     const int D = (int)lane.ctxs.size(), n = (int)sources.size();
     const int64_t cap = 1024, out_cap = cap; // the kept list is a subsequence of the raw list: out_cap = cap always fits
     sbm_nms_params prm;
@@ -858,10 +928,7 @@ std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& 
     std::string msg;
     for (int d = 0; d < D && !bad; ++d, ++begun) {
         if (!count[d]) continue;
-        std::vector<const uint8_t*> ptrs;
-        for (int f = 0; f < count[d]; ++f) ptrs.push_back(sources[first[d] + f].data);
-        const int rc = sbm_match_batch_host_begin(lane.ctxs[d], ptrs.data(), (int32_t)ptrs.size(), s0.rows, s0.cols, (int)s0.step, s0.channels(),
-                                                  mask8.empty() ? nullptr : mask8.data, threshold, cap, 0);
+        const int rc = begin_frames(lane.ctxs[d], sources, first[d], count[d], mask8, masks8, threshold, cap);
         if (rc) {
             bad = rc;
             msg = std::string("sbm_match_batch_host_begin: ") + sbm_last_error();
@@ -895,7 +962,7 @@ std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& 
         Engine::Lane single;
         single.ctxs.assign(1, lane.ctxs[0]);
         for (size_t f : redo) {
-            const int64_t k = match_on_lane(single, sources[f], mask8, threshold);
+            const int64_t k = match_on_lane(single, sources[f], mask_of_frame(mask8, masks8, f), threshold);
             const std::vector<Match> all = to_matches(*flat, single.recs.data(), k);
             std::vector<Rect> boxes;
             std::vector<float> scores;
