@@ -279,21 +279,12 @@ protected:
 private:
     /* device side (facade/line2Dup_amd.cpp): a pool of LANES, each one engine context per device with the templates
      * uploaded and its own class selection.  A match() call takes a free lane for its duration -- creating one, up to
-     * setConcurrency(), when all are busy, else waiting -- so concurrent callers never share a context. */
+     * setConcurrency(), when all are busy, else waiting -- so concurrent callers never share a context.  The batch entry
+     * points share one begin / end path, a member of Engine (a nested class reads the detector's fields). */
     mutable Engine* eng_;
     int device_id_;
     std::vector<int> device_ids_;
     void dropContext();
-    /* the batch entry points under one shared mask (masks == NULL) or one mask per frame */
-    std::vector<std::vector<Match>> matchBatchImpl(const std::vector<cv::Mat>& sources, float threshold,
-                                                   const std::vector<std::string>& class_ids, const cv::Mat& mask,
-                                                   const std::vector<cv::Mat>* masks) const;
-    std::vector<std::vector<Match>> matchBatchNMSImpl(const std::vector<cv::Mat>& sources, float threshold,
-                                                      const std::vector<std::string>& class_ids, float score_threshold,
-                                                      float nms_threshold, float eta, int top_k, const cv::Mat& mask,
-                                                      const std::vector<cv::Mat>* masks) const;
-    void matchAsyncImpl(const std::vector<cv::Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
-                        const cv::Mat& mask, const std::vector<cv::Mat>* masks) const;
 };
 
 } // namespace line2Dup

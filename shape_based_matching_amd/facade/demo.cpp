@@ -44,6 +44,63 @@ static int usage()
     return 2;
 }
 
+// test.cpp:344-353: the image inside `pad` zero pixels on every side; empty (and reported) when it cannot be read
+static Mat read_padded(const std::string& path, int pad)
+{
+    Mat test_img = imread(path, IMREAD_UNCHANGED);
+    if (test_img.empty()) {
+        fprintf(stderr, "cannot read %s\n", path.c_str());
+        return Mat();
+    }
+    Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
+    test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
+    return padded;
+}
+
+// ... then cropped to multiples of 16 (less what the caller takes off)
+static Mat crop16(const Mat& m, int fewer_cols = 0, int fewer_rows = 0)
+{
+    const int stride = 16;
+    return m(Rect(0, 0, stride * (m.cols / stride) - fewer_cols, stride * (m.rows / stride) - fewer_rows)).clone();
+}
+
+// frame b = the image shifted 8 b columns to the right (wrapping)
+static std::vector<Mat> shifted_frames(const Mat& img, int nf)
+{
+    std::vector<Mat> frames;
+    const int esz = img.channels();
+    for (int b = 0; b < nf; ++b) {
+        Mat f(img.rows, img.cols, img.type());
+        const int sh = (8 * b) % img.cols;
+        for (int y = 0; y < img.rows; ++y) {
+            memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
+            memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
+        }
+        frames.push_back(f);
+    }
+    return frames;
+}
+
+static bool same(const std::vector<line2Dup::Match>& a, const std::vector<line2Dup::Match>& b)
+{
+    if (a.size() != b.size()) return false;
+    for (size_t i = 0; i < a.size(); ++i)
+        if (!(a[i] == b[i]) || a[i].template_id != b[i].template_id) return false;
+    return true;
+}
+
+// "0,0,0" -> {0, 0, 0}
+static std::vector<int> parse_devices(const char* p)
+{
+    std::vector<int> devices;
+    while (*p) {
+        devices.push_back(atoi(p));
+        while (*p && *p != ',') ++p;
+        if (*p == ',') ++p;
+    }
+    return devices;
+}
+
 int main(int argc, char** argv)
 {
     try {
@@ -58,14 +115,9 @@ int main(int argc, char** argv)
             line2Dup::Detector detector(num_features, {4, 8});
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            // test.cpp:344-353: pad, then crop to multiples of 16
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            Mat inner = padded(Rect(pad, pad, test_img.cols, test_img.rows));
-            test_img.copyTo(inner);
-            const int stride = 16;
-            Mat img = padded(Rect(0, 0, stride * (padded.cols / stride), stride * (padded.rows / stride))).clone();
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
+            Mat img = crop16(padded);
             std::vector<line2Dup::Match> matches = detector.match(img, threshold, ids);
             printf("matches %zu templates %d image %dx%dx%d\n", matches.size(), detector.numTemplates(), img.rows, img.cols, img.channels());
             for (const auto& m : matches) {
@@ -130,12 +182,9 @@ int main(int argc, char** argv)
             line2Dup::Detector detector(num_features, {4, 8});
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
-            const int stride = 16;
-            Mat img = padded(Rect(0, 0, stride * (padded.cols / stride), stride * (padded.rows / stride))).clone();
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
+            Mat img = crop16(padded);
             auto matches = detector.match(img, threshold, ids);
             std::vector<Rect> boxes;
             std::vector<float> scores;
@@ -176,20 +225,9 @@ int main(int argc, char** argv)
             const int top_k = atoi(argv[11]);
             line2Dup::Detector detector(num_features, {4, 8});
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat img = test_img(Rect(0, 0, 16 * (test_img.cols / 16), 16 * (test_img.rows / 16))).clone();
-            std::vector<Mat> frames;
-            const int esz = img.channels();
-            for (int b = 0; b < nf; ++b) {
-                Mat f(img.rows, img.cols, img.type());
-                const int sh = (8 * b) % img.cols;
-                for (int y = 0; y < img.rows; ++y) {
-                    memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
-                    memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
-                }
-                frames.push_back(f);
-            }
+            const Mat unpadded = read_padded(path, 0);
+            if (unpadded.empty()) return 1;
+            const std::vector<Mat> frames = shifted_frames(crop16(unpadded), nf);
             const auto kept = detector.matchBatchNMS(frames, threshold, ids, score_thr, nms_thr, eta, top_k);
             for (size_t f = 0; f < kept.size(); ++f) {
                 printf("frame %zu kept %zu\n", f, kept[f].size());
@@ -210,12 +248,9 @@ int main(int argc, char** argv)
             line2Dup::Detector detector(num_features, {4, 8});
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
-            const int stride = 16;
-            Mat img = padded(Rect(0, 0, stride * (padded.cols / stride), stride * (padded.rows / stride))).clone();
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
+            Mat img = crop16(padded);
             size_t n_matches = 0;
             for (int i = 0; i < 10; ++i) n_matches = detector.match(img, threshold, ids).size();
             const auto t0 = std::chrono::steady_clock::now();
@@ -261,38 +296,14 @@ int main(int argc, char** argv)
             const std::string fmt = argv[2], class_id = argv[3], path = argv[4];
             const float threshold = (float)atof(argv[5]);
             const int num_features = atoi(argv[6]), nf = atoi(argv[7]), pad = atoi(argv[8]);
-            std::vector<int> devices;
-            for (const char* p = argv[9]; *p;) {
-                devices.push_back(atoi(p));
-                while (*p && *p != ',') ++p;
-                if (*p == ',') ++p;
-            }
+            const std::vector<int> devices = parse_devices(argv[9]);
             line2Dup::Detector detector(num_features, {4, 8});
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
-            Mat img = padded(Rect(0, 0, 16 * (padded.cols / 16), 16 * (padded.rows / 16))).clone();
-            // frame b = the image shifted 8 b columns to the right (wrapping)
-            std::vector<Mat> frames;
-            const int esz = img.channels();
-            for (int b = 0; b < nf; ++b) {
-                Mat f(img.rows, img.cols, img.type());
-                const int sh = (8 * b) % img.cols;
-                for (int y = 0; y < img.rows; ++y) {
-                    memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
-                    memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
-                }
-                frames.push_back(f);
-            }
-            auto same = [](const std::vector<line2Dup::Match>& a, const std::vector<line2Dup::Match>& b) {
-                if (a.size() != b.size()) return false;
-                for (size_t i = 0; i < a.size(); ++i)
-                    if (!(a[i] == b[i]) || a[i].template_id != b[i].template_id) return false;
-                return true;
-            };
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
+            Mat img = crop16(padded);
+            const std::vector<Mat> frames = shifted_frames(img, nf);
             std::vector<std::vector<line2Dup::Match>> single;
             for (const Mat& f : frames) single.push_back(detector.match(f, threshold, ids));
             const auto batch = detector.matchBatch(frames, threshold, ids);
@@ -343,33 +354,18 @@ int main(int argc, char** argv)
             const std::string fmt = argv[2], class_id = argv[3], path = argv[4];
             const float threshold = (float)atof(argv[5]);
             const int num_features = atoi(argv[6]), nf = atoi(argv[7]), pad = atoi(argv[8]);
-            std::vector<int> devices;
-            for (const char* p = argv[9]; *p;) {
-                devices.push_back(atoi(p));
-                while (*p && *p != ',') ++p;
-                if (*p == ',') ++p;
-            }
+            const std::vector<int> devices = parse_devices(argv[9]);
             line2Dup::Detector detector(num_features, {4, 8});
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
-            Mat img = padded(Rect(0, 0, 16 * (padded.cols / 16), 16 * (padded.rows / 16))).clone();
-            // frame b = the image shifted 8 b columns to the right (wrapping), as in `batch`
-            std::vector<Mat> frames, masks;
-            const int esz = img.channels();
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
+            Mat img = crop16(padded);
+            const std::vector<Mat> frames = shifted_frames(img, nf); // as in `batch`
+            std::vector<Mat> masks;
             Mat wide(img.rows, img.cols + 24, CV_8UC1, Scalar::all(255)); // the parent of the non-continuous masks
             for (int y = img.rows / 2; y < img.rows; ++y) memset(wide.ptr(y), 0, (size_t)wide.cols);
             for (int b = 0; b < nf; ++b) {
-                Mat f(img.rows, img.cols, img.type());
-                const int sh = (8 * b) % img.cols;
-                for (int y = 0; y < img.rows; ++y) {
-                    memcpy(f.ptr(y) + (size_t)sh * esz, img.ptr(y), (size_t)(img.cols - sh) * esz);
-                    memcpy(f.ptr(y), img.ptr(y) + (size_t)(img.cols - sh) * esz, (size_t)sh * esz);
-                }
-                frames.push_back(f);
                 Mat m(img.rows, img.cols, CV_8UC1, Scalar::all(0));
                 if (b % 4 == 0) { // contains the object
                     for (int y = pad / 2; y < img.rows - pad / 2; ++y) memset(m.ptr(y), 255, (size_t)m.cols);
@@ -382,12 +378,6 @@ int main(int argc, char** argv)
                 }
                 masks.push_back(m);
             }
-            auto same = [](const std::vector<line2Dup::Match>& a, const std::vector<line2Dup::Match>& b) {
-                if (a.size() != b.size()) return false;
-                for (size_t i = 0; i < a.size(); ++i)
-                    if (!(a[i] == b[i]) || a[i].template_id != b[i].template_id) return false;
-                return true;
-            };
             std::vector<std::vector<line2Dup::Match>> single;
             for (size_t f = 0; f < frames.size(); ++f) single.push_back(detector.match(frames[f], threshold, ids, masks[f]));
             const auto batch = detector.matchBatch(frames, threshold, ids, masks);
@@ -431,20 +421,10 @@ int main(int argc, char** argv)
             if (argc > 10) detector.setConcurrency(atoi(argv[10]));
             std::vector<std::string> ids{class_id};
             detector.readClasses(ids, fmt);
-            Mat test_img = imread(path, IMREAD_UNCHANGED);
-            if (test_img.empty()) { fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-            Mat padded(test_img.rows + 2 * pad, test_img.cols + 2 * pad, test_img.type(), Scalar::all(0));
-            test_img.copyTo(padded(Rect(pad, pad, test_img.cols, test_img.rows)));
+            const Mat padded = read_padded(path, pad);
+            if (padded.empty()) return 1;
             // two geometries: the padded frame, and the same with 64 rows / 32 columns less
-            std::vector<Mat> frames;
-            frames.push_back(padded(Rect(0, 0, 16 * (padded.cols / 16), 16 * (padded.rows / 16))).clone());
-            frames.push_back(padded(Rect(0, 0, 16 * (padded.cols / 16) - 32, 16 * (padded.rows / 16) - 64)).clone());
-            auto same = [](const std::vector<line2Dup::Match>& a, const std::vector<line2Dup::Match>& b) {
-                if (a.size() != b.size()) return false;
-                for (size_t i = 0; i < a.size(); ++i)
-                    if (!(a[i] == b[i]) || a[i].template_id != b[i].template_id) return false;
-                return true;
-            };
+            const std::vector<Mat> frames{crop16(padded), crop16(padded, 32, 64)};
             std::vector<std::vector<line2Dup::Match>> alone;
             for (const Mat& f : frames) alone.push_back(detector.match(f, threshold, ids));
             std::vector<int> bad((size_t)n_threads, 0);

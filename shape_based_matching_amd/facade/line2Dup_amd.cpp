@@ -288,7 +288,8 @@ Detector* Detector::instance = nullptr;
 // Here a call needs an engine context (device buffers sized for the frame, uploaded templates, a stream), which is not
 // thread-safe.  So the Detector keeps a pool of LANES -- a lane = one context per device + what was uploaded / selected
 // on them -- and every call takes a free lane for its duration: concurrent callers never share a context, a single
-// caller only ever uses lane 0.
+// caller only ever uses lane 0.  The vector of lanes grows under `mu` while other callers run, so it is only ever touched
+// under `mu`; a caller works through the Lane* its lease took there (the lanes themselves never move).
 struct Detector::Engine {
     struct Flat { // the TemplatesMap flattened for sbm_upload_templates, rebuilt when class_templates changed
         std::vector<sbm_template_level> levels;
@@ -306,33 +307,47 @@ struct Detector::Engine {
         std::vector<unsigned char> recs; // match record scratch, kept between calls
         bool busy = false;
     };
+    // A batch of frames between begin() and end(): the one flow behind matchBatch, matchBatchNMS and matchAsync + wait.
+    struct Batch {
+        Lane* lane = nullptr;             // held by the caller's lease from before begin() until after end()
+        std::shared_ptr<const Flat> flat; // null: nothing selected, nothing began, every list is empty
+        // the frames (Mat headers: the pixels are the caller's and must stay unchanged until end()) and the mask(s) (a copy
+        // when not continuous): the uploads begin() enqueues read them until end(), and a frame matched again needs them
+        std::vector<Mat> sources;
+        Mat mask8;
+        std::vector<Mat> masks8; // one per frame (the overloads that take a vector of masks), else empty
+        float threshold = 0.f;
+        int64_t cap = 1024;            // records per frame; the NMS-kept list is a subsequence of the raw list, so it fits too
+        std::vector<int> first, count; // the frames of context d
+        int begun = 0;                 // contexts [0, begun) began (those with count > 0) and must end
+
+        void begin(const Detector& det, const std::vector<Mat>& frames, float thr, const std::vector<std::string>& class_ids, const Mat& mask,
+                   const std::vector<Mat>* masks);
+        std::vector<std::vector<Match>> end(const Detector& det, const sbm_nms_params* nms, int bad = 0, std::string msg = std::string());
+    };
     std::mutex mu;
     std::condition_variable cv;
     std::vector<std::unique_ptr<Lane>> lanes;
     int max_lanes = 4;
     std::shared_ptr<const Flat> flat; // null = class_templates changed since the last flattening
-    std::map<const void*, std::pair<int, sbm_ctx*>> pins; // pinBuffer: buffer -> (lane, context it is registered with)
-    struct Async { // batch in flight (matchAsync): its lane, frames per context, capacity, what a retry needs
+    std::map<const void*, std::pair<Lane*, sbm_ctx*>> pins; // pinBuffer: buffer -> (lane, context it is registered with)
+    struct Async { // matchAsync ... wait: the detector's one batch in flight; batch.lane is set once it holds its lane
         bool active = false;
-        int lane = -1;
-        std::vector<int> first, count;
-        int64_t cap = 0;
-        size_t n_frames = 0;
-        std::vector<Mat> sources;
-        Mat mask8;
-        std::vector<Mat> masks8; // one per frame (the overloads that take a vector of masks), else empty
-        float threshold = 0.f;
-        std::shared_ptr<const Flat> flat;
+        Batch batch;
     } async;
-};
 
-namespace {
-struct LaneLease { // releases the lane when the call ends, also by exception
-    line2Dup::Detector::Engine* e;
-    int idx;
-    ~LaneLease();
+    void templates_changed() // class_templates changed: the next call flattens and uploads again
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        flat.reset();
+    }
+    std::shared_ptr<const Flat> prepare(const Detector& det, Lane& lane, const std::vector<std::string>& class_ids, int rows, int cols, bool sharded);
+    std::vector<std::vector<Match>> run_batch(const Detector& det, const std::vector<Mat>& sources, float threshold,
+                                              const std::vector<std::string>& class_ids, const Mat& mask, const std::vector<Mat>* masks,
+                                              const sbm_nms_params* nms);
+    void start_async(const Detector& det, const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                     const Mat& mask, const std::vector<Mat>* masks);
 };
-} // namespace
 
 Detector::Detector() : modality(makePtr<ColorGradient>()), pyramid_levels(2), T_at_level({4, 8}), eng_(new Engine), device_id_(0) {}
 Detector::Detector(std::vector<int> T)
@@ -406,67 +421,69 @@ void Detector::setConcurrency(int n)
     eng_->max_lanes = n; // lanes beyond n that already exist stay (their memory is the price already paid); no new ones
 }
 
-LaneLease::~LaneLease()
-{
-    {
-        std::lock_guard<std::mutex> lock(e->mu);
-        e->lanes[(size_t)idx]->busy = false;
-    }
-    e->cv.notify_all();
-}
-
 namespace {
 
-// take a free lane (want < 0: any; else that one), creating an empty one while the pool may grow, else wait
-int acquire_lane(line2Dup::Detector::Engine& e, int want = -1)
+typedef line2Dup::Detector::Engine Engine;
+
+// take a free lane (want == null: any; else that one), creating an empty one while the pool may grow, else wait
+Engine::Lane* acquire_lane(Engine& e, Engine::Lane* want = nullptr)
 {
     std::unique_lock<std::mutex> lock(e.mu);
     for (;;) {
-        if (want >= 0) {
-            if ((size_t)want < e.lanes.size() && !e.lanes[(size_t)want]->busy) {
-                e.lanes[(size_t)want]->busy = true;
+        if (want) {
+            if (!want->busy) {
+                want->busy = true;
                 return want;
             }
         } else {
-            for (size_t i = 0; i < e.lanes.size(); ++i)
-                if (!e.lanes[i]->busy) {
-                    e.lanes[i]->busy = true;
-                    return (int)i;
+            for (auto& l : e.lanes)
+                if (!l->busy) {
+                    l->busy = true;
+                    return l.get();
                 }
             // a batch in flight (matchAsync ... wait) holds its lane between two calls of the SAME thread: it does not count
             // against the limit, or `matchAsync(); match(); wait();` with setConcurrency(1) would wait for itself
-            if ((int)e.lanes.size() < e.max_lanes + (e.async.active && e.async.lane >= 0 ? 1 : 0)) {
-                e.lanes.emplace_back(new line2Dup::Detector::Engine::Lane);
+            if ((int)e.lanes.size() < e.max_lanes + (e.async.active && e.async.batch.lane ? 1 : 0)) {
+                e.lanes.emplace_back(new Engine::Lane);
                 e.lanes.back()->busy = true;
-                return (int)e.lanes.size() - 1;
+                return e.lanes.back().get();
             }
         }
         e.cv.wait(lock);
     }
 }
 
+struct LaneLease { // a lane taken under the pool's lock; released when the call ends, also by exception
+    Engine* e;
+    Engine::Lane* lane;
+    ~LaneLease()
+    {
+        {
+            std::lock_guard<std::mutex> lock(e->mu);
+            lane->busy = false;
+        }
+        e->cv.notify_all();
+    }
+};
+
 } // namespace
 
-// Contexts, templates and class selection of lane `li` (held by the caller) for a call.  sharded: the selected templates
+// Contexts, templates and class selection of `lane` (held by the caller) for a call.  sharded: the selected templates
 // are divided over the lane's contexts (match() with several devices); else every context holds the whole selection (one
 // device, or matchBatch, which deals frames).  The engine's selection calls synchronise the device, so they are issued
 // only when something changed.  Returns the flattening the lane now holds, or null when the selection is empty.
-static std::shared_ptr<const Detector::Engine::Flat> prepare_lane(const Detector& det, Detector::Engine& e, int li, const std::vector<int>& devs,
-                                                                  const std::map<std::string, std::vector<std::vector<Template>>>& class_templates,
-                                                                  int pyramid_levels, const std::vector<int>& T_at_level, float weak_threshold,
-                                                                  const std::vector<std::string>& class_ids, int rows, int cols, bool sharded)
+std::shared_ptr<const Detector::Engine::Flat> Detector::Engine::prepare(const Detector& det, Lane& lane, const std::vector<std::string>& class_ids,
+                                                                        int rows, int cols, bool sharded)
 {
-    (void)det;
-    typedef Detector::Engine::Flat Flat;
-    Detector::Engine::Lane& lane = *e.lanes[(size_t)li];
+    const int pyramid_levels = det.pyramid_levels;
     if (lane.ctxs.empty()) {
-        CV_Assert(pyramid_levels >= 1 && pyramid_levels <= SBM_MAX_LEVELS && (int)T_at_level.size() >= pyramid_levels);
-        for (int d : devs) {
+        CV_Assert(pyramid_levels >= 1 && pyramid_levels <= SBM_MAX_LEVELS && (int)det.T_at_level.size() >= pyramid_levels);
+        for (int d : det.device_ids_.empty() ? std::vector<int>{det.device_id_} : det.device_ids_) {
             sbm_config cfg;
             memset(&cfg, 0, sizeof cfg);
             cfg.n_levels = pyramid_levels;
-            for (int l = 0; l < pyramid_levels; ++l) cfg.T[l] = T_at_level[l];
-            cfg.weak_threshold = weak_threshold;
+            for (int l = 0; l < pyramid_levels; ++l) cfg.T[l] = det.T_at_level[l];
+            cfg.weak_threshold = det.modality->weak_threshold;
             cfg.device_id = d;
             cfg.max_candidates = 0;
             sbm_ctx* c = nullptr;
@@ -478,10 +495,10 @@ static std::shared_ptr<const Detector::Engine::Flat> prepare_lane(const Detector
     // one flattening of the TemplatesMap per change, shared by the lanes
     std::shared_ptr<const Flat> flat;
     {
-        std::lock_guard<std::mutex> lock(e.mu);
-        if (!e.flat) {
+        std::lock_guard<std::mutex> lock(mu);
+        if (!this->flat) {
             std::shared_ptr<Flat> f(new Flat);
-            for (const auto& kv : class_templates) {
+            for (const auto& kv : det.class_templates) {
                 const int ci = (int)f->class_order.size();
                 f->class_order.push_back(kv.first);
                 for (size_t t = 0; t < kv.second.size(); ++t) {
@@ -504,9 +521,9 @@ static std::shared_ptr<const Detector::Engine::Flat> prepare_lane(const Detector
                     f->tid.push_back((int32_t)t);
                 }
             }
-            e.flat = f;
+            this->flat = f;
         }
-        flat = e.flat;
+        flat = this->flat;
     }
     if (lane.uploaded != flat) {
         for (sbm_ctx* c : lane.ctxs)
@@ -557,16 +574,23 @@ static std::shared_ptr<const Detector::Engine::Flat> prepare_lane(const Detector
     return flat;
 }
 
+// engine records as Matches, in the records' order
+static std::vector<Match> recs_to_matches(const Detector::Engine::Flat& flat, const sbm_match_rec* recs, int64_t n)
+{
+    std::vector<Match> matches;
+    matches.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        matches.push_back(Match(recs[i].x, recs[i].y, recs[i].similarity, flat.class_order[(size_t)recs[i].class_idx], recs[i].template_id));
+    return matches;
+}
+
 // epilogue (:1142-1145): canonical sort, exact-duplicate removal, then the reference's own adjacent std::unique (its
 // operator== ignores template_id)
 static std::vector<Match> to_matches(const Detector::Engine::Flat& flat, const void* recs_in, int64_t n)
 {
     std::vector<sbm_match_rec> recs((const sbm_match_rec*)recs_in, (const sbm_match_rec*)recs_in + n);
     n = sbm_canonicalize(recs.data(), n);
-    std::vector<Match> matches;
-    matches.reserve((size_t)n);
-    for (int64_t i = 0; i < n; ++i)
-        matches.push_back(Match(recs[i].x, recs[i].y, recs[i].similarity, flat.class_order[(size_t)recs[i].class_idx], recs[i].template_id));
+    std::vector<Match> matches = recs_to_matches(flat, recs.data(), n);
     matches.erase(std::unique(matches.begin(), matches.end()), matches.end());
     return matches;
 }
@@ -605,16 +629,25 @@ std::vector<Match> Detector::match(Mat source, float threshold, const std::vecto
     }
     Engine& e = *eng_;
     LaneLease lease{&e, acquire_lane(e)};
-    const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
-    const std::shared_ptr<const Engine::Flat> flat = prepare_lane(*this, e, lease.idx, devs, class_templates, pyramid_levels, T_at_level,
-                                                                  modality->weak_threshold, class_ids, source.rows, source.cols, true);
+    const std::shared_ptr<const Engine::Flat> flat = e.prepare(*this, *lease.lane, class_ids, source.rows, source.cols, true);
     if (!flat) return std::vector<Match>();
-    Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
-    const int64_t n = match_on_lane(lane, source, mask8, threshold);
-    return to_matches(*flat, lane.recs.data(), n);
+    const int64_t n = match_on_lane(*lease.lane, source, mask8, threshold);
+    return to_matches(*flat, lease.lane->recs.data(), n);
 }
 
 // ---- throughput path: batches of frames from host memory, uploads overlapped with the kernels ----------------------
+// what every batch entry point requires of its frames and of the one shared mask
+static void check_batch(const std::vector<Mat>& sources, const Mat& mask)
+{
+    CV_Assert(!sources.empty());
+    const Mat& s0 = sources[0];
+    for (const Mat& m : sources) {
+        CV_Assert(!m.empty() && m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3));
+        CV_Assert(m.rows == s0.rows && m.cols == s0.cols && m.channels() == s0.channels() && m.step == s0.step);
+    }
+    CV_Assert(mask.empty() || (mask.size() == s0.size() && mask.type() == CV_8UC1));
+}
+
 // One mask per frame (the overloads that take a vector of masks: the mask of Detector::match belongs to the call,
 // line2Dup.cpp:1078): empty, or one entry per frame; an entry is empty (no mask for that frame) or CV_8UC1 of the frames'
 // size, and is copied if it is not continuous.
@@ -629,9 +662,6 @@ static std::vector<Mat> frame_masks8(const std::vector<Mat>* masks, const Mat& s
     }
     return out;
 }
-
-// the mask frame f is matched under
-static const Mat& mask_of_frame(const Mat& mask8, const std::vector<Mat>& masks8, size_t f) { return masks8.empty() ? mask8 : masks8[f]; }
 
 // sbm_match_batch_host_begin for the frames [first, first + count) of a batch (one context's share): under the one shared
 // mask, or each frame under its own
@@ -649,80 +679,128 @@ static int begin_frames(sbm_ctx* ctx, const std::vector<Mat>& sources, int first
                                              threshold, cap, 0);
 }
 
-void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids, const Mat mask) const
+// Prepares the batch's lane (every context holds the whole selection), deals the frames over the contexts in contiguous
+// groups (frames are independent: Detector::match keeps no state) and enqueues each group's uploads and kernels.  A begin
+// that fails ends the contexts that began before it and is thrown.
+void Detector::Engine::Batch::begin(const Detector& det, const std::vector<Mat>& frames, float thr, const std::vector<std::string>& class_ids,
+                                    const Mat& mask, const std::vector<Mat>* masks)
 {
-    matchAsyncImpl(sources, threshold, class_ids, mask, nullptr);
-}
-
-void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
-                          const std::vector<Mat>& masks) const
-{
-    matchAsyncImpl(sources, threshold, class_ids, Mat(), &masks);
-}
-
-void Detector::matchAsyncImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids, const Mat& mask,
-                              const std::vector<Mat>* masks) const
-{
-    CV_Assert(!sources.empty());
-    const Mat& s0 = sources[0];
-    for (const Mat& m : sources) {
-        CV_Assert(!m.empty() && m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3));
-        CV_Assert(m.rows == s0.rows && m.cols == s0.cols && m.channels() == s0.channels() && m.step == s0.step);
+    const Mat& s0 = frames[0];
+    sources = frames;
+    threshold = thr;
+    flat = det.eng_->prepare(det, *lane, class_ids, s0.rows, s0.cols, false);
+    if (!flat) return;
+    if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
+    masks8 = frame_masks8(masks, s0, frames.size());
+    const int D = (int)lane->ctxs.size(), n = (int)frames.size();
+    for (int d = 0; d < D; ++d) {
+        first.push_back((int)((int64_t)n * d / D));
+        count.push_back((int)((int64_t)n * (d + 1) / D) - first.back());
     }
-    CV_Assert(mask.empty() || (mask.size() == s0.size() && mask.type() == CV_8UC1));
-    Engine& e = *eng_;
+    for (begun = 0; begun < D; ++begun) {
+        if (!count[begun]) continue;
+        const int rc = begin_frames(lane->ctxs[begun], sources, first[begun], count[begun], mask8, masks8, threshold, cap);
+        if (rc) end(det, nullptr, rc, std::string("sbm_match_batch_host_begin: ") + sbm_last_error()); // ends [0, begun), throws
+    }
+}
+
+// Ends every context that began, whatever happened since, and returns the frames' lists: the raw lists through the
+// epilogue, or (nms) the lists the device's epilogue + NMS kept.  bad / msg: a failure so far (a begin's); the first
+// failure is thrown once every context has ended, and from a failure on a context only ends (the plain call).
+// SBM_ERR_CAPACITY is no failure: some frame of that context produced more raw records than the per-frame capacity of the
+// batch (its count says how many, or its overflow flag is set).  The other frames' lists are complete: keep them, and run
+// the affected frames again one at a time, where match_on_lane grows its buffer -- the promise is
+// matchBatch(frames)[f] == match(frames[f]) whatever the lists' sizes.
+std::vector<std::vector<Match>> Detector::Engine::Batch::end(const Detector& det, const sbm_nms_params* nms, int bad, std::string msg)
+{
+    std::vector<std::vector<Match>> out(sources.size());
+    if (!flat) return out;
+    std::vector<size_t> redo;
+    for (int d = 0; d < begun; ++d) {
+        const int nf = count[d];
+        if (!nf) continue;
+        std::vector<sbm_match_rec> recs((size_t)nf * cap);
+        std::vector<int32_t> cnt((size_t)nf * 2);
+        const bool kept = nms && !bad; // what the context returns: the NMS-kept lists, else the raw ones
+        const int rc = kept ? sbm_match_batch_host_end_nms(lane->ctxs[d], nms, recs.data(), cap, cnt.data())
+                            : sbm_match_batch_host_end(lane->ctxs[d], recs.data(), cnt.data());
+        if (rc && rc != SBM_ERR_CAPACITY && !bad) {
+            bad = rc;
+            msg = std::string(kept ? "sbm_match_batch_host_end_nms: " : "sbm_match_batch_host_end: ") + sbm_last_error();
+        }
+        if (bad) continue;
+        for (int f = 0; f < nf; ++f) {
+            const size_t g = (size_t)(first[d] + f);
+            const sbm_match_rec* r = recs.data() + (size_t)f * cap;
+            // the raw list did not fit: NMS flags 1 | 2, else the count or the overflow word
+            if (kept ? (cnt[2 * f + 1] & 3) != 0 : (cnt[2 * f] < 0 || cnt[2 * f] > cap || cnt[2 * f + 1] != 0)) redo.push_back(g);
+            else out[g] = kept ? recs_to_matches(*flat, r, cnt[2 * f]) : to_matches(*flat, r, cnt[2 * f]);
+        }
+    }
+    if (bad) CV_Error(bad == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, msg);
+    if (redo.empty()) return out;
+    // the lane's selection is the batch's (whole selection on every context); one context is enough for a frame
+    Lane single;
+    single.ctxs.assign(1, lane->ctxs[0]);
+    for (size_t f : redo) {
+        const int64_t k = match_on_lane(single, sources[f], masks8.empty() ? mask8 : masks8[f], threshold);
+        const std::vector<Match> all = to_matches(*flat, single.recs.data(), k);
+        if (!nms) {
+            out[f] = all;
+            continue;
+        }
+        // the reference's own loop: boxes of the level-0 template sizes and NMSBoxes (nms.hpp)
+        std::vector<Rect> boxes;
+        std::vector<float> scores;
+        for (const Match& m : all) {
+            const std::vector<Template>& templ = det.class_templates.at(m.class_id)[(size_t)m.template_id];
+            boxes.push_back(Rect(m.x, m.y, templ[0].width, templ[0].height));
+            scores.push_back(m.similarity);
+        }
+        std::vector<int> idx;
+        cv_dnn::NMSBoxes(boxes, scores, nms->score_threshold, nms->nms_threshold, idx, nms->eta, nms->top_k);
+        for (int i : idx) out[f].push_back(all[(size_t)i]);
+    }
+    return out;
+}
+
+// matchBatch / matchBatchNMS: a lane for the call, begin, end.  Not matchAsync + wait: several threads may run batches on
+// one detector at once, each on a lane of its own, while matchAsync / wait is the detector's ONE batch in flight.
+std::vector<std::vector<Match>> Detector::Engine::run_batch(const Detector& det, const std::vector<Mat>& sources, float threshold,
+                                                            const std::vector<std::string>& class_ids, const Mat& mask,
+                                                            const std::vector<Mat>* masks, const sbm_nms_params* nms)
+{
+    if (sources.empty()) return std::vector<std::vector<Match>>();
+    check_batch(sources, mask);
+    LaneLease lease{this, acquire_lane(*this)};
+    Batch b;
+    b.lane = lease.lane;
+    b.begin(det, sources, threshold, class_ids, mask, masks);
+    return b.end(det, nms);
+}
+
+// matchAsync: claim the detector's one batch in flight, take a lane for it and begin; wait() ends it and frees both
+void Detector::Engine::start_async(const Detector& det, const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                                   const Mat& mask, const std::vector<Mat>* masks)
+{
+    check_batch(sources, mask);
     {
-        std::lock_guard<std::mutex> lock(e.mu);
-        CV_Assert(!e.async.active); // one batch in flight per detector
-        e.async = Engine::Async();
-        e.async.active = true; // claimed; filled in below by this thread only
+        std::lock_guard<std::mutex> lock(mu);
+        CV_Assert(!async.active); // one batch in flight per detector
+        async = Async();
+        async.active = true; // claimed; filled in below by this thread only
     }
-    Engine::Async& as = e.async;
-    const int li = acquire_lane(e);
-    as.lane = li;
-    auto give_up = [&]() { // nothing in flight after all: free the lane and the claim
-        LaneLease drop{&e, li};
-        std::lock_guard<std::mutex> lock(e.mu);
-        as.active = false;
-    };
+    Lane* lane = acquire_lane(*this);
     try {
-        as.n_frames = sources.size();
-        as.threshold = threshold;
-        const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
-        as.flat = prepare_lane(*this, e, li, devs, class_templates, pyramid_levels, T_at_level, modality->weak_threshold, class_ids, s0.rows,
-                               s0.cols, false);
-        if (!as.flat) { // nothing selected: wait() returns empty lists
-            as.cap = 0;
-            return;
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            async.batch.lane = lane;
         }
-        Engine::Lane& lane = *e.lanes[(size_t)li];
-        // the frames (Mat headers: the pixels are the caller's and must stay unchanged until wait()) and the mask (a copy
-        // when it is not continuous) are kept until wait(): the uploads enqueued below read them after this call returns
-        as.sources = sources;
-        if (!mask.empty()) as.mask8 = mask.isContinuous() ? mask : mask.clone();
-        as.masks8 = frame_masks8(masks, s0, sources.size());
-        // frames dealt over the devices in contiguous groups (frames are independent: Detector::match keeps no state)
-        const int D = (int)lane.ctxs.size(), n = (int)sources.size();
-        as.cap = 1024;
-        for (int d = 0; d < D; ++d) {
-            as.first.push_back((int)((int64_t)n * d / D));
-            as.count.push_back((int)((int64_t)n * (d + 1) / D) - as.first.back());
-        }
-        for (int d = 0; d < D; ++d) {
-            if (!as.count[d]) continue;
-            const int rc = begin_frames(lane.ctxs[d], sources, as.first[d], as.count[d], as.mask8, as.masks8, threshold, as.cap);
-            if (rc) {
-                const std::string msg = sbm_last_error();
-                for (int k = 0; k < d; ++k) { // drain what was started
-                    std::vector<sbm_match_rec> tmp((size_t)as.count[k] * as.cap);
-                    std::vector<int32_t> cnt((size_t)as.count[k] * 2);
-                    if (as.count[k]) (void)sbm_match_batch_host_end(lane.ctxs[k], tmp.data(), cnt.data());
-                }
-                CV_Error(rc == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, "sbm_match_batch_host_begin: " + msg);
-            }
-        }
-    } catch (...) {
-        give_up();
+        async.batch.begin(det, sources, threshold, class_ids, mask, masks);
+    } catch (...) { // nothing in flight after all: free the lane and the claim
+        LaneLease drop{this, lane};
+        std::lock_guard<std::mutex> lock(mu);
+        async = Async();
         throw;
     }
 }
@@ -730,12 +808,11 @@ void Detector::matchAsyncImpl(const std::vector<Mat>& sources, float threshold, 
 std::vector<std::vector<Match>> Detector::wait() const
 {
     Engine& e = *eng_;
-    Engine::Async& as = e.async;
     {
         std::lock_guard<std::mutex> lock(e.mu);
-        CV_Assert(as.active && as.lane >= 0);
+        CV_Assert(e.async.active && e.async.batch.lane);
     }
-    LaneLease lease{&e, as.lane}; // the lane matchAsync took is released when this call ends
+    LaneLease lease{&e, e.async.batch.lane}; // the lane matchAsync took is released when this call ends
     struct Done {
         Detector::Engine& e;
         ~Done()
@@ -744,239 +821,45 @@ std::vector<std::vector<Match>> Detector::wait() const
             e.async = Detector::Engine::Async();
         }
     } done{e};
-    std::vector<std::vector<Match>> out(as.n_frames);
-    if (as.cap == 0) return out;
-    Engine::Lane& lane = *e.lanes[(size_t)as.lane];
-    int bad = 0;
-    std::string msg;
-    std::vector<size_t> redo; // frames whose list did not fit the batch's per-frame capacity
-    for (size_t d = 0; d < lane.ctxs.size(); ++d) {
-        const int nf = as.count[d];
-        if (!nf) continue;
-        std::vector<sbm_match_rec> recs((size_t)nf * as.cap);
-        std::vector<int32_t> cnt((size_t)nf * 2);
-        const int rc = sbm_match_batch_host_end(lane.ctxs[d], recs.data(), cnt.data());
-        if (rc && rc != SBM_ERR_CAPACITY && !bad) {
-            bad = rc;
-            msg = sbm_last_error();
-        }
-        if (rc && rc != SBM_ERR_CAPACITY) continue;
-        // SBM_ERR_CAPACITY: some frame of this context produced more raw records than the per-frame capacity of the batch
-        // (its count says how many, or its overflow flag is set).  The other frames' lists are complete: keep them, and
-        // run the affected frames again one at a time, where match() grows its buffer -- the promise is
-        // matchBatch(frames)[f] == match(frames[f]) whatever the lists' sizes.
-        for (int f = 0; f < nf; ++f) {
-            if (cnt[2 * f] < 0 || cnt[2 * f] > as.cap || cnt[2 * f + 1] != 0) redo.push_back((size_t)(as.first[d] + f));
-            else out[(size_t)(as.first[d] + f)] = to_matches(*as.flat, recs.data() + (size_t)f * as.cap, cnt[2 * f]);
-        }
-    }
-    if (bad) CV_Error(bad == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, "sbm_match_batch_host_end: " + msg);
-    if (!redo.empty()) {
-        // the lane's selection is the batch's (whole selection on every context); one context is enough for a frame
-        Engine::Lane single;
-        single.ctxs.assign(1, lane.ctxs[0]);
-        for (size_t f : redo) {
-            const int64_t n = match_on_lane(single, as.sources[f], mask_of_frame(as.mask8, as.masks8, f), as.threshold);
-            out[f] = to_matches(*as.flat, single.recs.data(), n);
-        }
-    }
-    return out;
+    return e.async.batch.end(*this, nullptr);
+}
+
+void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids, const Mat mask) const
+{
+    eng_->start_async(*this, sources, threshold, class_ids, mask, nullptr);
+}
+
+void Detector::matchAsync(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
+                          const std::vector<Mat>& masks) const
+{
+    eng_->start_async(*this, sources, threshold, class_ids, Mat(), &masks);
 }
 
 std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                      const Mat mask) const
 {
-    return matchBatchImpl(sources, threshold, class_ids, mask, nullptr);
+    return eng_->run_batch(*this, sources, threshold, class_ids, mask, nullptr, nullptr);
 }
 
 std::vector<std::vector<Match>> Detector::matchBatch(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                      const std::vector<Mat>& masks) const
 {
-    return matchBatchImpl(sources, threshold, class_ids, Mat(), &masks);
-}
-
-std::vector<std::vector<Match>> Detector::matchBatchImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
-                                                         const Mat& mask, const std::vector<Mat>* masks) const
-{
-    if (sources.empty()) return std::vector<std::vector<Match>>();
-    // not matchAsync + wait: several threads may run batches on one detector at once, each on a lane of its own, while
-    // matchAsync / wait is the detector's ONE batch in flight
-    const Mat& s0 = sources[0];
-    for (const Mat& m : sources) {
-        CV_Assert(!m.empty() && m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3));
-        CV_Assert(m.rows == s0.rows && m.cols == s0.cols && m.channels() == s0.channels() && m.step == s0.step);
-    }
-    CV_Assert(mask.empty() || (mask.size() == s0.size() && mask.type() == CV_8UC1));
-    Engine& e = *eng_;
-    LaneLease lease{&e, acquire_lane(e)};
-    const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
-    const std::shared_ptr<const Engine::Flat> flat = prepare_lane(*this, e, lease.idx, devs, class_templates, pyramid_levels, T_at_level,
-                                                                  modality->weak_threshold, class_ids, s0.rows, s0.cols, false);
-    std::vector<std::vector<Match>> out(sources.size());
-    if (!flat) return out;
-    Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
-    Mat mask8;
-    if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
-    const std::vector<Mat> masks8 = frame_masks8(masks, s0, sources.size());
-    const int D = (int)lane.ctxs.size(), n = (int)sources.size();
-    const int64_t cap = 1024;
-    std::vector<int> first, count;
-    for (int d = 0; d < D; ++d) {
-        first.push_back((int)((int64_t)n * d / D));
-        count.push_back((int)((int64_t)n * (d + 1) / D) - first.back());
-    }
-    int begun = 0, bad = 0;
-    std::string msg;
-    for (int d = 0; d < D && !bad; ++d, ++begun) {
-        if (!count[d]) continue;
-        const int rc = begin_frames(lane.ctxs[d], sources, first[d], count[d], mask8, masks8, threshold, cap);
-        if (rc) {
-            bad = rc;
-            msg = std::string("sbm_match_batch_host_begin: ") + sbm_last_error();
-            break;
-        }
-    }
-    std::vector<size_t> redo;
-    for (int d = 0; d < begun; ++d) { // every context that began must end, whatever happened since
-        if (!count[d]) continue;
-        std::vector<sbm_match_rec> recs((size_t)count[d] * cap);
-        std::vector<int32_t> cnt((size_t)count[d] * 2);
-        const int rc = sbm_match_batch_host_end(lane.ctxs[d], recs.data(), cnt.data());
-        if (rc && rc != SBM_ERR_CAPACITY) {
-            if (!bad) {
-                bad = rc;
-                msg = std::string("sbm_match_batch_host_end: ") + sbm_last_error();
-            }
-            continue;
-        }
-        if (bad) continue;
-        for (int f = 0; f < count[d]; ++f) { // see wait(): frames whose list did not fit are matched again one at a time
-            if (cnt[2 * f] < 0 || cnt[2 * f] > cap || cnt[2 * f + 1] != 0) redo.push_back((size_t)(first[d] + f));
-            else out[(size_t)(first[d] + f)] = to_matches(*flat, recs.data() + (size_t)f * cap, cnt[2 * f]);
-        }
-    }
-    if (bad) CV_Error(bad == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, msg);
-    if (!redo.empty()) {
-        Engine::Lane single;
-        single.ctxs.assign(1, lane.ctxs[0]);
-        for (size_t f : redo) {
-            const int64_t k = match_on_lane(single, sources[f], mask_of_frame(mask8, masks8, f), threshold);
-            out[f] = to_matches(*flat, single.recs.data(), k);
-        }
-    }
-    return out;
-}
-
-// the NMS-kept records of one frame (already in epilogue order, walk order kept) as Matches
-static std::vector<Match> kept_to_matches(const Detector::Engine::Flat& flat, const sbm_match_rec* recs, int64_t n)
-{
-    std::vector<Match> matches;
-    matches.reserve((size_t)n);
-    for (int64_t i = 0; i < n; ++i)
-        matches.push_back(Match(recs[i].x, recs[i].y, recs[i].similarity, flat.class_order[(size_t)recs[i].class_idx], recs[i].template_id));
-    return matches;
+    return eng_->run_batch(*this, sources, threshold, class_ids, Mat(), &masks, nullptr);
 }
 
 std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                         float score_threshold, float nms_threshold, float eta, int top_k, const Mat mask) const
 {
-    return matchBatchNMSImpl(sources, threshold, class_ids, score_threshold, nms_threshold, eta, top_k, mask, nullptr);
+    const sbm_nms_params prm{score_threshold, nms_threshold, eta, top_k};
+    return eng_->run_batch(*this, sources, threshold, class_ids, mask, nullptr, &prm);
 }
 
 std::vector<std::vector<Match>> Detector::matchBatchNMS(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
                                                         float score_threshold, float nms_threshold, float eta, int top_k,
                                                         const std::vector<Mat>& masks) const
 {
-    return matchBatchNMSImpl(sources, threshold, class_ids, score_threshold, nms_threshold, eta, top_k, Mat(), &masks);
-}
-
-std::vector<std::vector<Match>> Detector::matchBatchNMSImpl(const std::vector<Mat>& sources, float threshold, const std::vector<std::string>& class_ids,
-                                                            float score_threshold, float nms_threshold, float eta, int top_k, const Mat& mask,
-                                                            const std::vector<Mat>* masks) const
-{
-    if (sources.empty()) return std::vector<std::vector<Match>>();
-    const Mat& s0 = sources[0];
-    for (const Mat& m : sources) {
-        CV_Assert(!m.empty() && m.depth() == CV_8U && (m.channels() == 1 || m.channels() == 3));
-        CV_Assert(m.rows == s0.rows && m.cols == s0.cols && m.channels() == s0.channels() && m.step == s0.step);
-    }
-    CV_Assert(mask.empty() || (mask.size() == s0.size() && mask.type() == CV_8UC1));
-    Engine& e = *eng_;
-    LaneLease lease{&e, acquire_lane(e)};
-    const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
-    const std::shared_ptr<const Engine::Flat> flat = prepare_lane(*this, e, lease.idx, devs, class_templates, pyramid_levels, T_at_level,
-                                                                  modality->weak_threshold, class_ids, s0.rows, s0.cols, false);
-    std::vector<std::vector<Match>> out(sources.size());
-    if (!flat) return out;
-    Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
-    Mat mask8;
-    if (!mask.empty()) mask8 = mask.isContinuous() ? mask : mask.clone();
-    const std::vector<Mat> masks8 = frame_masks8(masks, s0, sources.size());
-    const int D = (int)lane.ctxs.size(), n = (int)sources.size();
-    const int64_t cap = 1024, out_cap = cap; // the kept list is a subsequence of the raw list: out_cap = cap always fits
-    sbm_nms_params prm;
-    prm.score_threshold = score_threshold;
-    prm.nms_threshold = nms_threshold;
-    prm.eta = eta;
-    prm.top_k = top_k;
-    std::vector<int> first, count;
-    for (int d = 0; d < D; ++d) {
-        first.push_back((int)((int64_t)n * d / D));
-        count.push_back((int)((int64_t)n * (d + 1) / D) - first.back());
-    }
-    int begun = 0, bad = 0;
-    std::string msg;
-    for (int d = 0; d < D && !bad; ++d, ++begun) {
-        if (!count[d]) continue;
-        const int rc = begin_frames(lane.ctxs[d], sources, first[d], count[d], mask8, masks8, threshold, cap);
-        if (rc) {
-            bad = rc;
-            msg = std::string("sbm_match_batch_host_begin: ") + sbm_last_error();
-            break;
-        }
-    }
-    std::vector<size_t> redo;
-    for (int d = 0; d < begun; ++d) { // every context that began must end, whatever happened since
-        if (!count[d]) continue;
-        std::vector<sbm_match_rec> recs((size_t)count[d] * out_cap);
-        std::vector<int32_t> cnt((size_t)count[d] * 2);
-        const int rc = bad ? sbm_match_batch_host_end(lane.ctxs[d], recs.data(), cnt.data())
-                           : sbm_match_batch_host_end_nms(lane.ctxs[d], &prm, recs.data(), out_cap, cnt.data());
-        if (rc && rc != SBM_ERR_CAPACITY) {
-            if (!bad) {
-                bad = rc;
-                msg = std::string("sbm_match_batch_host_end_nms: ") + sbm_last_error();
-            }
-            continue;
-        }
-        if (bad) continue;
-        for (int f = 0; f < count[d]; ++f) { // flags 1 | 2: the raw list did not fit the batch's capacity
-            if (cnt[2 * f + 1] & 3) redo.push_back((size_t)(first[d] + f));
-            else out[(size_t)(first[d] + f)] = kept_to_matches(*flat, recs.data() + (size_t)f * out_cap, cnt[2 * f]);
-        }
-    }
-    if (bad) CV_Error(bad == SBM_ERR_INVALID ? Error::StsBadArg : Error::StsError, msg);
-    if (!redo.empty()) {
-        // such frames are matched again one at a time (match() grows its buffer), then the reference's own loop: boxes of
-        // the level-0 template sizes and NMSBoxes (nms.hpp)
-        Engine::Lane single;
-        single.ctxs.assign(1, lane.ctxs[0]);
-        for (size_t f : redo) {
-            const int64_t k = match_on_lane(single, sources[f], mask_of_frame(mask8, masks8, f), threshold);
-            const std::vector<Match> all = to_matches(*flat, single.recs.data(), k);
-            std::vector<Rect> boxes;
-            std::vector<float> scores;
-            for (const Match& m : all) {
-                const std::vector<Template>& templ = class_templates.at(m.class_id)[(size_t)m.template_id];
-                boxes.push_back(Rect(m.x, m.y, templ[0].width, templ[0].height));
-                scores.push_back(m.similarity);
-            }
-            std::vector<int> idx;
-            cv_dnn::NMSBoxes(boxes, scores, score_threshold, nms_threshold, idx, eta, top_k);
-            for (int i : idx) out[f].push_back(all[(size_t)i]);
-        }
-    }
-    return out;
+    const sbm_nms_params prm{score_threshold, nms_threshold, eta, top_k};
+    return eng_->run_batch(*this, sources, threshold, class_ids, Mat(), &masks, &prm);
 }
 
 void Detector::pinBuffer(const Mat& frame) const
@@ -984,32 +867,29 @@ void Detector::pinBuffer(const Mat& frame) const
     CV_Assert(!frame.empty());
     Engine& e = *eng_;
     LaneLease lease{&e, acquire_lane(e)};
-    Engine::Lane& lane = *e.lanes[(size_t)lease.idx];
-    if (lane.ctxs.empty()) { // a lane nobody matched on yet: give it its contexts (templates follow with the first call)
-        const std::vector<int> devs = device_ids_.empty() ? std::vector<int>{device_id_} : device_ids_;
-        prepare_lane(*this, e, lease.idx, devs, class_templates, pyramid_levels, T_at_level, modality->weak_threshold, std::vector<std::string>(), 0,
-                     0, false);
-    }
+    Engine::Lane& lane = *lease.lane;
+    // a lane nobody matched on yet: give it its contexts (templates follow with the first call)
+    if (lane.ctxs.empty()) e.prepare(*this, lane, std::vector<std::string>(), 0, 0, false);
     // page-locking is process-wide (hipHostRegister): every lane's uploads from the buffer are direct DMAs; the context
     // only keeps the registration so that unpinBuffer can drop it
     check(sbm_pin_host_buffer(lane.ctxs[0], frame.data, (int64_t)frame.step * frame.rows), "sbm_pin_host_buffer");
     std::lock_guard<std::mutex> lock(e.mu);
-    e.pins[frame.data] = std::make_pair(lease.idx, lane.ctxs[0]);
+    e.pins[frame.data] = std::make_pair(&lane, lane.ctxs[0]);
 }
 
 void Detector::unpinBuffer(const Mat& frame) const
 {
     CV_Assert(!frame.empty());
     Engine& e = *eng_;
-    int li = -1;
+    Engine::Lane* lane = nullptr;
     {
         std::lock_guard<std::mutex> lock(e.mu);
         auto it = e.pins.find(frame.data);
         CV_Assert(it != e.pins.end());
-        li = it->second.first;
+        lane = it->second.first;
     }
-    LaneLease lease{&e, acquire_lane(e, li)}; // the lane whose context holds the registration, once it is free
-    check(sbm_unpin_host_buffer(e.lanes[(size_t)li]->ctxs[0], frame.data), "sbm_unpin_host_buffer");
+    LaneLease lease{&e, acquire_lane(e, lane)}; // the lane whose context holds the registration, once it is free
+    check(sbm_unpin_host_buffer(lane->ctxs[0], frame.data), "sbm_unpin_host_buffer");
     std::lock_guard<std::mutex> lock(e.mu);
     e.pins.erase(frame.data);
 }
@@ -1035,10 +915,7 @@ int Detector::addTemplate(const Mat source, const std::string& class_id, const M
     }
     crop_templates(tp);
     template_pyramids.push_back(tp);
-    {
-        std::lock_guard<std::mutex> lock(eng_->mu);
-        eng_->flat.reset(); // class_templates changed: the next call flattens and uploads again
-    }
+    eng_->templates_changed();
     return template_id;
 }
 
@@ -1074,10 +951,7 @@ int Detector::addTemplate_rotate(const std::string& class_id, int zero_id, float
     }
     crop_templates(tp);
     template_pyramids.push_back(tp);
-    {
-        std::lock_guard<std::mutex> lock(eng_->mu);
-        eng_->flat.reset(); // class_templates changed: the next call flattens and uploads again
-    }
+    eng_->templates_changed();
     return template_id;
 }
 
@@ -1146,10 +1020,7 @@ std::string Detector::readClass(const FileNode& fn, const std::string& class_id_
         for (FileNodeIterator jt = templates_fn.begin(); jt != templates_fn.end(); ++jt) tps[template_id][idx++].read(*jt);
     }
     class_templates[class_id] = tps;
-    {
-        std::lock_guard<std::mutex> lock(eng_->mu);
-        eng_->flat.reset(); // class_templates changed: the next call flattens and uploads again
-    }
+    eng_->templates_changed();
     return class_id;
 }
 
