@@ -191,6 +191,16 @@ public:
     int addTemplate(const cv::Mat sources, const std::string& class_id, const cv::Mat& object_mask, float sscale = -1.0,
                     float orientation = -1.0, int tagFieldID = 0, std::string fiducial_src = "none", int num_features = 0);
 
+    /* MI355X extension: addTemplate for a list of sources in one call.  Element k of the result is exactly what the k-th
+     * call of a loop of addTemplate(sources[k], class_id, object_masks[k], sscales[k], orientations[k], ...) returns (a
+     * failed template returns -1 and takes no id) and the detector afterwards is identical to the loop's.  object_masks:
+     * empty, or one per source (an empty Mat = no mask); sscales / orientations: empty (addTemplate's defaults) or one per
+     * source.  Sources of one size and type are trained together on the device (sbm_train_batch). */
+    std::vector<int> addTemplates(const std::vector<cv::Mat>& sources, const std::string& class_id,
+                                  const std::vector<cv::Mat>& object_masks, const std::vector<float>& sscales = {},
+                                  const std::vector<float>& orientations = {}, int tagFieldID = 0,
+                                  std::string fiducial_src = "none", int num_features = 0);
+
     int addTemplate_rotate(const std::string& class_id, int zero_id, float theta, cv::Point2f center);
 
     const cv::Ptr<ColorGradient>& getModalities() const { return modality; }
@@ -285,6 +295,7 @@ private:
     int device_id_;
     std::vector<int> device_ids_;
     void dropContext();
+    void templatesChanged(); /* class_templates changed: the next match flattens and uploads again */
 };
 
 } // namespace line2Dup

@@ -446,6 +446,44 @@ int sbm_similarity(sbm_ctx* ctx, int32_t template_index, uint16_t* dst_host);
 int sbm_similarity_local(sbm_ctx* ctx, int32_t level, int32_t template_index, int32_t cx,
                          int32_t cy, uint16_t* dst_host);
 
+/* ---- batched template training ---------------------------------------------
+ * Detector::addTemplate (line2Dup.cpp:1299-1353) for n_images images of one geometry, on the device from the gradient
+ * stage to cropTemplates: per pyramid level (n_levels and weak_threshold are the context's) quantised orientations,
+ * pyrDown and the nearest-neighbour mask of the next level, then the 5x5 local maxima above strong_threshold under the
+ * 3x3-eroded mask, their ties resolved in row-major order as extractTemplate's scan does (:452-539), the candidates in
+ * std::stable_sort's order, selectScatteredFeatures (:163-212; num_features halves per level, :427) and cropTemplates
+ * (:115-161) -- every kernel after the gradients launched once for the batch.  Image i is exactly what addTemplate
+ * makes of it alone:
+ *   levels[i * n_levels + l]   the template of level l; feature_offset counts from the image's feature block, level l's
+ *                              features directly behind level l-1's
+ *   feats[i * feat_cap ...]    the image's features (theta = Feature::theta, the unquantised angle)
+ *   status[2 * i]              0 ok | 1 too few candidates at some level (where addTemplate returns -1) | 2 feat_cap too
+ *                              small; nothing else of an image that is not ok is valid
+ *   status[2 * i + 1]          the image's number of features (status 0 and 2), the failing level (status 1)
+ * One image's failure does not touch another image's output.  rows, cols <= 32767. */
+typedef struct sbm_train_feature {
+    int32_t x, y, label;
+    float theta;
+} sbm_train_feature;
+
+/* Device form: image i at d_imgs + i * img_stride bytes (rows of `stride` bytes).  d_masks: NULL = no mask;
+ * mask_stride == 0 = one mask for all images; any other stride must be >= rows * cols (SBM_ERR_INVALID otherwise).
+ * d_levels: n_images * n_levels sbm_template_level; d_feats: n_images * feat_cap sbm_train_feature; d_status:
+ * n_images * 2 int32.  Stream-ordered on `stream` (NULL: the context's); the scratch grows on a first call of a larger
+ * batch or geometry (which waits for the device, as sbm_match_batch_device does); steady-state calls do not synchronise.
+ * A context has ONE training scratch: calls on one context must be ordered by the caller (the same stream, or events
+ * between streams) -- two calls in flight on different streams would share it.  Use a context per stream to overlap. */
+int sbm_train_batch_device(sbm_ctx* ctx, const void* d_imgs, int64_t img_stride, int32_t n_images, int32_t rows,
+                           int32_t cols, int32_t stride, int32_t channels, const void* d_masks, int64_t mask_stride,
+                           float strong_threshold, int32_t num_features, void* d_levels, void* d_feats,
+                           int64_t feat_cap, void* d_status, void* stream);
+/* Host form: imgs[i] (rows of `stride` bytes); masks may be NULL, and so may any masks[i] (no mask for that image).
+ * Uploads, runs the device form on the context's stream, downloads and synchronises. */
+int sbm_train_batch(sbm_ctx* ctx, const uint8_t* const* imgs, int32_t n_images, int32_t rows, int32_t cols,
+                    int32_t stride, int32_t channels, const uint8_t* const* masks, float strong_threshold,
+                    int32_t num_features, sbm_template_level* levels, sbm_train_feature* feats, int64_t feat_cap,
+                    int32_t* status);
+
 /* ---- measurement ---------------------------------------------------------
  * Per-kernel HIP-event timings of the last sbm_match/sbm_build_pyramid/
  * sbm_match_templates call when profiling was enabled (adds synchronisation;

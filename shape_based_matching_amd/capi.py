@@ -14,6 +14,8 @@ import numpy as np
 
 from .templates import FEATURE_DTYPE, LEVEL_DTYPE, MATCH_DTYPE, TemplateSet
 
+TRAIN_FEATURE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("label", "<i4"), ("theta", "<f4")])  # sbm_train_feature
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsbm_hip.so")
 SBM_MAX_LEVELS = 8
@@ -32,6 +34,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_device_banded", "sbm_pin_host_buffer", "sbm_unpin_host_buffer",
     "sbm_select_templates", "sbm_partition_templates", "sbm_match_sharded",
     "sbm_match_batch_host", "sbm_match_batch_host_begin", "sbm_match_batch_host_end", "sbm_extract_local_maxima",
+    "sbm_train_batch", "sbm_train_batch_device",
     "sbm_set_pipeline_depth", "sbm_set_coarse_mode", "sbm_set_refine_order", "sbm_set_refine_bits", "sbm_get_coarse_bitplanes",
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
@@ -206,6 +209,8 @@ def lib() -> C.CDLL:
     L.sbm_match_device_sharded.argtypes = [vp, vp, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp, vp]
     L.sbm_match_batch_device_sharded.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp, vp]
     L.sbm_extract_local_maxima.argtypes = [vp, vp, vp, i32, i32, f32, vp, i64, C.POINTER(i64)]
+    L.sbm_train_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, f32, i32, vp, vp, i64, vp, vp]
+    L.sbm_train_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, i32, vp, vp, i64, vp]
     L.sbm_set_pipeline_depth.argtypes = [vp, i32]
     L.sbm_set_coarse_mode.argtypes = [vp, i32]
     L.sbm_set_refine_order.argtypes = [vp, i32]
@@ -433,6 +438,55 @@ class Context:
                                               C.byref(n)))
         xy = xy[: n.value]
         return np.stack([xy & 0xFFFF, xy >> 16], axis=1)
+
+    def train_batch_device(self, d_imgs: int, img_stride: int, n_images: int, rows: int, cols: int, stride: int, channels: int,
+                           strong_threshold: float, num_features: int, d_levels: int, d_feats: int, feat_cap: int, d_status: int,
+                           stream: int = 0, d_masks: int = 0, mask_stride: int = 0):
+        """Detector::addTemplate for n_images images of one geometry, on the device (sbm_train_batch_device): image i at
+        d_imgs + i*img_stride; its n_levels level records at d_levels, its features at d_feats + i*feat_cap records, its
+        {status, count} at d_status + 2*i int32.  d_masks 0: no mask; mask_stride 0: one mask for all images."""
+        _check(lib().sbm_train_batch_device(self._h, C.c_void_p(d_imgs), img_stride, n_images, rows, cols, stride, channels,
+                                            C.c_void_p(d_masks) if d_masks else None, mask_stride, C.c_float(strong_threshold),
+                                            num_features, C.c_void_p(d_levels), C.c_void_p(d_feats) if d_feats else None, feat_cap,
+                                            C.c_void_p(d_status), C.c_void_p(stream) if stream else None))
+
+    def train_batch_raw(self, imgs: Sequence[np.ndarray], masks: Optional[Sequence[Optional[np.ndarray]]], strong_threshold: float,
+                        num_features: int, feat_cap: int):
+        """sbm_train_batch as it is: (levels[n, n_levels], feats[n, feat_cap], status[n, 2])"""
+        arrs = [_img(im) for im in imgs]
+        if not arrs:
+            raise ValueError("no images")
+        _, r, c, ch = arrs[0]
+        if any(a[1:] != (r, c, ch) for a in arrs):
+            raise ValueError("the images of a batch share one geometry")
+        n = len(arrs)
+        ms = [None] * n if masks is None else [None if m is None else np.ascontiguousarray(m, np.uint8) for m in masks]
+        if len(ms) != n or any(m is not None and m.shape != (r, c) for m in ms):
+            raise ValueError("masks: None, or one (rows, cols) array or None per image")
+        ip = (C.c_void_p * n)(*[a[0].ctypes.data for a in arrs])
+        mp = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in ms])
+        levels = np.zeros((n, self.n_levels), LEVEL_DTYPE)
+        feats = np.zeros((n, max(feat_cap, 1)), TRAIN_FEATURE_DTYPE)
+        status = np.zeros((n, 2), np.int32)
+        _check(lib().sbm_train_batch(self._h, ip, n, r, c, c * ch, ch, None if masks is None else mp, C.c_float(strong_threshold), num_features,
+                                     _p(levels), _p(feats), feat_cap, _p(status)))
+        return levels, feats[:, :feat_cap], status
+
+    def train_batch(self, imgs: Sequence[np.ndarray], masks: Optional[Sequence[Optional[np.ndarray]]], strong: float, num_features: int):
+        """Detector::addTemplate for every image of a batch of one geometry: a list of (levels, feats), None where
+        addTemplate returns -1.  masks: None, or per image a (rows, cols) array or None."""
+        _, r, c, _ = _img(imgs[0])
+        cap = sum(((r >> l) + 2) // 3 * (((c >> l) + 2) // 3) for l in range(self.n_levels))  # no more maxima than 3x3 cells
+        levels, feats, status = self.train_batch_raw(imgs, masks, strong, num_features, cap)
+        out = []
+        for i in range(len(imgs)):
+            if status[i, 0] == 1:
+                out.append(None)
+                continue
+            if status[i, 0] != 0:
+                raise SbmError(-3, f"image {i}: {status[i, 1]} features exceed the capacity {cap}")
+            out.append((levels[i].copy(), feats[i, : status[i, 1]].copy()))
+        return out
 
     def select_templates(self, idx: Sequence[int]):
         a = np.ascontiguousarray(idx, np.int32)

@@ -31,3 +31,4 @@ using namespace sbm;
 #include "sbm_capi_stages.inc"  // stage entry points, profiling
 #include "sbm_capi_multi.inc"   // RCCL, sharded / banded steps, sbm_match_sharded
 #include "sbm_capi_nms.inc"     // match epilogue + NMS on the device
+#include "sbm_capi_train.inc"   // batched template training on the device

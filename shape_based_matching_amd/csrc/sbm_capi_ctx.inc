@@ -229,6 +229,8 @@ struct sbm_ctx {
     DevBuf d_nms_labels, d_nms_scratch, d_nms_out;
     int32_t* h_nms_counts = nullptr;
     int h_nms_counts_frames = 0;
+    // batched training (sbm_capi_train.inc): the scratch of a batch, grown by the rule of d_nms_scratch; the host form's images, masks and results
+    DevBuf d_train, d_train_in, d_train_mask, d_train_out;
 
     // hipGraph cache for sbm_match_device (one captured graph per distinct argument tuple)
     struct GraphEntry {

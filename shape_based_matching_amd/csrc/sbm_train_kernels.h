@@ -11,9 +11,13 @@
 //   2. (host, sbm_extract_local_maxima) the emitted pixels are sorted row-major and a pixel is dropped when an earlier
 //      KEPT pixel lies within its 5x5 window -- the reference's invalidation among equal-score neighbours, exactly.
 // Maxima at or below the threshold never influence the result: to invalidate a candidate they would need its score.
+// The batched path (sbm_train_batch_device, below) does step 2 and everything after it on the device as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/sbm.h"
+#include "sbm_train_math.h"
 
 namespace sbm {
 
@@ -43,6 +47,323 @@ __global__ __launch_bounds__(256) void k_local_maxima5(const float* __restrict__
         if (!is_max) continue;
         const int k = atomicAdd(count, 1);
         if (k < cap) out_xy[k] = c | (r << 16);
+    }
+}
+
+// ---- batched training (sbm_train_batch_device): everything after the gradient stage, without a host round trip --------
+// Per (image, level): S = the pixels k_local_maxima5 would emit, as a dense flag plane (k_train_maxima); the row-major
+// tie resolution on it and the row-major list of candidates (k_train_resolve); their order (k_train_sort); the
+// selection of scattered features (k_train_select); per image, cropTemplates and the caller's layout (k_train_crop).
+// The scalar rules are those of sbm_train_math.h.  The level is a grid dimension beside the image; the levels of an
+// image lie behind each other in one per-image "pixel space" (planes) and "candidate space" (lists).
+struct TrainCand {
+    int32_t xy;    // x | y << 16
+    int32_t label; // bit index of the one-hot orientation
+    float score;   // squared magnitude
+    float theta;   // angle_ori
+};
+
+struct TrainLevel {
+    int32_t rows, cols;
+    int32_t cand_cap;    // train_cand_bound(rows, cols)
+    uint32_t nf;         // features asked of this level
+    int64_t pix_off;     // of this level in an image's pixel space
+    int64_t cand_off;    // ... candidate space
+    int64_t sort_off;    // ... key space (a power of two >= cand_cap keys per level)
+    const uint8_t* mask; // level's masks (nullptr: none), mask_fs bytes apart (0: one for all images)
+    int64_t mask_fs;
+};
+
+struct TrainPlan {
+    int32_t L, n_images;
+    float thr_sq;
+    int64_t pix_stride, cand_stride, sort_stride; // per image
+    const float* mag;     // [n_images][pix_stride]
+    const float* ori;
+    const uint8_t* quant;
+    uint8_t* flags;       // bit 0: in S; bit 1: kept by the tie resolution
+    TrainCand* cand;      // [n_images][cand_stride]
+    uint64_t* keys;       // [n_images][sort_stride]
+    int32_t* sel;         // [n_images][cand_stride]: the selected candidates, as indices into the level's list
+    uint32_t* kept_xy;    // [n_images][cand_stride]: their positions beyond what LDS holds
+    int32_t* counts;      // [n_images][L][2]: candidates; selected features, -1 = the level failed
+    TrainLevel lv[8];
+};
+
+enum { TRAIN_KEPT_LDS = 4096 };
+
+__global__ __launch_bounds__(256) void k_train_maxima(const TrainPlan p)
+{
+    const TrainLevel& v = p.lv[blockIdx.y];
+    const int64_t base = (int64_t)blockIdx.z * p.pix_stride + v.pix_off;
+    const float* __restrict__ mag = p.mag + base;
+    uint8_t* __restrict__ flags = p.flags + base;
+    const uint8_t* __restrict__ mask = v.mask ? v.mask + (int64_t)blockIdx.z * v.mask_fs : nullptr;
+    const int rows = v.rows, cols = v.cols, n = rows * cols;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+        const int r = idx / cols, c = idx % cols;
+        bool in = r >= 2 && r < rows - 2 && c >= 2 && c < cols - 2;
+        float s = 0.f;
+        if (in) {
+            s = mag[idx];
+            in = s > p.thr_sq;
+        }
+        if (in && mask) { // cv::erode(mask, 3x3, BORDER_REPLICATE); the window of a scanned pixel lies inside the image
+            for (int dr = -1; dr <= 1; ++dr)
+                for (int dc = -1; dc <= 1; ++dc) in = in && mask[idx + dr * cols + dc] != 0;
+        }
+        if (in) {
+            for (int dr = -2; dr <= 2; ++dr)
+                for (int dc = -2; dc <= 2; ++dc) in = in && !(s < mag[idx + dr * cols + dc]);
+        }
+        flags[idx] = in ? 1 : 0;
+    }
+}
+
+// One wave per (image, level) walks the rows.  Lane i owns the columns [i * K, (i + 1) * K): it composes the column
+// maps of its segment, the wave composes the segments' maps by a prefix scan, and the lane replays its segment from its
+// incoming state.  Kept pixels are marked in the flag plane, where the next two rows find them.
+__global__ __launch_bounds__(64) void k_train_resolve(const TrainPlan p)
+{
+    const int l = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
+    const TrainLevel& v = p.lv[l];
+    const int64_t base = (int64_t)img * p.pix_stride + v.pix_off;
+    uint8_t* flags = p.flags + base;
+    const uint8_t* __restrict__ quant = p.quant + base;
+    const float* __restrict__ mag = p.mag + base;
+    const float* __restrict__ ori = p.ori + base;
+    TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + v.cand_off;
+    const int rows = v.rows, cols = v.cols;
+    const int K = (cols + 63) / 64;
+    const int c0 = min(lane * K, cols), c1 = min(c0 + K, cols);
+    int total = 0;
+    for (int r = 2; r < rows - 2; ++r) {
+        uint8_t* f0 = flags + (size_t)r * cols;
+        const uint8_t* f1 = f0 - cols;
+        const uint8_t* f2 = f1 - cols;
+        // a pixel of S has its five columns inside the image
+        auto available = [&](int c) {
+            if (!(f0[c] & 1)) return false;
+            uint32_t above = 0;
+            for (int d = -2; d <= 2; ++d) above |= (uint32_t)f1[c + d] | (uint32_t)f2[c + d];
+            return (above & 2u) == 0;
+        };
+        uint32_t f = TRAIN_TIE_IDENTITY;
+        for (int c = c0; c < c1; ++c) f = train_tie_compose(f, train_tie_fn(available(c)));
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t g = __shfl_up(f, d);
+            if (lane >= d) f = train_tie_compose(g, f);
+        }
+        const uint32_t before = __shfl_up(f, 1);
+        uint32_t state = lane ? train_tie_apply(before, 0) : 0u;
+        int cnt = 0;
+        for (int c = c0; c < c1; ++c) {
+            const bool a = available(c);
+            if (train_tie_keeps(a, state)) {
+                f0[c] = 3;
+                cnt += quant[(size_t)r * cols + c] != 0;
+            }
+            state = train_tie_apply(train_tie_fn(a), state);
+        }
+        int incl = cnt;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        int pos = total + incl - cnt;
+        total += __shfl(incl, 63);
+        if (cnt) {
+            for (int c = c0; c < c1; ++c) {
+                const uint32_t a = quant[(size_t)r * cols + c];
+                if ((f0[c] & 2) && a) {
+                    if (pos < v.cand_cap) {
+                        TrainCand k;
+                        k.xy = c | (r << 16);
+                        k.label = __ffs(a) - 1;
+                        k.score = mag[(size_t)r * cols + c];
+                        k.theta = ori[(size_t)r * cols + c];
+                        cand[pos] = k;
+                    }
+                    ++pos;
+                }
+            }
+        }
+        __syncthreads(); // the marks of this row, before the next row reads them
+    }
+    if (lane == 0) p.counts[((int64_t)img * p.L + l) * 2] = min(total, v.cand_cap);
+}
+
+// bitonic sort of the level's keys (train_key), descending, in global scratch by one workgroup
+__global__ __launch_bounds__(256) void k_train_sort(const TrainPlan p)
+{
+    const int l = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
+    const TrainLevel& v = p.lv[l];
+    const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + v.cand_off;
+    uint64_t* keys = p.keys + (int64_t)img * p.sort_stride + v.sort_off;
+    const int n = p.counts[((int64_t)img * p.L + l) * 2];
+    if (train_level_fails((size_t)n, v.nf)) return;
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int i = tid; i < P; i += 256) keys[i] = i < n ? train_key(__float_as_uint(cand[i].score), (uint32_t)i) : 0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < P / 2; t += 256) {
+                const int i = (t / j) * 2 * j + (t % j);
+                const uint64_t a = keys[i], b = keys[i + j];
+                const bool descending = (i & k) == 0;
+                if ((a < b) == descending) {
+                    keys[i] = b;
+                    keys[i + j] = a;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// selectScatteredFeatures by one wave per (image, level): the candidates in sorted order, 64 at a time -- every lane
+// tests its candidate against the features kept before the chunk, then the chunk's survivors are taken in order, each
+// one striking out the later survivors too close to it.  That is the sequential sweep: a candidate is taken iff it is far
+// from every feature taken before it.
+__global__ __launch_bounds__(64) void k_train_select(const TrainPlan p)
+{
+    __shared__ uint32_t s_kept[TRAIN_KEPT_LDS];
+    const int l = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
+    const TrainLevel& v = p.lv[l];
+    const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + v.cand_off;
+    const uint64_t* __restrict__ keys = p.keys + (int64_t)img * p.sort_stride + v.sort_off;
+    int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + v.cand_off;
+    uint32_t* kept_g = p.kept_xy + (int64_t)img * p.cand_stride + v.cand_off;
+    int32_t* counts = p.counts + ((int64_t)img * p.L + l) * 2;
+    const int n = counts[0];
+    if (train_level_fails((size_t)n, v.nf)) {
+        if (lane == 0) counts[1] = -1;
+        return;
+    }
+    TrainSelect st = train_select_begin((size_t)n, v.nf);
+    int cnt = 0;
+    for (;;) {
+        const float d2 = st.distance * st.distance;
+        for (int first = 0; first < n; first += 64) {
+            const int i = first + lane;
+            int idx = 0, xy = 0;
+            if (i < n) {
+                idx = (int)train_key_index(keys[i]);
+                xy = cand[idx].xy;
+            }
+            const int x = xy & 0xffff, y = xy >> 16;
+            bool alive = i < n;
+            for (int j = 0; j < cnt; ++j) {
+                const uint32_t k = j < TRAIN_KEPT_LDS ? s_kept[j] : kept_g[j];
+                alive = alive && train_far(x, y, (int)(k & 0xffffu), (int)(k >> 16), d2);
+                if ((j & 15) == 15 && !__builtin_amdgcn_ballot_w64(alive)) break;
+            }
+            uint64_t m = __builtin_amdgcn_ballot_w64(alive);
+            while (m) {
+                const int k = __ffsll((unsigned long long)m) - 1;
+                const int kxy = __shfl(xy, k);
+                if (lane == k) {
+                    if (cnt < v.cand_cap) {
+                        if (cnt < TRAIN_KEPT_LDS) s_kept[cnt] = (uint32_t)xy;
+                        else kept_g[cnt] = (uint32_t)xy;
+                        sel[cnt] = idx;
+                    }
+                    alive = false;
+                }
+                ++cnt;
+                alive = alive && train_far(x, y, kxy & 0xffff, kxy >> 16, d2);
+                m = __builtin_amdgcn_ballot_w64(alive);
+            }
+            __syncthreads(); // the chunk's features, before the next chunk reads them
+        }
+        const int next = train_select_next(st, (size_t)cnt, v.nf);
+        if (next == TRAIN_PASS_STOP) break;
+        if (next == TRAIN_PASS_RESTART) cnt = 0;
+    }
+    if (lane == 0) counts[1] = min(cnt, v.cand_cap);
+}
+
+// cropTemplates and the caller's layout, one workgroup per image.  status: {0, features} | {1, first failing level} |
+// {2, features needed} when they exceed feat_cap; the level records of an image that is not ok are zeroed.
+__global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_template_level* __restrict__ levels, sbm_train_feature* __restrict__ feats,
+                                                    int64_t feat_cap, int32_t* __restrict__ status)
+{
+    __shared__ int s_mm[4];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const int32_t* counts = p.counts + (int64_t)img * p.L * 2;
+    levels += (int64_t)img * p.L;
+    feats += (int64_t)img * feat_cap;
+    int failed = -1;
+    int64_t total = 0;
+    for (int l = p.L - 1; l >= 0; --l) {
+        if (counts[2 * l + 1] < 0) failed = l;
+        else total += counts[2 * l + 1];
+    }
+    if (failed >= 0 || total > feat_cap) {
+        if (tid < p.L) {
+            sbm_template_level z;
+            z.width = z.height = z.tl_x = z.tl_y = z.pyramid_level = z.n_features = 0;
+            z.feature_offset = 0;
+            levels[tid] = z;
+        }
+        if (tid == 0) {
+            status[2 * img] = failed >= 0 ? 1 : 2;
+            status[2 * img + 1] = failed >= 0 ? failed : (int32_t)min(total, (int64_t)INT32_MAX);
+        }
+        return;
+    }
+    if (tid == 0) {
+        s_mm[0] = s_mm[1] = INT32_MAX;
+        s_mm[2] = s_mm[3] = INT32_MIN;
+    }
+    __syncthreads();
+    int mn_x = INT32_MAX, mn_y = INT32_MAX, mx_x = INT32_MIN, mx_y = INT32_MIN;
+    for (int l = 0; l < p.L; ++l) {
+        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        for (int k = tid; k < counts[2 * l + 1]; k += 256) {
+            const int xy = cand[sel[k]].xy;
+            const int x = (xy & 0xffff) << l, y = (xy >> 16) << l;
+            mn_x = min(mn_x, x), mn_y = min(mn_y, y), mx_x = max(mx_x, x), mx_y = max(mx_y, y);
+        }
+    }
+    atomicMin(&s_mm[0], mn_x);
+    atomicMin(&s_mm[1], mn_y);
+    atomicMax(&s_mm[2], mx_x);
+    atomicMax(&s_mm[3], mx_y);
+    __syncthreads();
+    const int min_x = train_crop_even(s_mm[0]), min_y = train_crop_even(s_mm[1]);
+    int64_t off = 0;
+    for (int l = 0; l < p.L; ++l) {
+        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        const int nl = counts[2 * l + 1];
+        const TrainBox b = train_crop_level(min_x, min_y, s_mm[2], s_mm[3], l);
+        if (tid == 0) {
+            sbm_template_level t;
+            t.width = b.width;
+            t.height = b.height;
+            t.tl_x = b.tl_x;
+            t.tl_y = b.tl_y;
+            t.pyramid_level = l;
+            t.n_features = nl;
+            t.feature_offset = off;
+            levels[l] = t;
+        }
+        for (int k = tid; k < nl; k += 256) {
+            const TrainCand c = cand[sel[k]];
+            sbm_train_feature f;
+            f.x = (c.xy & 0xffff) - b.tl_x;
+            f.y = (c.xy >> 16) - b.tl_y;
+            f.label = c.label;
+            f.theta = c.theta;
+            feats[off + k] = f;
+        }
+        off += nl;
+    }
+    if (tid == 0) {
+        status[2 * img] = 0;
+        status[2 * img + 1] = (int32_t)total;
     }
 }
 

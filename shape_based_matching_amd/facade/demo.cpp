@@ -23,6 +23,9 @@
 //       one mask per frame: matchBatch / matchAsync+wait / matchBatchNMS / setDevices + matchBatch with a vector of masks
 //       against per-frame match(frame_f, threshold, ids, mask_f); the frames of `batch`, masks that contain the object, cut it,
 //       are absent (empty Mat) or are a non-continuous view, in turn
+//   demo trainbatch <num_features> <loop_fmt> <batch_fmt> <class_id> <image> <mask.pgm|-> [<image> <mask.pgm|-> ...]
+//       the same list of sources trained twice: a loop of addTemplate into one detector, one addTemplates into another;
+//       prints both lists of ids and writes both detectors with writeClasses (`-` = no mask)
 //   demo instance <config.yaml> <image> <threshold>
 //       Detector::getInstance(path) (line2Dup.cpp:1366-1393) + match over the classes the config lists
 #include <chrono>
@@ -456,6 +459,37 @@ int main(int argc, char** argv)
             }
             printf("threads %d calls %d matches %zu %zu different %d\n", n_threads, n_calls, alone[0].size(), alone[1].size(), n_bad);
             return n_bad ? 2 : 0;
+        }
+        if (mode == "trainbatch") {
+            if (argc < 8 || (argc - 6) % 2) return usage();
+            const int num_features = atoi(argv[2]);
+            const std::string loop_fmt = argv[3], batch_fmt = argv[4], class_id = argv[5];
+            std::vector<Mat> sources, masks;
+            for (int a = 6; a + 1 < argc; a += 2) {
+                Mat img = imread(argv[a], IMREAD_UNCHANGED);
+                if (img.empty()) { fprintf(stderr, "cannot read %s\n", argv[a]); return 1; }
+                Mat mask;
+                if (strcmp(argv[a + 1], "-")) {
+                    mask = imread(argv[a + 1], IMREAD_GRAYSCALE);
+                    if (mask.empty()) { fprintf(stderr, "cannot read %s\n", argv[a + 1]); return 1; }
+                }
+                sources.push_back(img);
+                masks.push_back(mask);
+            }
+            line2Dup::Detector loop(num_features, {4, 8}), batch(num_features, {4, 8});
+            std::vector<int> loop_ids;
+            for (size_t k = 0; k < sources.size(); ++k) loop_ids.push_back(loop.addTemplate(sources[k], class_id, masks[k]));
+            const std::vector<int> batch_ids = batch.addTemplates(sources, class_id, masks);
+            std::cout.flush();
+            printf("loop");
+            for (int id : loop_ids) printf(" %d", id);
+            printf("\nbatch");
+            for (int id : batch_ids) printf(" %d", id);
+            printf("\n");
+            loop.writeClasses(loop_fmt);
+            batch.writeClasses(batch_fmt);
+            printf("trained %d and %d templates\n", loop.numTemplates(), batch.numTemplates());
+            return 0;
         }
         if (mode == "instance") {
             if (argc < 5) return usage();

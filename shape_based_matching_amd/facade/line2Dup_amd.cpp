@@ -919,6 +919,9 @@ int Detector::addTemplate(const Mat source, const std::string& class_id, const M
     return template_id;
 }
 
+// addTemplates, the batched form, lives in line2Dup_train_batch.cpp; a changed template set is reported here
+void Detector::templatesChanged() { eng_->templates_changed(); }
+
 // addTemplate_rotate, line2Dup.cpp:1395-1451
 int Detector::addTemplate_rotate(const std::string& class_id, int zero_id, float theta, Point2f center)
 {
