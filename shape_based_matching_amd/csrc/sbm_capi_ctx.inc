@@ -97,10 +97,13 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //   SBM_FUSED_BITS=0          match entry points build the coarsest level's 8 response planes and pack the bit planes from them
 //   SBM_LOCAL_BITS=0|1        refinement pass of a T = 4 strip level on spread bytes | on bit strips (sbm_local_bits.h;
 //                             sbm_set_refine_bits overrides per context)
+//   SBM_SPARSE_STRIPS=0       match entry points build level 0's bit strips whole, inside the one linear-memory launch, instead of
+//                             only in the tiles the coarse candidates' refinement reads (sbm_refine_tiles.h)
 struct Tuning {
     int coarse = 0, quantize = 0, hs0 = 0, hs1 = 0, local_grid = 0, local_waves = 0, local_order = -1;
     bool qs_pack = true, full_lm = false, strip_lm = true, graph_fork = true, fused_bits = true, lm_allty = true;
     int bits_wide = -1, bits_dw = 0, bits_block = -1, match_bands = 0, local_bits = -1;
+    bool sparse_strips = true;
 };
 static const Tuning& tuning()
 {
@@ -129,6 +132,7 @@ static const Tuning& tuning()
         k.lm_allty = num("SBM_LM_ALLTY", 1) != 0;
         k.bits_block = num("SBM_BITS_BLOCK", -1);
         k.local_bits = num("SBM_LOCAL_BITS", -1);
+        k.sparse_strips = num("SBM_SPARSE_STRIPS", 1) != 0;
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
         k.bits_dw = num("SBM_BITS_DW", 0) == 2 ? 2 : (num("SBM_BITS_DW", 0) == 1 ? 1 : 0);
         return k;
@@ -154,6 +158,7 @@ struct sbm_ctx {
     DevBuf d_citems, d_cfoff, d_soff, d_soffbase; // coarse pass: per active template one record, its feature offsets sorted by byte
                                                    // misalignment, the first 64 of them again by slot (k_prep_coarse_items)
     bool citems_dirty = true;
+    DevBuf d_fext;                      // per (template, level): largest feature x | largest feature y << 16 (k_mark_refine_tiles)
     DevBuf d_fxy_s, d_flabel_s, d_fcls; // refinement pass on the strip plane: features sorted by (x / T) & 15 per template level + 17 class offsets
     bool have_thr = false;
     float thr_cached = 0.f;
@@ -178,6 +183,9 @@ struct sbm_ctx {
     // Round 4: a T = 4 strip level that a match entry point builds is stored as BIT STRIPS instead (2 bits per cell and
     // orientation, build_lm_strip4_allty) and refined by k_similarity_local_bits (sbm_local_bits.h)
     DevBuf d_lbits[SBM_MAX_LEVELS];
+    // ... and, as level 0 of a two-level pyramid, only in the tiles the call's coarse candidates read (LM_BIT_STRIPS_SPARSE):
+    // one byte flag per frame and tile (sbm_refine_tiles.h), cleared with the counters, set by k_mark_refine_tiles
+    DevBuf d_tiles;
     // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
     // (sbm_level_forms.h; per level, not per frame: the forms rebuilt on demand cover frame 0 only)
     LevelForms forms[SBM_MAX_LEVELS];
@@ -408,6 +416,11 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             if (c->cfg.T[l] == 4)
                 if (int e = c->d_lbits[l].ensure(B * lbits_frame_bytes(c, l), true)) return e;
         }
+        if (l == 0) {
+            c->d_tiles.release(); // sized by level 0's grid and the batch
+            if (c->d_lbits[0].p)
+                if (int e = c->d_tiles.ensure(B * (size_t)refine_tile_count(cc / c->cfg.T[0], r / c->cfg.T[0]), true)) return e;
+        }
         c->forms[l].forget();
     }
     c->d_blm.release(); // fresh, zeroed: the tails of the bit planes must read as 0 too
@@ -439,6 +452,7 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
     if (int e = c->d_lm[l].ensure((size_t)8 * c->lm_stride[l], true)) return e;
     c->d_lmc[l].release();
     c->d_lbits[l].release();
+    if (l == 0) c->d_tiles.release();
     c->forms[l].forget();
     if (l == c->L - 1) {
         c->d_blm.release();
@@ -636,6 +650,7 @@ PlanInputs plan_inputs(const sbm_ctx* c)
     p.lm_allty = tuning().lm_allty;
     p.fused_bits = tuning().fused_bits;
     p.local_bits = tuning().local_bits;
+    p.sparse_strips = tuning().sparse_strips && c->d_tiles.p != nullptr;
     return p;
 }
 bool coarse_on_bits(const sbm_ctx* c) { return coarse_on_bits(plan_inputs(c)); }
@@ -647,11 +662,13 @@ LmLevelArgs lm_level_args(const sbm_ctx* c, int l, LmForm f, int frames, int beg
     const int64_t stride = c->lm_stride[l];
     // few frames: shorter, more numerous work items
     const LmWork w = lm_work(f, T, c->rows[l], W, H, frames < 4 ? LM_FULL_SPLIT : 1, tuning().lm_allty);
+    const bool strips = f == LM_BIT_STRIPS || f == LM_BIT_STRIPS_SPARSE; // one layout: the kernel's compact == 4
     uint8_t* const lm = f == LM_PLANES8 ? c->d_lm[l].as<uint8_t>() : f == LM_BIT_PLANES ? c->d_blm.as<uint8_t>()
-                      : f == LM_BIT_STRIPS ? c->d_lbits[l].as<uint8_t>() : c->d_lmc[l].as<uint8_t>();
-    const int64_t lm_fs = f == LM_BIT_STRIPS ? lbits_frame_bytes(c, l) : (f == LM_PLANES8 ? 8 : f == LM_BIT_PLANES ? 2 : 1) * stride;
+                      : strips ? c->d_lbits[l].as<uint8_t>() : c->d_lmc[l].as<uint8_t>();
+    const int64_t lm_fs = strips ? lbits_frame_bytes(c, l) : (f == LM_PLANES8 ? 8 : f == LM_BIT_PLANES ? 2 : 1) * stride;
     *blocks = (int)((w.items + 255) / 256);
-    return LmLevelArgs{c->d_quant[l].as<uint8_t>(), lm, stride, c->rows[l], c->cols[l], W, H, T, begin, (int64_t)c->rows[l] * c->cols[l], lm_fs, f, w.split, w.allty};
+    return LmLevelArgs{c->d_quant[l].as<uint8_t>(), lm, stride, c->rows[l], c->cols[l], W, H, T, begin, (int64_t)c->rows[l] * c->cols[l], lm_fs,
+                       strips ? (int32_t)LM_BIT_STRIPS : (int32_t)f, w.split, w.allty};
 }
 
 // level l alone (frame 0) in form f through the one-launch builder
@@ -703,7 +720,8 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
 int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
 {
     const LmForm src = full_lm_source(c->forms[l]);
-    if (src == LM_PLANES8 || src == LM_NONE) return 0;
+    // nothing current: the level's strips were built sparsely (or nothing was built yet: not resident, nothing to do)
+    if (src == LM_PLANES8 || (src == LM_NONE && l >= c->levels_valid)) return 0;
     if (src == LM_SPREAD || src == LM_SPREAD_STRIP) {
         const int T = c->cfg.T[l];
         const int64_t n = (int64_t)T * T * (c->cols[l] / T) * (c->rows[l] / T);
@@ -887,15 +905,24 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
         // every level's linear memories in one launch (block ranges coarsest level first: its blocks -- T * 8 / 4 stores per
         // lane -- are the long ones, and a launch that dispatches its long blocks last ends with a few of them running alone),
         // which also zeroes the per-frame counters and *reset_count
+        // A level planned as sparse bit strips has no share in it: its tiles are built behind the coarse pass (enqueue_sparse_strips);
+        // this launch clears their flags.
         LmArgs a;
         memset(&a, 0, sizeof a);
-        a.n_levels = c->L;
         int blocks = 0;
-        for (int l = c->L - 1, n = 0; l >= 0; --l, blocks += n) a.lv[l] = lm_level_args(c, l, plan.form[l], frames, blocks, &n);
+        for (int l = c->L - 1, n = 0; l >= 0; --l) {
+            if (plan.form[l] == LM_BIT_STRIPS_SPARSE) continue;
+            a.lv[a.n_levels++] = lm_level_args(c, l, plan.form[l], frames, blocks, &n);
+            blocks += n;
+        }
         if (reset_count) {
             a.counters = c->d_counters.as<int32_t>();
             a.out_count = reset_count;
             c->counters_fresh = true;
+            if (plan.form[0] == LM_BIT_STRIPS_SPARSE) {
+                a.clear_tiles = c->d_tiles.as<uint8_t>();
+                a.n_tiles = refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]);
+            }
         }
         SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
@@ -1057,12 +1084,15 @@ int64_t features_in_bounds(const sbm_ctx* c, const DevTL& tl, int rows, int cols
 }
 
 // coarse pass over the active templates (reset + k_similarity_coarse; single-level pyramids emit here)
-int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames = 1)
+// clear_tiles: where its own k_reset runs, that also clears frame 0's refinement-tile flags (a sparse call's retry)
+int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames = 1, bool clear_tiles = false)
 {
     const int L = c->L, lc = L - 1;
     int32_t* counters = c->d_counters.as<int32_t>();
     if (!c->counters_fresh && frames > 1) return fail(SBM_ERR_STATE, "batched template loop without a batched pyramid");
-    if (!c->counters_fresh) hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, s, counters, d_count);
+    if (!c->counters_fresh)
+        hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, s, counters, d_count, clear_tiles ? c->d_tiles.as<uint8_t>() : (uint8_t*)nullptr,
+                           clear_tiles ? refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]) : 0);
     c->counters_fresh = false;
     const int n_active = (int)c->h_active.size();
     if (n_active > 0) {
@@ -1169,7 +1199,9 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
 }
 
 // refinement passes, finest level last (emits the match records)
-int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames = 1, bool raised = false)
+// sparse0: level 0's bit strips were built for this call's candidates alone (enqueue_sparse_strips); the record calls nothing current
+int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames = 1, bool raised = false,
+                  bool sparse0 = false)
 {
     const int L = c->L;
     int32_t* counters = c->d_counters.as<int32_t>();
@@ -1188,7 +1220,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
         int order = c->local_order >= 0 ? c->local_order : (planes > (32 << 20) ? 2 : 0);
         const dim3 local_dim = order == 2 ? dim3((unsigned)(std::min(frames, 64) * local_grid), (unsigned)((frames + 63) / 64))
                                           : dim3(frames, local_grid);
-        const LmForm reads = refine_reads(c->forms[l]);
+        const LmForm reads = l == 0 && sparse0 ? LM_BIT_STRIPS : refine_reads(c->forms[l]);
         if (reads == LM_NONE) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", l);
         const int local_waves = tuning().local_waves; // 4 or 16
         const bool small_blocks = local_waves ? local_waves == 4 : frames >= 4;
@@ -1237,11 +1269,46 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
     return 0;
 }
 
-// the template loop: coarse pass, then the refinement passes
+// The template loop of this call refines level 0 on sparse bit strips: the plan of a match entry point says so and the
+// record calls nothing of the level current (a reader since -- ensure_local_forms, ensure_full_lm -- would have rebuilt a form
+// from the orientation map, and the loop reads that).
+bool sparse_refine(const sbm_ctx* c)
+{
+    return c->L == 2 && c->levels_valid == c->L && refine_reads(c->forms[0]) == LM_NONE &&
+           plan_build(plan_inputs(c), all_rows_ok(c), true).form[0] == LM_BIT_STRIPS_SPARSE;
+}
+
+// Between the coarse pass and the refinement of a sparse call: flag the tiles of level 0 that the candidates' patches lie in,
+// then build the bit strips of the flagged tiles from the orientation map (the bit-strip share of k_build_lm_rows; a
+// workgroup whose flag is 0 returns at once).  The unflagged tiles keep whatever an earlier call left: nothing reads them.
+int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
+{
+    const int T = c->cfg.T[0], W = c->cols[0] / T, H = c->rows[0] / T, n_tiles = refine_tile_count(W, H);
+    SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
+               (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles);
+    HIP_TRY(hipGetLastError());
+    LmArgs a;
+    memset(&a, 0, sizeof a);
+    a.n_levels = 1;
+    int blocks = 0;
+    a.lv[0] = lm_level_args(c, 0, LM_BIT_STRIPS_SPARSE, frames, 0, &blocks);
+    if (blocks != n_tiles) return fail(SBM_ERR_STATE, "level 0: %d strip workgroups for %d refinement tiles", blocks, n_tiles);
+    a.tile_flags = c->d_tiles.as<uint8_t>();
+    a.n_tiles = n_tiles;
+    SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the template loop: coarse pass, then the refinement passes -- with level 0's strips built in between where the call
+// holds them sparsely
 int enqueue_loop(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, int32_t* d_count, int frames, bool raised)
 {
-    if (int e = enqueue_coarse(c, s, d_out, cap, d_count, frames)) return e;
-    return enqueue_local(c, s, d_out, cap, d_count, frames, raised);
+    const bool sparse = sparse_refine(c);
+    if (int e = enqueue_coarse(c, s, d_out, cap, d_count, frames, sparse)) return e;
+    if (sparse)
+        if (int e = enqueue_sparse_strips(c, s, frames)) return e;
+    return enqueue_local(c, s, d_out, cap, d_count, frames, raised, sparse);
 }
 
 // The template loop on a pyramid that the stage entry points built (response planes at every level): its T = 4 refinement
@@ -1252,6 +1319,19 @@ int ensure_local_forms(sbm_ctx* c, hipStream_t s)
     const PlanInputs pin = plan_inputs(c);
     for (int l = 0; l < c->L - 1; ++l) {
         LevelForms& f = c->forms[l];
+        if (refine_reads(f) == LM_NONE) {
+            // nothing current: a match call built the level's strips sparsely.  Whole strips from the orientation map, or the
+            // response planes where strips are not wanted (any more)
+            if (local_bits_wanted(pin, l) && lm_rows_ok(c->d_quant[l].as<uint8_t>(), c->cols[l], c->cfg.T[l])) {
+                if (int e = c->d_lbits[l].ensure((size_t)lbits_frame_bytes(c, l), true)) return e;
+                if (int e = launch_lm_level(c, s, l, LM_BIT_STRIPS)) return e;
+                f.bit_strips = true;
+            } else {
+                if (int e = launch_build_lm(c, s, l)) return e;
+                f.planes8 = true;
+            }
+            continue;
+        }
         if (f.bit_strips) {
             // strips are current.  Asked for the byte form since, and the response planes are there: read those
             if (!local_bits_wanted(pin, l) && f.planes8) f.bit_strips = false;

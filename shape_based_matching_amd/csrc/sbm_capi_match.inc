@@ -91,6 +91,7 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
     std::vector<DevTL> tls((size_t)n_templates * L);
     std::vector<uint32_t> fxy((size_t)n_features, 0);
     std::vector<uint8_t> flabel((size_t)n_features, 0), flevel((size_t)n_features, 0);
+    std::vector<uint32_t> fext((size_t)n_templates * L, 0); // largest feature x | largest feature y << 16 per template level
     for (int t = 0; t < n_templates; ++t)
         for (int l = 0; l < L; ++l) {
             const sbm_template_level& s = levels[(size_t)t * L + l];
@@ -105,6 +106,8 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
                 fxy[s.feature_offset + i] = (uint32_t)f.x | ((uint32_t)f.y << 16);
                 flabel[s.feature_offset + i] = (uint8_t)f.label;
                 flevel[s.feature_offset + i] = (uint8_t)l;
+                uint32_t& e = fext[(size_t)t * L + l];
+                e = std::max(e & 0xffffu, (uint32_t)f.x) | (std::max(e >> 16, (uint32_t)f.y) << 16);
             }
             DevTL d;
             d.width = s.width;
@@ -153,7 +156,8 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
         (rc = c->d_flabel.ensure(flabel.size())) || (rc = c->d_flevel.ensure(flevel.size())) ||
         (rc = c->d_foff.ensure(fxy.size() * 4)) || (rc = c->d_class.ensure(cls.size() * 4)) ||
         (rc = c->d_tid.ensure(tid.size() * 4)) || (rc = c->d_fxy_s.ensure(fxy_s.size() * 4)) ||
-        (rc = c->d_flabel_s.ensure(flabel_s.size())) || (rc = c->d_fcls.ensure(std::max<size_t>(fcls.size(), 1) * 2)))
+        (rc = c->d_flabel_s.ensure(flabel_s.size())) || (rc = c->d_fcls.ensure(std::max<size_t>(fcls.size(), 1) * 2)) ||
+        (rc = c->d_fext.ensure(std::max<size_t>(fext.size(), 1) * 4)))
         return rc;
     HIP_TRY(hipDeviceSynchronize()); // frames still in flight on the caller's streams read the old tables
     if (!tls.empty()) HIP_TRY(hipMemcpy(c->d_tls.p, tls.data(), tls.size() * sizeof(DevTL), hipMemcpyHostToDevice));
@@ -165,6 +169,7 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
         HIP_TRY(hipMemcpy(c->d_flabel_s.p, flabel_s.data(), flabel_s.size(), hipMemcpyHostToDevice));
     }
     if (!fcls.empty()) HIP_TRY(hipMemcpy(c->d_fcls.p, fcls.data(), fcls.size() * 2, hipMemcpyHostToDevice));
+    if (!fext.empty()) HIP_TRY(hipMemcpy(c->d_fext.p, fext.data(), fext.size() * 4, hipMemcpyHostToDevice));
     if (n_templates) {
         HIP_TRY(hipMemcpy(c->d_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c->d_tid.p, tid.data(), tid.size() * 4, hipMemcpyHostToDevice));

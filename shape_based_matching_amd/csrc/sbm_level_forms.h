@@ -16,6 +16,9 @@ enum LmForm : int32_t {
     LM_SPREAD_STRIP = 2, // the same plane strip-interleaved (d_lmc, lm_strip_offset)
     LM_BIT_PLANES = 3,   // the coarsest level's 16 bit planes (d_blm, sbm_coarse_bits.h)
     LM_BIT_STRIPS = 4,   // a T = 4 refinement level as bit strips (d_lbits, sbm_local_bits.h)
+    // the same strips, but only in the tiles the call's coarse candidates read (sbm_refine_tiles.h): built between the call's
+    // coarse pass and its refinement, for that refinement alone -- not a layout of its own, and nothing the call leaves behind
+    LM_BIT_STRIPS_SPARSE = 5,
 };
 
 // Per level: every field says "this buffer holds the level's current contents" and nothing else.  Several may be set (a
@@ -29,7 +32,9 @@ struct LevelForms {
     bool bit_strips = false;   // d_lbits[l]
     bool bit_planes = false;   // d_blm (coarsest level only)
     void forget() { *this = LevelForms{}; }
-    void set(LmForm f) // the level was rebuilt in form f: every other buffer is stale
+    // the level was rebuilt in form f: every other buffer is stale.  LM_BIT_STRIPS_SPARSE leaves NOTHING current: the strips
+    // are whole in no frame, and the orientation map (levels_valid) is what the next reader rebuilds its form from.
+    void set(LmForm f)
     {
         forget();
         planes8 = f == LM_PLANES8;
@@ -40,7 +45,9 @@ struct LevelForms {
     }
 };
 
-// What the refinement pass reads of a level: the bit strips, else the spread plane unless the 8 planes are current, else those
+// What the refinement pass reads of a level: the bit strips, else the spread plane unless the 8 planes are current, else those.
+// LM_NONE: nothing is current -- after a sparse match call; the reader rebuilds from the resident orientation map
+// (ensure_local_forms), or is that call's own refinement, which builds its tiles (sparse_refine).
 inline LmForm refine_reads(const LevelForms& f)
 {
     if (f.bit_strips) return LM_BIT_STRIPS;
@@ -49,7 +56,8 @@ inline LmForm refine_reads(const LevelForms& f)
 }
 
 // What the 8 response planes of a level are made from when a stage entry point asks for them: themselves, the spread plane
-// (expanded), or -- returned as the form that is current -- the resident orientation map
+// (expanded), or -- returned as the form that is current, LM_NONE where none is (a sparse match call) -- the resident
+// orientation map
 inline LmForm full_lm_source(const LevelForms& f)
 {
     if (f.planes8) return LM_PLANES8;
@@ -80,6 +88,7 @@ struct PlanInputs {
     float thr = 0.f;
     bool full_lm = false, strip_lm = true, lm_allty = true, fused_bits = true; // SBM_FULL_LM, SBM_STRIP_LM, SBM_LM_ALLTY, SBM_FUSED_BITS
     int local_bits = -1;                                                       // SBM_LOCAL_BITS
+    bool sparse_strips = false; // level 0 of a two-level pyramid as LM_BIT_STRIPS_SPARSE (off here; on in a context unless SBM_SPARSE_STRIPS=0)
     int W(int l) const { return cols[l] / T[l]; }
     int H(int l) const { return rows[l] / T[l]; }
 };
@@ -123,6 +132,9 @@ inline BuildPlan plan_build(const PlanInputs& p, bool one_launch, bool match_ent
         b.form[l] = p.strip_lm && (p.W(l) & 15) == 0 ? LM_SPREAD_STRIP : LM_SPREAD;
         if (match_entry && local_bits_wanted(p, l) && p.has_bit_strips[l]) b.form[l] = LM_BIT_STRIPS;
     }
+    // Two levels: the coarse candidates are the refinement's, so level 0's strips wait for them.  (Deeper pyramids keep the
+    // whole build: refinement at an intermediate level moves the candidates before level 0 is read.)
+    if (p.sparse_strips && p.L == 2 && b.form[0] == LM_BIT_STRIPS) b.form[0] = LM_BIT_STRIPS_SPARSE;
     // the coarsest level of a coarse pass on bit planes: those only, inside the launch (a wave's 256 positions must not
     // straddle two sub-planes), else the spread plane and a pack launch; without either, the 8 planes (packed on demand)
     const int lc = p.L - 1;
@@ -160,7 +172,7 @@ inline LmWork lm_work(LmForm f, int T, int rows, int W, int H, int split, bool l
     if (f == LM_PLANES8) {
         w.split = split;
         w.items *= w.split;
-    } else if (f == LM_BIT_STRIPS) {
+    } else if (f == LM_BIT_STRIPS || f == LM_BIT_STRIPS_SPARSE) { // (sparse: the later launch's share; none of the pyramid's)
         w.allty = 1;
         w.items = (int64_t)((W + 31) >> 5) * ((H + 31) >> 5) * 256;
     } else if (f == LM_SPREAD_STRIP) { // a workgroup per 16 grid rows x 64 cells, for all four ty at T = 4 (all-ty threads), else per ty

@@ -421,6 +421,12 @@ struct LmArgs {
     int32_t n_levels;
     int32_t* counters;  // may be null
     int32_t* out_count; // may be null
+    // Refinement tiles (sbm_refine_tiles.h), n_tiles byte flags per frame.  clear_tiles (may be null): zeroed with the
+    // counters, for k_mark_refine_tiles further down the stream.  tile_flags (may be null): a workgroup of a bit-strip level
+    // builds its tile only where the flag is set.
+    uint8_t* clear_tiles;
+    const uint8_t* tile_flags;
+    int32_t n_tiles;
 };
 
 __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
@@ -431,6 +437,8 @@ __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
     if (blockIdx.x == 0 && a.counters) {
         if (threadIdx.x < CTR_STRIDE) a.counters[frame * CTR_STRIDE + threadIdx.x] = 0;
         if (threadIdx.x < 2 && a.out_count) a.out_count[frame * 2 + threadIdx.x] = 0;
+        if (a.clear_tiles)
+            for (int i = threadIdx.x; i < a.n_tiles; i += 256) a.clear_tiles[frame * a.n_tiles + i] = 0;
     }
     // the level whose block range holds this block (the host orders the ranges heaviest blocks first)
     int l = 0, lb = -1;
@@ -438,6 +446,8 @@ __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
     for (int i = 0; i < SBM_MAX_LEVELS; ++i)
         if (i < a.n_levels && (int)blockIdx.x >= a.lv[i].block_begin && a.lv[i].block_begin > lb) l = i, lb = a.lv[i].block_begin;
     const LmLevelArgs& p = a.lv[l];
+    // a bit-strip tile that no candidate's refinement reads: nothing to build (the whole workgroup leaves, before its first load)
+    if (a.tile_flags && p.allty && p.compact == 4 && a.tile_flags[frame * a.n_tiles + ((int)blockIdx.x - p.block_begin)] == 0) return;
     const int64_t item = (int64_t)((int)blockIdx.x - p.block_begin) * 256 + threadIdx.x;
     const uint8_t* q = p.q + frame * p.q_fs;
     uint8_t* lm = p.lm + frame * p.lm_fs;

@@ -1,0 +1,95 @@
+// sbm_refine_tiles.h — which tiles of a T = 4 level's bit strips (sbm_local_bits.h) the refinement of one coarse candidate
+// reads.  A match call whose plan holds level 0 as LM_BIT_STRIPS_SPARSE (sbm_level_forms.h) builds the strips only in the
+// tiles that k_mark_refine_tiles flags by this arithmetic.  Plain integer code, no HIP types: the kernels use it on the
+// device, tests/test_refine_tiles.py compiles it for the CPU suite.
+//
+// A TILE is one workgroup of build_lm_strip4_allty<true> (sbm_lm_kernels.h): RT_STRIPS strips of 16 cells x RT_ROWS grid
+// rows, for all 128 (sub-plane, orientation) planes; tile (tx, ty) of a W x H grid has index ty * ((W + 31) / 32) + tx, the
+// workgroup's block number inside its level.
+//
+// What local_best_bits loads for a feature at pixel (x, y), cell (gx0, gy0) = (x / 4, y / 4), strip s = gx0 / 16:
+//     dwords  lm_bits_offset(plane, s, gy0) + r  and  ... + r + H,   r = 0 .. 15
+// i.e. rows gy0 .. gy0 + 15 of strips s and s + 1.  The index is flat: a row past H - 1 is row (gy0 + r - H) of the NEXT strip
+// (strips s + 1 and s + 2), and a strip past the last one is strip 0, 1, ... of the next plane -- the same tile column as
+// that strip of any plane, since a tile holds all planes.  Behind the last plane lies the zero tail, which needs no tile.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SBM_RT_HD __host__ __device__ __forceinline__
+#else
+#define SBM_RT_HD inline
+#endif
+
+namespace sbm {
+
+constexpr int RT_STRIPS = 2; // strips of 16 cells per tile
+constexpr int RT_ROWS = 32;  // grid rows per tile
+
+SBM_RT_HD int refine_tile_cols(int W) { return (W + 16 * RT_STRIPS - 1) / (16 * RT_STRIPS); }
+SBM_RT_HD int refine_tile_rows(int H) { return (H + RT_ROWS - 1) / RT_ROWS; }
+SBM_RT_HD int refine_tile_count(int W, int H) { return refine_tile_cols(W) * refine_tile_rows(H); }
+
+// Where the refinement of a candidate looks (similarityLocal's caller, line2Dup.cpp:1234-1262): the candidate's position one
+// level down, clamped so that the template and the 16 x 16 search window stay inside the level, and the window's origin.
+// cx, cy: Match::x, ::y at the level above; width, height: the template's box at this level.
+struct RefineOrigin {
+    int x, y;   // the clamped position
+    int ox, oy; // pixel offset added to every feature: the window's first cell
+};
+SBM_RT_HD RefineOrigin refine_origin(int cx, int cy, int width, int height, int rows, int cols, int T)
+{
+    const int border = 8 * T;
+    int x = cx * 2 + 1, y = cy * 2 + 1;
+    const int max_x = cols - width - border, max_y = rows - height - border;
+    x = x < border ? border : x;
+    y = y < border ? border : y;
+    x = x > max_x ? max_x : x;
+    y = y > max_y ? max_y : y;
+    return RefineOrigin{x, y, (x / T - 8) * T, (y / T - 8) * T};
+}
+
+// The strips and rows a candidate's patches cover, before wrapping (refine_tiles_for_each wraps):
+//   strips s0 .. s1, rows r0 .. r1   the patch rows below H of every in-bounds feature, strips s and s + 1
+//   strips s0 + 1 .. s1 + 1, rows 0 .. over   the flat overrun of patches that pass row H - 1 (over < 0: none)
+struct RefineTiles {
+    int s0, s1, r0, r1, over;
+    bool any; // false: no feature of the box can lie inside the level
+};
+SBM_RT_HD RefineTiles refine_tiles(const RefineOrigin& o, int width, int height, int rows, int cols, int T, int W, int H)
+{
+    RefineTiles t{0, 0, 0, 0, -1, false};
+    // in-bounds features (fx < width, fy < height) land on pixels [ox, ox + width) x [oy, oy + height), cut to the level
+    const int x_lo = o.ox > 0 ? o.ox : 0, x_hi = o.ox + width - 1 < cols - 1 ? o.ox + width - 1 : cols - 1;
+    const int y_lo = o.oy > 0 ? o.oy : 0, y_hi = o.oy + height - 1 < rows - 1 ? o.oy + height - 1 : rows - 1;
+    if (x_lo > x_hi || y_lo > y_hi) return t;
+    t.any = true;
+    if (H < 16) { // a patch is longer than a strip: everything
+        t.s1 = (W >> 4) - 1;
+        t.r1 = H - 1;
+        return t;
+    }
+    const int gy_hi = y_hi / T + 15;
+    t.s0 = (x_lo / T) >> 4;
+    t.s1 = ((x_hi / T) >> 4) + 1;
+    t.r0 = y_lo / T;
+    t.r1 = gy_hi < H - 1 ? gy_hi : H - 1;
+    t.over = gy_hi >= H ? gy_hi - H : -1;
+    return t;
+}
+
+// mark(tile index) for every tile of the footprint; a tile may be named more than once
+template <class F>
+SBM_RT_HD void refine_tiles_for_each(const RefineTiles& t, int W, int H, F mark)
+{
+    if (!t.any) return;
+    (void)H;
+    const int ns = W >> 4, n_cb = refine_tile_cols(W);
+    for (int s = t.s0; s <= t.s1; ++s)
+        for (int ty = t.r0 / RT_ROWS; ty <= t.r1 / RT_ROWS; ++ty) mark(ty * n_cb + (s % ns) / RT_STRIPS);
+    if (t.over >= 0)
+        for (int s = t.s0 + 1; s <= t.s1 + 1; ++s)
+            for (int ty = 0; ty <= t.over / RT_ROWS; ++ty) mark(ty * n_cb + (s % ns) / RT_STRIPS);
+}
+
+} // namespace sbm

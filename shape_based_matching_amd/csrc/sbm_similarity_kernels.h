@@ -10,6 +10,7 @@
 #include "sbm_lm_kernels.h" // response4: the refinement pass applies the response LUT to spread bytes
 
 #include "sbm_local_bits.h"
+#include "sbm_refine_tiles.h"
 
 namespace sbm {
 
@@ -397,11 +398,40 @@ __global__ __launch_bounds__(256) void k_copy_bytes(const uint8_t* __restrict__ 
 }
 
 // zero the per-call counters (one launch instead of two memsets)
-__global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ out_count)
+// tiles (may be null): frame 0's refinement-tile flags (sbm_refine_tiles.h), cleared for k_mark_refine_tiles
+__global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ out_count, uint8_t* __restrict__ tiles, int n_tiles)
 {
     top_wave_priority();
     for (int i = threadIdx.x; i < CTR_STRIDE; i += blockDim.x) counters[i] = 0; // layout: sbm_common.h CTR_*
     if (threadIdx.x < 2) out_count[threadIdx.x] = 0;
+    if (tiles)
+        for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) tiles[i] = 0;
+}
+
+// Between the coarse pass and the refinement of a level held as sparse bit strips (LM_BIT_STRIPS_SPARSE): a thread per coarse
+// candidate flags the tiles its refinement will read (refine_tiles: every dword local_best_bits can load for it), for the
+// k_build_lm_rows launch that follows.  grid = (blocks, frames); rows .. H: the refinement level's geometry.
+// fext[t * L + l] = largest feature x | largest feature y << 16 of template t's level l: the box the footprint is taken of
+// is the features' own (the reference's templates have features AT x = width, cropTemplates line2Dup.cpp:148, and an
+// uploaded template may declare any box), while the clamps use the declared one as the refinement pass does.
+__global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restrict__ cands, const int32_t* __restrict__ counters, int cand_cap,
+                                                           int rows, int cols, int T, int W, int H, const uint32_t* __restrict__ fext, int L,
+                                                           int l, uint8_t* __restrict__ tiles, int n_tiles)
+{
+    raise_wave_priority();
+    const size_t frame = blockIdx.y;
+    const int n_all = counters[frame * CTR_STRIDE + CTR_COUNT];
+    const int n = n_all < cand_cap ? n_all : cand_cap;
+    uint8_t* const flags = tiles + frame * n_tiles;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const Cand c = cands[frame * cand_cap + i];
+        if (c.raw < 0) continue;
+        const RefineOrigin o = refine_origin(c.x, c.y, c.next_width, c.next_height, rows, cols, T);
+        const uint32_t ext = fext[(size_t)c.t * L + l];
+        refine_tiles_for_each(refine_tiles(o, (int)(ext & 0xffff) + 1, (int)(ext >> 16) + 1, rows, cols, T, W, H), W, H, [&](int tile) {
+            if (tile >= 0 && tile < n_tiles) flags[tile] = 1;
+        });
+    }
 }
 
 // Which (position chunk, template slot, frame) a workgroup of the coarse pass works on.  Pure speed: any bijection
@@ -991,7 +1021,7 @@ __device__ __forceinline__ void similarity_local_body(SBM_LOCAL_PARAMS)
     }
     const int g_first = ORDER == 2 ? (int)blockIdx.x : slot, g_step = ORDER == 2 ? (int)gridDim.x : n_slots;
     __shared__ uint32_t s_part[LW][2][64];
-    const int border = 8 * T, offset = T / 2 + (T % 2 - 1);
+    const int offset = T / 2 + (T % 2 - 1);
     unsigned long long stat_bytes = 0;
     for (int g = g_first; g < tot; g += g_step) {
         size_t frame = frame_wg;
@@ -1017,13 +1047,8 @@ __device__ __forceinline__ void similarity_local_body(SBM_LOCAL_PARAMS)
         tl.height = c.next_height;
         tl.nf = c.next_nf;
         tl.feat_off = c.next_feat_off;
-        int x = c.x * 2 + 1, y = c.y * 2 + 1;
-        const int max_x = cols - tl.width - border, max_y = rows - tl.height - border;
-        x = x < border ? border : x;
-        y = y < border ? border : y;
-        x = x > max_x ? max_x : x;
-        y = y > max_y ? max_y : y;
-        const int ox = (x / T - 8) * T, oy = (y / T - 8) * T;
+        const RefineOrigin org = refine_origin(c.x, c.y, tl.width, tl.height, rows, cols, T); // (k_mark_refine_tiles: the same)
+        const int x = org.x, y = org.y, ox = org.ox, oy = org.oy;
         uint32_t best = 0;
         if constexpr (COMPACT == 3) {
             // bit strips (sbm_local_bits.h): one wave per candidate (LW == 1), the maximum comes back in key form
