@@ -84,6 +84,8 @@ def lib() -> C.CDLL:
         L.sbo_coarse_bytes.restype = i64
         L.sbo_add_template.argtypes = [vp, i32, i32, i32, i32, vp, i32, f32, f32, i32, vp, vp, i64]
         L.sbo_add_template.restype = i32
+        L.sbo_add_template_planes.argtypes = [vp, vp, vp, vp, vp, vp, i32, f32, i32, vp, vp, i64]
+        L.sbo_add_template_planes.restype = i32
         L.sbo_add_template_rotate.argtypes = [vp, vp, i32, f32, f32, f32, vp, vp]
         L.sbo_add_template_rotate.restype = i32
         _lib = L
@@ -313,6 +315,44 @@ def add_template(img: np.ndarray, mask: Optional[np.ndarray], n_levels: int, num
         return None
     n = int(levels["n_features"].sum())
     return levels, feats[:n].copy()
+
+
+def add_template_failing_level(img: np.ndarray, mask: Optional[np.ndarray], n_levels: int, num_features: int,
+                                weak: float = 30.0, strong: float = 60.0) -> int:
+    """The pyramid level at which Detector::addTemplate gives up (extractTemplate returns false), -1 where it succeeds.
+    sbo_add_template writes a level's record once the level has succeeded and stops at the first that does not."""
+    img, r, c, ch = _img(img)
+    m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+    levels = np.zeros(n_levels, LEVEL_DTYPE)
+    levels["pyramid_level"] = -1
+    cap = r * c
+    feats = np.zeros(cap, TRAIN_FEATURE_DTYPE)
+    rc = lib().sbo_add_template(_p(img), r, c, c * ch, ch, _p(m), n_levels, C.c_float(weak), C.c_float(strong),
+                                num_features, _p(levels), _p(feats), cap)
+    if rc >= 0:
+        return -1
+    return int(np.nonzero(levels["pyramid_level"] < 0)[0][0])
+
+
+def add_template_planes(planes, num_features: int, strong: float = 60.0):
+    """Detector::addTemplate's level loop on given planes: per level (magnitude f32, one-hot angle u8, angle_ori f32,
+    mask u8 or None; the masks all given or all None).  Returns (levels, train_feats), or the failing level as an int."""
+    mags = [np.ascontiguousarray(p[0], np.float32) for p in planes]
+    angs = [np.ascontiguousarray(p[1], np.uint8) for p in planes]
+    oris = [np.ascontiguousarray(p[2], np.float32) for p in planes]
+    masks = None if planes[0][3] is None else [np.ascontiguousarray(p[3], np.uint8) for p in planes]
+    n = len(planes)
+    ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
+    rows = np.asarray([m.shape[0] for m in mags], np.int32)
+    cols = np.asarray([m.shape[1] for m in mags], np.int32)
+    levels = np.zeros(n, LEVEL_DTYPE)
+    cap = int(sum(m.size for m in mags))
+    feats = np.zeros(cap, TRAIN_FEATURE_DTYPE)
+    rc = lib().sbo_add_template_planes(ptrs(mags), ptrs(angs), ptrs(oris), None if masks is None else ptrs(masks), _p(rows), _p(cols),
+                                       n, C.c_float(strong), num_features, _p(levels), _p(feats), cap)
+    if rc < 0:
+        return -1 - rc
+    return levels, feats[: int(levels["n_features"].sum())].copy()
 
 
 def add_template_rotate(levels: np.ndarray, feats: np.ndarray, theta: float, center: Tuple[float, float]):

@@ -1,13 +1,18 @@
 // Stand-in for the part of OpenCV 4's core module that the reference's line2Dup.cpp compiles against.
 //
-// TEST INFRASTRUCTURE ONLY (oracle/ref_match.mk).  Written for this project; it shares no code with OpenCV or with the
+// TEST INFRASTRUCTURE ONLY (oracle/ref_match.mk, oracle/ref_train.mk).  Written for this project; it shares no code with OpenCV or with the
 // product's own cv:: subset (include/sbm_cvlite.h), so that a misreading in one cannot hide on both sides of the
 // comparison the reference binary makes.
 //
 // What the match half runs has a real body: Mat (create, zeros, ptr, at, step1, size, type, empty, ROI, clone,
 // convertTo 8U -> 16U), Mat_, Size, Point, Rect, Ptr / makePtr, CV_Assert / CV_Error / Exception, format.
+// The training half (oracle/ref_train.mk) adds what ColorGradientPyramid::extractTemplate itself calls: erode with the
+// default 3x3 element and BORDER_REPLICATE, and the Mat(size, CV_8UC1, Scalar) fill.
 // Everything else the file names (the gradient half's filters, FileStorage I/O, geometry transforms) is declared so
-// the translation unit compiles, and throws cv::Exception if it is ever called.
+// the translation unit compiles, and throws cv::Exception if it is ever called on an image.  On an EMPTY Mat the
+// gradient half's filters and Mat arithmetic (GaussianBlur, Sobel, phase, pyrDown, mul, +, convertTo) do nothing and
+// return an empty Mat: that is how the training driver obtains a ColorGradientPyramid, whose constructor and pyrDown()
+// call update(), without any gradient arithmetic (see oracle/ref_train_driver.cpp).
 //
 // Allocation follows OpenCV: rows are continuous (step == cols * elemSize) and the buffer starts on a 64-byte
 // boundary (orUnaligned8u's scalar prologue depends on the alignment).  Unlike OpenCV, every buffer is zero-filled and
@@ -87,7 +92,7 @@ inline String format(const char* fmt, ...) {
 }
 
 [[noreturn]] inline void not_in_stand_in(const char* what) {
-    throw Exception(Error::StsNotImplemented, std::string(what) + " is not part of the match-half stand-in", what,
+    throw Exception(Error::StsNotImplemented, std::string(what) + " is not part of the stand-in", what,
                     __FILE__, __LINE__);
 }
 
@@ -220,6 +225,10 @@ public:
 
     // the one conversion the match half makes: similarity_64's 8-bit sums widened to CV_16U, alpha 1, beta 0
     void convertTo(Mat& dst, int rtype, double alpha = 1, double beta = 0) const {
+        if (empty()) {
+            dst = Mat();
+            return;
+        }
         if (rtype < 0) rtype = depth();
         if (!(depth() == CV_8U && channels() == 1 && CV_MAT_DEPTH(rtype) == CV_16U && alpha == 1 && beta == 0))
             not_in_stand_in("Mat::convertTo (other than 8U -> 16U)");
@@ -241,10 +250,16 @@ public:
         return *this;
     }
 
-    Mat mul(const Mat&, double = 1) const { not_in_stand_in("Mat::mul"); }
+    Mat mul(const Mat& m, double = 1) const {
+        if (empty() && m.empty()) return Mat();
+        not_in_stand_in("Mat::mul");
+    }
 };
 
-inline Mat operator+(const Mat&, const Mat&) { not_in_stand_in("Mat + Mat"); }
+inline Mat operator+(const Mat& a, const Mat& b) {
+    if (a.empty() && b.empty()) return Mat();
+    not_in_stand_in("Mat + Mat");
+}
 inline Mat operator>(const Mat&, double) { not_in_stand_in("Mat > scalar"); }
 inline void Mat::copyTo(Mat&, const Mat&) const { not_in_stand_in("Mat::copyTo with a mask"); }
 
@@ -268,12 +283,38 @@ private:
     }
 };
 
-// ---- declared so the file compiles; the match half never calls them ------------------------------------------
-inline void GaussianBlur(const Mat&, Mat&, Size, double, double = 0, int = BORDER_DEFAULT) { not_in_stand_in("GaussianBlur"); }
-inline void Sobel(const Mat&, Mat&, int, int, int, int = 3, double = 1, double = 0, int = BORDER_DEFAULT) { not_in_stand_in("Sobel"); }
-inline void phase(const Mat&, const Mat&, Mat&, bool = false) { not_in_stand_in("phase"); }
-inline void pyrDown(const Mat&, Mat&, const Size& = Size(), int = BORDER_DEFAULT) { not_in_stand_in("pyrDown"); }
-inline void erode(const Mat&, Mat&, const Mat&, Point = Point(-1, -1), int = 1, int = BORDER_CONSTANT) { not_in_stand_in("erode"); }
+// ---- the gradient half's filters: empty in, empty out; on an image they throw -----------------------------------
+inline void empty_or_refuse(const Mat& src, Mat& dst, const char* what) {
+    if (!src.empty()) not_in_stand_in(what);
+    dst = Mat();
+}
+inline void GaussianBlur(const Mat& s, Mat& d, Size, double, double = 0, int = BORDER_DEFAULT) { empty_or_refuse(s, d, "GaussianBlur"); }
+inline void Sobel(const Mat& s, Mat& d, int, int, int, int = 3, double = 1, double = 0, int = BORDER_DEFAULT) { empty_or_refuse(s, d, "Sobel"); }
+inline void phase(const Mat& x, const Mat&, Mat& d, bool = false) { empty_or_refuse(x, d, "phase"); }
+inline void pyrDown(const Mat& s, Mat& d, const Size& = Size(), int = BORDER_DEFAULT) { empty_or_refuse(s, d, "pyrDown"); }
+
+// erode as extractTemplate calls it: the default element (an empty Mat: the 3x3 rectangle anchored at its centre), one
+// iteration, BORDER_REPLICATE, on an 8-bit single-channel image -- the minimum over the window, rows and columns
+// outside the image standing for the nearest one inside
+inline void erode(const Mat& src, Mat& dst, const Mat& element, Point anchor = Point(-1, -1), int iterations = 1, int border = BORDER_CONSTANT) {
+    if (!(element.empty() && anchor.x == -1 && anchor.y == -1 && iterations == 1 && border == BORDER_REPLICATE && src.type() == CV_8UC1 &&
+          !src.empty()))
+        not_in_stand_in("erode (other than 3x3, BORDER_REPLICATE, 8UC1)");
+    Mat out(src.rows, src.cols, CV_8UC1);
+    for (int r = 0; r < src.rows; ++r) {
+        const uchar* up = src.ptr(std::max(r - 1, 0));
+        const uchar* mid = src.ptr(r);
+        const uchar* down = src.ptr(std::min(r + 1, src.rows - 1));
+        for (int c = 0; c < src.cols; ++c) {
+            const int left = std::max(c - 1, 0), right = std::min(c + 1, src.cols - 1);
+            uchar m = std::min(std::min(up[left], up[c]), up[right]);
+            m = std::min(m, std::min(std::min(mid[left], mid[c]), mid[right]));
+            m = std::min(m, std::min(std::min(down[left], down[c]), down[right]));
+            out.ptr(r)[c] = m;
+        }
+    }
+    dst = out;
+}
 inline void resize(const Mat&, Mat&, Size, double = 0, double = 0, int = INTER_LINEAR) { not_in_stand_in("resize"); }
 inline void rotate(const Mat&, Mat&, int) { not_in_stand_in("rotate"); }
 inline void warpAffine(const Mat&, Mat&, const Mat&, Size, int = INTER_LINEAR, int = BORDER_CONSTANT, const Scalar& = Scalar()) { not_in_stand_in("warpAffine"); }

@@ -902,6 +902,33 @@ int sbo_add_template(const uint8_t* img, int rows, int cols, int stride, int ch,
     return n_levels;
 }
 
+/* The level loop of Detector::addTemplate (:1324-1348) on gradient planes of the caller's: extract_template per level
+ * with num_features halved per level (:427), the stop at the first failing level, crop_templates.  The same statics
+ * as sbo_add_template; for inputs that no image produces (a magnitude plane full of ties). */
+int sbo_add_template_planes(const float* const* magnitude, const uint8_t* const* angle, const float* const* angle_ori,
+                            const uint8_t* const* mask, const int* rows, const int* cols, int n_levels, float strong,
+                            int num_features, sbm_template_level* out_levels, sbo_train_feature* out_feats,
+                            int64_t max_feats)
+{
+    size_t nfeat = (size_t)num_features;
+    int64_t used = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        if (l > 0) nfeat /= 2;
+        int n = extract_template(magnitude[l], angle[l], angle_ori[l], mask ? mask[l] : NULL, rows[l], cols[l], nfeat, strong,
+                                 out_feats + used, max_feats - used);
+        if (n < 0) return -1 - l;
+        out_levels[l].width = -1;
+        out_levels[l].height = -1;
+        out_levels[l].tl_x = out_levels[l].tl_y = 0;
+        out_levels[l].pyramid_level = l;
+        out_levels[l].n_features = n;
+        out_levels[l].feature_offset = used;
+        used += n;
+    }
+    crop_templates(out_levels, out_feats, n_levels);
+    return n_levels;
+}
+
 /* Detector::addTemplate_rotate.  line2Dup.cpp:1395-1451. */
 int sbo_add_template_rotate(const sbm_template_level* in_levels, const sbo_train_feature* in_feats,
                             int n_levels, float theta, float center_x, float center_y,

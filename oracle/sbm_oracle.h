@@ -105,6 +105,12 @@ int sbo_add_template(const uint8_t* img, int rows, int cols, int stride, int ch,
                      const uint8_t* mask, int n_levels, float weak, float strong,
                      int num_features, sbm_template_level* out_levels,
                      sbo_train_feature* out_feats, int64_t max_feats);
+/* addTemplate's level loop on the caller's gradient planes (per level: magnitude, one-hot angle, angle_ori, mask or
+ * mask == NULL for none): returns n_levels, or -1 - l where level l fails. */
+int sbo_add_template_planes(const float* const* magnitude, const uint8_t* const* angle, const float* const* angle_ori,
+                            const uint8_t* const* mask, const int* rows, const int* cols, int n_levels, float strong,
+                            int num_features, sbm_template_level* out_levels, sbo_train_feature* out_feats,
+                            int64_t max_feats);
 /* addTemplate_rotate on a pyramid produced by sbo_add_template. */
 int sbo_add_template_rotate(const sbm_template_level* in_levels, const sbo_train_feature* in_feats,
                             int n_levels, float theta, float center_x, float center_y,

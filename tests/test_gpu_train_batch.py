@@ -1,5 +1,9 @@
 """Batched template training on the device (sbm_train_batch / sbm_train_batch_device) against the oracle's add_template,
-bit for bit: levels, features, theta as bits, None where the oracle fails.  BGR inputs, pyramid {4, 8} (two levels)."""
+bit for bit: levels, features, theta as bits, None where the oracle fails.  First BGR inputs on a two-level pyramid {4, 8}
+with packed rows; then the other configurations a context accepts (one and three levels, gray, padded rows, odd sizes, the
+widths at which the tie resolution's segment length changes) and training on a context that is matching.  Where
+oracle/_ref/ref_train exists (the reference's own training half, tests/test_reference_train_half.py), the new tests hold
+the device output to it as well, without the oracle's training half in between."""
 import numpy as np
 import pytest
 
@@ -241,3 +245,294 @@ def test_argument_errors(ctx_factory):
         assert rc(**kw) == -1, kw
     lv, ft, st = b.run(63)
     assert st[0, 0] == 0
+
+
+# ---- the configurations a context accepts ---------------------------------------------------------------------------------
+T_OF = {1: (4,), 2: (4, 8), 3: (4, 8, 8)}
+# features per level the oracle keeps at num_features 63 on a three-level pyramid; None: the template fails
+RECT_COUNTS = {(48, 200, None): (74, 30, 13), (48, 200, "cut_edge"): (67, 26, 11), (48, 200, "left_half"): (36, 15, 6),
+               (97, 131, None): (66, 26, 8), (97, 131, "cut_edge"): (60, 22, 5), (97, 131, "left_half"): None}
+MASKS = (None, "cut_edge", "left_half")
+
+
+def mask_of(name, rows, cols):
+    return None if name is None else getattr(TC, name)(rows, cols)
+
+
+def reference_result(oracle, img, mask, n_levels, nf, strong):
+    """what the reference's own training half makes of the oracle's gradient planes, or None where this host has no binary"""
+    from oracle import ref_train as RT
+
+    if RT.missing_binaries():
+        return None
+    return RT.run(RT.planes_of(oracle, img, mask, n_levels, TC.WEAK, TC.nearest_mask), nf, strong)
+
+
+def check_image(oracle, got, status, img, mask, n_levels, nf, strong=TC.STRONG, counts=None):
+    """one image of a device batch against the oracle and, where present, the reference binary; returns the oracle's result"""
+    from oracle import ref_train as RT
+
+    want = TC.want(oracle, img, mask, nf, strong, n_levels)
+    failed = oracle.add_template_failing_level(img, mask, n_levels, nf, TC.WEAK, strong)
+    ref = reference_result(oracle, img, mask, n_levels, nf, strong)
+    if isinstance(ref, RT.Failed):
+        assert want is None and failed == ref.level
+        failed = ref.level  # the level the reference names
+    elif ref is not None:
+        assert TC.same_template(got, ref)
+    if want is None:
+        assert got is None and status.tolist() == [1, failed]
+    else:
+        assert status.tolist() == [0, len(want[1])]
+        assert TC.same_template(got, want)
+        if counts is not None:
+            assert TC.counts(want) == counts
+    return want
+
+
+class DeviceTrain:
+    """a batch in device memory with rows of cols * ch + row_pad bytes and images rows * stride + img_pad bytes apart, the
+    padding filled with 0xA5; a mask per image where masks are given (None among them: all set)"""
+
+    def __init__(self, ctx, imgs, masks=None, row_pad=0, img_pad=0, stream=None):
+        import torch
+
+        from shape_based_matching_amd.capi import TRAIN_FEATURE_DTYPE
+        from shape_based_matching_amd.templates import LEVEL_DTYPE
+
+        self.torch, self.ctx, self.L = torch, ctx, ctx.n_levels
+        self.dev = torch.device("cuda", 0)
+        self.n = n = len(imgs)
+        self.rows, self.cols = imgs[0].shape[:2]
+        self.ch = 1 if imgs[0].ndim == 2 else 3
+        assert all(im.shape == imgs[0].shape for im in imgs)
+        self.stride = self.cols * self.ch + row_pad
+        self.img_stride = self.rows * self.stride + img_pad
+        buf = np.full((n, self.img_stride), 0xA5, np.uint8)
+        for i, im in enumerate(imgs):
+            buf[i, : self.rows * self.stride].reshape(self.rows, self.stride)[:, : self.cols * self.ch] = im.reshape(self.rows, self.cols * self.ch)
+        self.d_imgs = torch.from_numpy(buf).to(self.dev)
+        self.d_masks, self.mask_stride = None, 0
+        if masks is not None and any(m is not None for m in masks):
+            self.mask_stride = self.rows * self.cols + 24
+            mbuf = np.full((n, self.mask_stride), 0xA5, np.uint8)
+            for i, m in enumerate(masks):
+                mbuf[i, : self.rows * self.cols] = 255 if m is None else m.reshape(-1)
+            self.d_masks = torch.from_numpy(mbuf).to(self.dev)
+        self.cap = sum(((self.rows >> l) + 2) // 3 * (((self.cols >> l) + 2) // 3) for l in range(self.L))
+        self.lv_dtype, self.ft_dtype = LEVEL_DTYPE, TRAIN_FEATURE_DTYPE
+        self.d_lv = torch.zeros(n * self.L * LEVEL_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self.d_ft = torch.zeros(n * self.cap * TRAIN_FEATURE_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
+        self.d_st = torch.full((n * 2,), -7, dtype=torch.int32, device=self.dev)
+        self.stream = stream or torch.cuda.Stream(device=self.dev)
+        torch.cuda.synchronize()
+
+    def enqueue(self, nf, strong=TC.STRONG):
+        self.ctx.train_batch_device(self.d_imgs.data_ptr(), self.img_stride, self.n, self.rows, self.cols, self.stride, self.ch, strong, nf,
+                                    self.d_lv.data_ptr(), self.d_ft.data_ptr(), self.cap, self.d_st.data_ptr(), stream=self.stream.cuda_stream,
+                                    d_masks=0 if self.d_masks is None else self.d_masks.data_ptr(), mask_stride=self.mask_stride)
+
+    def fetch(self):
+        """(templates, status[n, 2], raw bytes of the three outputs) after the stream has drained"""
+        self.stream.synchronize()
+        lv = self.d_lv.cpu().numpy().view(self.lv_dtype).reshape(self.n, self.L)
+        ft = self.d_ft.cpu().numpy().view(self.ft_dtype).reshape(self.n, self.cap)
+        st = self.d_st.cpu().numpy().reshape(self.n, 2)
+        return unpack(lv, ft, st), st, (lv.tobytes(), ft.tobytes(), st.tobytes())
+
+    def run(self, nf, strong=TC.STRONG):
+        self.enqueue(nf, strong)
+        return self.fetch()
+
+
+def shifted_rectangle(rows, cols):
+    """the rectangle moved down 3 and right 5: a second content of the same geometry"""
+    return np.ascontiguousarray(np.roll(TC.rectangle(rows, cols), (3, 5), axis=(0, 1)))
+
+
+@pytest.mark.parametrize("rows,cols", [(48, 200), (97, 131)])
+@pytest.mark.parametrize("n_levels", [1, 3])
+def test_other_pyramids(ctx_factory, oracle, n_levels, rows, cols):
+    """T = (4,) and (4, 8, 8): the rectangle and a moved copy under no mask, a mask that cuts an edge and the left half, the six
+    images in one call; at three levels 97 x 131 under its left half fails at the last level, next to images that do not"""
+    ctx = ctx_factory(T=T_OF[n_levels])
+    contents = [TC.rectangle(rows, cols), shifted_rectangle(rows, cols)]
+    imgs = [im for im in contents for _ in MASKS]
+    masks = [mask_of(m, rows, cols) for _ in contents for m in MASKS]
+    got, st, _ = DeviceTrain(ctx, imgs, masks).run(63)
+    for i, (im, m) in enumerate(zip(imgs, masks)):
+        cnt = RECT_COUNTS[(rows, cols, MASKS[i])] if i < 3 else None
+        want = check_image(oracle, got[i], st[i], im, m, n_levels, 63, counts=None if cnt is None else cnt[:n_levels])
+        if i < 3 and n_levels == 3:
+            assert (want is None) == (cnt is None)
+    if n_levels == 3 and (rows, cols) == (97, 131):
+        assert st[2].tolist() == [1, 2]
+    check(ctx.train_batch(imgs, masks, TC.STRONG, 63), [TC.want(oracle, im, m, 63, TC.STRONG, n_levels) for im, m in zip(imgs, masks)])
+
+
+@pytest.mark.parametrize("n_levels", [1, 2, 3])
+def test_gray(ctx_factory, oracle, n_levels):
+    """single-channel images (the green channel of the rectangles) at one, two and three levels"""
+    ctx = ctx_factory(T=T_OF[n_levels])
+    for rows, cols in ((48, 200), (97, 131)):
+        imgs = [TC.gray(TC.rectangle(rows, cols))] * 3
+        masks = [mask_of(m, rows, cols) for m in MASKS]
+        assert imgs[0].ndim == 2
+        got, st, _ = DeviceTrain(ctx, imgs, masks).run(63)
+        wants = [check_image(oracle, got[i], st[i], imgs[i], masks[i], n_levels, 63) for i in range(3)]
+        assert any(w is not None for w in wants)
+        check(ctx.train_batch(imgs, masks, TC.STRONG, 63), wants)
+
+
+def test_gray_noise(ctx_factory, oracle):
+    """gray noise of odd size at strong_threshold 10, one level: 66 features kept of 63 asked, 205 candidates in all"""
+    ctx = ctx_factory(T=(4,))
+    img = TC.gray(TC.noise(131, 97, 7))
+    b = DeviceTrain(ctx, [img])
+    for nf, n in ((63, 66), (100000, 205)):
+        got, st, _ = b.run(nf, 10.0)
+        check_image(oracle, got[0], st[0], img, None, 1, nf, 10.0, counts=(n,))
+    check(ctx.train_batch([img], None, 10.0, 63), [TC.want(oracle, img, None, 63, 10.0, 1)])
+
+
+@pytest.mark.parametrize("gray", [False, True])
+def test_padded_rows(ctx_factory, oracle, gray):
+    """rows of cols * ch + 13 bytes and images further apart than rows * stride, the padding filled with 0xA5: the packed call's
+    output, byte for byte"""
+    ctx = ctx_factory()
+    imgs = [TC.rectangle(50, 70), TC.noise(50, 70, 2), shifted_rectangle(50, 70)]
+    if gray:
+        imgs = [TC.gray(im) for im in imgs]
+    masks = [TC.cut_edge(50, 70), None, TC.left_half(50, 70)]
+    for strong in (TC.STRONG, 10.0):
+        packed = DeviceTrain(ctx, imgs, masks).run(63, strong)
+        padded = DeviceTrain(ctx, imgs, masks, row_pad=13, img_pad=1000)
+        assert padded.stride == 70 * (1 if gray else 3) + 13 and padded.img_stride > 50 * padded.stride
+        got, st, raw = padded.run(63, strong)
+        assert raw == packed[2]
+        wants = [check_image(oracle, got[i], st[i], imgs[i], masks[i], 2, 63, strong) for i in range(3)]
+        assert any(w is not None for w in wants)
+
+
+@pytest.mark.parametrize("rows,cols,n_levels", [(51, 71, 2), (97, 131, 3)])
+def test_odd_sizes_with_masks(ctx_factory, oracle, rows, cols, n_levels):
+    """odd rows and columns at every level but the last, a mask per image: the nearest-neighbour mask chain from odd sources"""
+    ctx = ctx_factory(T=T_OF[n_levels])
+    rs = np.random.RandomState(rows)
+    imgs = [TC.rectangle(rows, cols), shifted_rectangle(rows, cols), TC.rectangle(rows, cols), TC.rectangle(rows, cols)]
+    masks = [(rs.rand(rows, cols) > 0.05).astype(np.uint8) * 255, (rs.rand(rows, cols) > 0.03).astype(np.uint8) * 255, TC.cut_edge(rows, cols), None]
+    got, st, _ = DeviceTrain(ctx, imgs, masks).run(63)
+    wants = [check_image(oracle, got[i], st[i], imgs[i], masks[i], n_levels, 63) for i in range(4)]
+    assert wants[3] is not None and sum(w is not None for w in wants) >= 3
+    assert not TC.same_template(wants[0], wants[3])  # the random mask matters
+    check(ctx.train_batch(imgs, masks, TC.STRONG, 63), wants)
+
+
+@pytest.mark.parametrize("cols", sorted(TC.SEGMENT_SEEDS))
+def test_resolve_segment_boundaries(ctx_factory, oracle, cols):
+    """64, 65, 128 and 129 columns: one, two (with idle lanes), two and three columns per lane of the tie resolution; a
+    rectangle, and noise whose candidates reach the last three scanned columns"""
+    ctx = ctx_factory(T=(4,))
+    rows = TC.SEGMENT_ROWS
+    rect, noise = TC.rectangle(rows, cols), TC.noise(rows, cols, TC.SEGMENT_SEEDS[cols])
+    assert TC.candidates_in_last_columns(oracle, noise, 10.0) >= 1
+    b = DeviceTrain(ctx, [rect, noise])
+    for nf in (16, 100000):
+        got, st, _ = b.run(nf, 10.0)
+        wants = [check_image(oracle, got[i], st[i], im, None, 1, nf, 10.0) for i, im in enumerate((rect, noise))]
+        assert all(w is not None for w in wants)
+    got, st, _ = b.run(63)
+    assert check_image(oracle, got[0], st[0], rect, None, 1, 63) is not None
+    check_image(oracle, got[1], st[1], noise, None, 1, 63)
+
+
+# ---- training on a context that is matching ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def match_world(oracle):
+    """three 512 x 640 frames (those of test_gpu_sparse_strips.py), their oracle match lists and the first frame's pyramid"""
+    import test_gpu_sparse_strips as S
+    from shape_based_matching_amd import synth
+
+    ts = S.load_templates()
+    centre = S.make_frames(None)
+    frames = [centre, S.shifted(centre, 0, -16), synth.scene_bgr(5, S.ROWS, S.COLS)]
+    want, p0 = [], None
+    for i, f in enumerate(frames):
+        p = oracle.Pyramid.build(f, [4, 8], 30.0)
+        want.append(S.multiset(p.match(ts.levels, ts.features, ts.class_idx, ts.template_id, S.THR, n_threads=S.NT)))
+        if i == 0:
+            p0 = p
+        else:
+            p.free()
+    assert len(want[0]) > 20 and len(want[1]) > 20
+    yield {"S": S, "ts": ts, "frames": frames, "want": want, "p0": p0}
+    p0.free()
+
+
+TRAIN_KERNELS = ["k_train_maxima", "k_train_resolve", "k_train_sort", "k_train_select", "k_train_crop"]
+
+
+@pytest.mark.parametrize("mode", ["plain", "graph", "profiling"])
+def test_training_on_a_context_in_use(ctx_factory, oracle, match_world, mode):
+    """one {4, 8} context, one caller stream, no host synchronisation between the calls: a batched match of three frames, a
+    training batch, the template loop on the resident pyramid, then the first level's linear memories.  Every match list,
+    the planes and the templates are the oracle's; a training call adds no graph; its timings name its five kernels once."""
+    import torch
+
+    from shape_based_matching_amd.templates import MATCH_DTYPE
+
+    S, w = match_world["S"], match_world
+    ctx = ctx_factory()
+    ctx.upload_templates(w["ts"])
+    if mode == "graph":
+        ctx.set_pipeline_depth(2)
+        ctx.set_graph_mode(True)
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream(device=dev)
+    B, CAP, REC = 3, S.CAP, MATCH_DTYPE.itemsize
+    d_img = torch.from_numpy(np.stack(w["frames"])).to(dev)
+    d_out = torch.zeros(B * CAP * REC, dtype=torch.uint8, device=dev)
+    d_cnt = torch.full((B * 2,), -1, dtype=torch.int32, device=dev)
+    d_one = torch.zeros(CAP * REC, dtype=torch.uint8, device=dev)
+    d_one_cnt = torch.full((2,), -1, dtype=torch.int32, device=dev)
+    imgs = [TC.rectangle(96, 96)] * 3 + [np.ascontiguousarray(TC.rectangle(96, 96)[:, ::-1])]
+    masks = [None, TC.left_half(96, 96), TC.cut_edge(96, 96), TC.cut_edge(96, 96)]
+    train = DeviceTrain(ctx, imgs, masks, stream=st)
+    wants = [TC.want(oracle, im, m, 63) for im, m in zip(imgs, masks)]
+    assert all(x is not None for x in wants)
+    torch.cuda.synchronize()
+    if mode == "profiling":
+        ctx.set_profiling(True)
+    rounds = 2  # the first round grows the training scratch and, in graph mode, captures; the second is the steady state
+    for rnd in range(rounds):
+        d_out.zero_(), d_cnt.fill_(-1), d_one.zero_(), d_one_cnt.fill_(-1), train.d_st.fill_(-7), train.d_ft.zero_(), train.d_lv.zero_()
+        torch.cuda.synchronize()
+        for _ in range(2 if mode == "graph" else 1):
+            ctx.match_batch_device(d_img.data_ptr(), w["frames"][0].size, B, S.ROWS, S.COLS, S.COLS * 3, 3, S.THR, d_out.data_ptr(), CAP,
+                                   d_cnt.data_ptr(), stream=st.cuda_stream)
+        graphs = ctx.graph_count()
+        train.enqueue(63)
+        assert ctx.graph_count() == graphs
+        if mode == "graph":  # the batched match replays its capture; later rounds also hold the template loop's
+            assert graphs >= 1
+        if mode == "profiling":  # reading a call's timings waits for its kernels: the one host wait of this mode
+            names = [n for n, _ in ctx.timings()]
+            assert [n for n in names if n.startswith("k_train_")] == TRAIN_KERNELS, names
+        ctx.match_templates_device(S.THR, d_one.data_ptr(), CAP, d_one_cnt.data_ptr(), stream=st.cuda_stream)
+        lm0 = ctx.get_linear_memories(0)
+        got, status, _ = train.fetch()
+        cnt = d_cnt.cpu().numpy().reshape(B, 2)
+        recs = d_out.cpu().numpy().view(MATCH_DTYPE).reshape(B, CAP)
+        assert (cnt[:, 1] == 0).all() and (cnt[:, 0] >= 0).all() and (cnt[:, 0] <= CAP).all(), cnt
+        for b in range(B):
+            assert S.multiset(recs[b, : cnt[b, 0]]) == w["want"][b], (rnd, b)
+        one = d_one_cnt.cpu().numpy()
+        assert one[1] == 0 and S.multiset(d_one.cpu().numpy().view(MATCH_DTYPE)[: max(int(one[0]), 0)]) == w["want"][0], rnd
+        n0 = S.ROWS * S.COLS
+        assert np.array_equal(lm0[:, :n0], w["p0"].lm(0)[:, :n0]), rnd
+        for i in range(len(imgs)):
+            assert status[i].tolist() == [0, len(wants[i][1])], (rnd, i)
+        check(got, wants)
+    ref = [reference_result(oracle, im, m, 2, 63, TC.STRONG) for im, m in zip(imgs, masks)]
+    if ref[0] is not None:
+        check(got, ref)

@@ -148,6 +148,22 @@ def test_resize_nearest_index_rule(oracle, sw):
     assert np.array_equal(oracle_resize_nearest(oracle, m, 1, dw), S.resize_nearest(m, 1, dw))
 
 
+@pytest.mark.parametrize("rows,cols", [(51, 71), (97, 131), (33, 47)])
+def test_mask_pyramid_on_odd_sizes(oracle, rows, cols):
+    """three levels of the mask pyramid from an odd-sized mask, every level from the one before: the oracle's nearest
+    resize, the spec's and train_batch_cases.nearest_mask (which the training tests feed the reference binary) agree"""
+    import train_batch_cases as TC
+
+    m = (np.random.RandomState(rows * cols).randint(0, 10, (rows, cols)) > 0).astype(np.uint8) * 255
+    for _ in range(3):
+        dr, dc = m.shape[0] // 2, m.shape[1] // 2
+        want = S.resize_nearest(m, dr, dc)
+        assert 0 < np.count_nonzero(want) < want.size
+        assert np.array_equal(oracle_resize_nearest(oracle, m, dr, dc), want)
+        assert np.array_equal(TC.nearest_mask(m), want)
+        m = want
+
+
 def test_resize_nearest_index_rule_all_widths():
     """min(floor(x * (1 / (dw / sw))), sw - 1) == floor(x * sw / dw) for every sw <= 8192 at dw = sw / 2: the spec may
     use either form"""

@@ -20,6 +20,11 @@ With --ref, only:
                                 list and match()'s epilogue list at three thresholds, and the SHA-256 of one level's
                                 linear memories.  The maps (from the oracle's gradient stage) and the template subset
                                 are stored with it, so the GPU suite can hold the HIP kernels to it without the binary.
+With --ref-train, only:
+  ref_train_cases.npz        <- what the reference's own training half (oracle/_ref/ref_train, built by
+                                oracle/ref_train.mk) makes of the 96 x 96 rectangle of tests/train_batch_cases.py under its
+                                four masks and of the 64 x 64 rectangle under its left half (which fails), two levels, 63
+                                features: per case the level records, the features (theta as bits) and the failing level.
 No reference source text is copied.
 """
 import gzip
@@ -108,8 +113,24 @@ def ref_match_fixture():
     np.savez_compressed(f"{OUT}/ref_match_case1.npz", **out)
 
 
+def ref_train_fixture():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import train_batch_cases as TC
+    from oracle import oracle as O
+    from oracle import ref_train as RT
+
+    out = {}
+    for name, (img, mask) in TC.recorded_cases().items():
+        got = RT.run(RT.planes_of(O, img, mask, TC.N_LEVELS, TC.WEAK, TC.nearest_mask), 63, TC.STRONG)
+        out.update(TC.pack_recorded(name, got, RT))
+        print(f"ref_train_cases: {name}: {got if isinstance(got, RT.Failed) else TC.counts(got)}")
+    np.savez_compressed(f"{OUT}/ref_train_cases.npz", **out)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["--ref"]:
         ref_match_fixture()
+    elif sys.argv[1:] == ["--ref-train"]:
+        ref_train_fixture()
     else:
         main()
