@@ -99,11 +99,16 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //                             sbm_set_refine_bits overrides per context)
 //   SBM_SPARSE_STRIPS=0       match entry points build level 0's bit strips whole, inside the one linear-memory launch, instead of
 //                             only in the tiles the coarse candidates' refinement reads (sbm_refine_tiles.h)
+//   SBM_SPARSE_GRADIENT=0     match entry points run level 0's whole gradient stage in front of the coarse pass instead of the source
+//                             pass there (cv::pyrDown + retained copy) and the gradient of the flagged tiles' reach behind it
+//                             (sbm_quantize_stream.h, QS_SOURCE / QS_SPARSE); SBM_SPARSE_STRIPS=0 implies it
+//   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
 struct Tuning {
     int coarse = 0, quantize = 0, hs0 = 0, hs1 = 0, local_grid = 0, local_waves = 0, local_order = -1;
     bool qs_pack = true, full_lm = false, strip_lm = true, graph_fork = true, fused_bits = true, lm_allty = true;
     int bits_wide = -1, bits_dw = 0, bits_block = -1, match_bands = 0, local_bits = -1;
-    bool sparse_strips = true;
+    bool sparse_strips = true, sparse_gradient = true;
+    int src_hs = 0;
 };
 static const Tuning& tuning()
 {
@@ -133,6 +138,8 @@ static const Tuning& tuning()
         k.bits_block = num("SBM_BITS_BLOCK", -1);
         k.local_bits = num("SBM_LOCAL_BITS", -1);
         k.sparse_strips = num("SBM_SPARSE_STRIPS", 1) != 0;
+        k.sparse_gradient = k.sparse_strips && num("SBM_SPARSE_GRADIENT", 1) != 0;
+        k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
         k.bits_dw = num("SBM_BITS_DW", 0) == 2 ? 2 : (num("SBM_BITS_DW", 0) == 1 ? 1 : 0);
         return k;
@@ -186,6 +193,13 @@ struct sbm_ctx {
     // ... and, as level 0 of a two-level pyramid, only in the tiles the call's coarse candidates read (LM_BIT_STRIPS_SPARSE):
     // one byte flag per frame and tile (sbm_refine_tiles.h), cleared with the counters, set by k_mark_refine_tiles
     DevBuf d_tiles;
+    // ... and level 0's orientation map itself only where those tiles' strip builders read it (BuildPlan::sparse_gradient): the
+    // source pass keeps the batch's level-0 source bytes here (batch x rows x cols x channels, packed), the gradient launch
+    // behind the coarse pass reads them, and so does the whole launch that a later reader of d_quant[0] asks for
+    // (ensure_level0_map) -- the caller's image may be gone by then.  map0_whole: d_quant[0] holds every frame's whole map.
+    DevBuf d_src0;
+    int src0_ch = 0;
+    bool map0_whole = true;
     // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
     // (sbm_level_forms.h; per level, not per frame: the forms rebuilt on demand cover frame 0 only)
     LevelForms forms[SBM_MAX_LEVELS];
@@ -257,6 +271,7 @@ struct sbm_ctx {
         hipGraph_t graph;
         hipGraphExec_t exec;
         uint64_t last_use;
+        bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
@@ -420,6 +435,9 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             c->d_tiles.release(); // sized by level 0's grid and the batch
             if (c->d_lbits[0].p)
                 if (int e = c->d_tiles.ensure(B * (size_t)refine_tile_count(cc / c->cfg.T[0], r / c->cfg.T[0]), true)) return e;
+            c->d_src0.release();
+            if (c->d_tiles.p && c->L == 2 && tuning().sparse_gradient)
+                if (int e = c->d_src0.ensure(B * r * cc * channels)) return e;
         }
         c->forms[l].forget();
     }
@@ -435,6 +453,7 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
     c->channels = channels;
     c->foff_dirty = true;
     c->levels_valid = 0;
+    c->map0_whole = true; // nothing resident: nothing to complete
     c->drop_graphs(); // captured launches hold the old buffer addresses
     return 0;
 }
@@ -452,7 +471,11 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
     if (int e = c->d_lm[l].ensure((size_t)8 * c->lm_stride[l], true)) return e;
     c->d_lmc[l].release();
     c->d_lbits[l].release();
-    if (l == 0) c->d_tiles.release();
+    if (l == 0) {
+        c->d_tiles.release();
+        c->d_src0.release();
+        c->map0_whole = true; // the caller sets the whole map
+    }
     c->forms[l].forget();
     if (l == c->L - 1) {
         c->d_blm.release();
@@ -549,9 +572,23 @@ int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frame
     return hs;
 }
 
+// A reduced form of the streaming kernel's row loop (QSStage): the source pass with its retained copy, or the gradient of
+// the flagged tiles' reach.  Whole levels only, no mask; the caller has checked that the launch takes the streaming kernel.
+struct QSForm {
+    int stage;
+    uint8_t* keep;
+    int64_t keep_fs;
+    const uint8_t* tile_flags;
+    int n_tiles, T, W, H;
+};
+
+// rows per work item of the source pass: its items run hs + 3 row iterations, in whole groups of 6
+int source_pass_rows() { return tuning().src_hs > 0 ? (tuning().src_hs + 1) & ~1 : 32; }
+
 int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, int cols, int stride, int ch,
                     const uint8_t* d_mask, float weak, uint8_t* d_out, float* d_mag, float* d_ori, uint8_t* d_pyr,
-                    int frames = 1, int64_t img_fs = 0, int row_lo = 0, int row_hi = -1, bool tile_band = false, int64_t mask_fs = 0)
+                    int frames = 1, int64_t img_fs = 0, int row_lo = 0, int row_hi = -1, bool tile_band = false, int64_t mask_fs = 0,
+                    const QSForm* form = nullptr)
 {
     if (!d_mask) mask_fs = 0; // mask_fs: bytes between the frames' masks, 0 = one mask for all frames
     if (row_hi < 0) row_hi = rows;
@@ -563,7 +600,10 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     const float thr_sq = weak * weak;
     const bool wf = d_mag || d_ori;
     const int64_t out_fs = (int64_t)rows * cols, pyr_fs = (int64_t)(rows / 2) * (cols / 2) * ch; // the context's own per-frame buffers
-    if (const int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0, mask_fs)) {
+    int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0, mask_fs);
+    if (form && (!hs || band || d_mask)) return fail(SBM_ERR_STATE, "a reduced gradient form needs a whole, unmasked launch of the streaming kernel");
+    if (form && form->stage == QS_SOURCE) hs = source_pass_rows();
+    if (hs) {
         QSArgs a;
         memset(&a, 0, sizeof a);
         a.img = d_img;
@@ -586,9 +626,29 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.frames = frames;
         a.pack_lanes = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride, mask_fs);
         a.pack_groups = a.pack_lanes ? (frames + 64 / a.pack_lanes - 1) / (64 / a.pack_lanes) : 0;
+        const int stage = form ? form->stage : (int)QS_WHOLE;
+        if (stage == QS_SOURCE) {
+            a.keep = form->keep;
+            a.keep_fs = form->keep_fs;
+        } else if (stage == QS_SPARSE) {
+            a.pyr = nullptr;
+            a.tile_flags = form->tile_flags;
+            a.n_tiles = form->n_tiles;
+            a.grid_t = form->T;
+            a.grid_w = form->W;
+            a.grid_h = form->H;
+        }
         const dim3 g((unsigned)((quantize_stream_items(a) + 3) / 4));
-        if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<1>), g, dim3(256), 0, s, a);
-        else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<3>), g, dim3(256), 0, s, a);
+        // (one timing name for all three forms: the launches of the gradient stage)
+#define SBM_QS(CH_)                                                                                                         \
+        do {                                                                                                                \
+            if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SOURCE>), g, dim3(256), 0, s, a); \
+            else if (stage == QS_SPARSE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SPARSE>), g, dim3(256), 0, s, a); \
+            else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                     \
+        } while (0)
+        if (ch == 1) SBM_QS(1);
+        else SBM_QS(3);
+#undef SBM_QS
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -717,11 +777,14 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
 
 // 8-plane linear memories of level l (frame 0) for the stage entry points: expanded from the spread plane, or -- a level held
 // as bit strips or bit planes only -- from the orientation map, which is still resident
+int ensure_level0_map(sbm_ctx* c, hipStream_t s);
 int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
 {
     const LmForm src = full_lm_source(c->forms[l]);
     // nothing current: the level's strips were built sparsely (or nothing was built yet: not resident, nothing to do)
     if (src == LM_PLANES8 || (src == LM_NONE && l >= c->levels_valid)) return 0;
+    if (l == 0 && src != LM_SPREAD && src != LM_SPREAD_STRIP) // built from the map, which a sparse call left in pieces
+        if (int e = ensure_level0_map(c, s)) return e;
     if (src == LM_SPREAD || src == LM_SPREAD_STRIP) {
         const int T = c->cfg.T[l];
         const int64_t n = (int64_t)T * T * (c->cols[l] / T) * (c->rows[l] / T);
@@ -866,6 +929,28 @@ int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const u
                            nullptr, l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames, img_fs, row_lo, row_hi, false, mask_fs);
 }
 
+// What one call adds to the plan's inputs for a sparse level-0 gradient (PlanInputs::sparse_gradient ...): the knob and the
+// retained buffer, whether both launches -- the source pass on the caller's frames, the later ones on the retained copy --
+// take the streaming kernel, the mask, the bands (a one-band exchange reads the map too; level 0 launched already counts)
+PlanInputs call_plan_inputs(const sbm_ctx* c, const uint8_t* mask, int stride0, int frames, int64_t img0_fs, const Bands* bands, bool level0_done)
+{
+    PlanInputs pin = plan_inputs(c);
+    const int rows = c->rows[0], cols = c->cols[0], ch = c->channels;
+    const int64_t fs = (int64_t)rows * cols * ch;
+    pin.sparse_gradient = tuning().sparse_gradient && c->d_src0.p && fs < (int64_t)0x7ff00000 && (size_t)frames * (size_t)fs <= c->d_src0.cap;
+    pin.l0_stream = pin.sparse_gradient && quantize_stream_rows(c, rows, cols, ch, frames, false, img0_fs, stride0) != 0 &&
+                    quantize_stream_rows(c, rows, cols, ch, frames, false, fs, cols * ch) != 0;
+    pin.l0_mask = mask != nullptr;
+    pin.banded = bands != nullptr || level0_done;
+    return pin;
+}
+
+// ... the plan of a match entry point then makes level 0's map sparsely
+bool plans_sparse_gradient(const sbm_ctx* c, const uint8_t* mask, int stride0, int frames, int64_t img0_fs, const Bands* bands, bool level0_done)
+{
+    return plan_build(call_plan_inputs(c, mask, stride0, frames, img0_fs, bands, level0_done), all_rows_ok(c), true).sparse_gradient;
+}
+
 int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0,
                     int32_t* reset_count = nullptr, int frames = 1, int64_t img0_fs = 0, const Bands* bands = nullptr,
                     bool level0_gradient_done = false, int64_t mask0_fs = 0)
@@ -880,7 +965,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
     // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch, and its T = 4 strip levels as bit strips.
     // The stage entry points keep the 8 response planes there (the bit planes are then packed from them on demand).
-    const BuildPlan plan = plan_build(plan_inputs(c), all_rows, reset_count != nullptr);
+    const BuildPlan plan = plan_build(call_plan_inputs(c, d_mask0, stride0, frames, img0_fs, bands, level0_gradient_done), all_rows, reset_count != nullptr);
     // (the linear memories of a level right behind its gradient launch -- two launches per batch, the orientation map still
     // in the caches -- measure the same as one launch for all levels at the end: tools/r03_lm_early.sh)
     for (int l = 0; l < c->L; ++l) {
@@ -893,6 +978,14 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
                 hi = std::min(c->rows[l], (bands->first + b + 1) * br + e);
             }
             const int64_t img_fs = l == 0 ? img0_fs : (int64_t)c->rows[l] * c->cols[l] * c->channels;
+            if (l == 0 && plan.sparse_gradient) {
+                // the source pass: level 1's image and the retained copy; the map waits for the coarse candidates (enqueue_sparse_strips)
+                const QSForm form{QS_SOURCE, c->d_src0.as<uint8_t>(), (int64_t)c->rows[0] * c->cols[0] * c->channels, nullptr, 0, 0, 0, 0};
+                if (int e = launch_quantize(c, s, img, c->rows[0], c->cols[0], stride, c->channels, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(),
+                                            nullptr, nullptr, c->d_img[1].as<uint8_t>(), frames, img_fs, 0, c->rows[0], false, 0, &form))
+                    return e;
+                continue;
+            }
             if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, mask_fs, frames, img_fs, lo, hi)) return e;
         }
         if (!all_rows && frames > 1) return fail(SBM_ERR_INVALID, "batched match needs T in {4, 8} and 16-column-aligned levels");
@@ -936,6 +1029,22 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     }
     record_build(c->forms, c->L, plan);
     c->levels_valid = c->L;
+    c->map0_whole = !plan.sparse_gradient;
+    if (plan.sparse_gradient) c->src0_ch = c->channels;
+    return 0;
+}
+
+// d_quant[0] whole in every frame of the last batch, for a reader other than the sparse call's own strip builder: the ordinary
+// gradient launch on the retained source.  On the reader's stream, outside any capture.
+int ensure_level0_map(sbm_ctx* c, hipStream_t s)
+{
+    if (c->map0_whole || c->levels_valid < 1) return 0;
+    const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
+    if (!c->d_src0.p || (size_t)c->last_frames * rows * cols * ch > c->d_src0.cap) return fail(SBM_ERR_STATE, "level 0's source is not retained");
+    if (int e = launch_quantize(c, s, c->d_src0.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(), nullptr,
+                                nullptr, nullptr, c->last_frames, (int64_t)rows * cols * ch))
+        return e;
+    c->map0_whole = true;
     return 0;
 }
 
@@ -1287,6 +1396,15 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
                (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles);
     HIP_TRY(hipGetLastError());
+    if (!c->map0_whole) {
+        // the call ran the source pass only (BuildPlan::sparse_gradient): level 0's gradient stage now, from the retained
+        // source, in the work items whose output the flagged tiles' builders load.  The map stays in pieces (map0_whole).
+        const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
+        const QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
+        if (int e = launch_quantize(c, s, c->d_src0.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(),
+                                    nullptr, nullptr, nullptr, frames, (int64_t)rows * cols * ch, 0, rows, false, 0, &form))
+            return e;
+    }
     LmArgs a;
     memset(&a, 0, sizeof a);
     a.n_levels = 1;
@@ -1317,6 +1435,7 @@ int enqueue_loop(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, i
 int ensure_local_forms(sbm_ctx* c, hipStream_t s)
 {
     const PlanInputs pin = plan_inputs(c);
+    if (int e = ensure_level0_map(c, s)) return e; // every rebuild below reads the orientation maps
     for (int l = 0; l < c->L - 1; ++l) {
         LevelForms& f = c->forms[l];
         if (refine_reads(f) == LM_NONE) {
@@ -1373,7 +1492,7 @@ bool graph_key_equal(const sbm_ctx::GraphEntry& g, const sbm_ctx::GraphEntry& k)
 {
     return g.img == k.img && g.rows == k.rows && g.cols == k.cols && g.stride == k.stride && g.ch == k.ch && g.mask == k.mask &&
            g.thr_bits == k.thr_bits && g.out == k.out && g.cap == k.cap && g.count == k.count && g.mo == k.mo && g.mc == k.mc &&
-           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride;
+           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride && g.sparse_grad == k.sparse_grad;
 }
 
 constexpr size_t GRAPH_CACHE = 16;
@@ -1445,10 +1564,13 @@ int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
 }
 
 // what a match entry point leaves resident, for the calls that replay its launches as a captured graph
-void record_match(sbm_ctx* c, bool one_launch)
+// sparse_grad: the captured call made level 0's map sparsely (its graph key says so)
+void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad)
 {
     record_match(c->forms, plan_inputs(c), one_launch, c->h_active.empty());
     c->levels_valid = c->L;
+    c->map0_whole = !sparse_grad;
+    if (sparse_grad) c->src0_ch = c->channels;
 }
 
 // every launch of a match call, in order
@@ -1481,6 +1603,7 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
         if (int e = launch_build_lm(c, fork ? sd : st, l)) return e;
     }
     record_build(c->forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
+    c->map0_whole = true;
     if (int e = enqueue_coarse(c, st, m.out, m.cap, m.counts)) return e;
     if (forked && (hipEventRecord(c->ev_join, sd) != hipSuccess || hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess))
         return fail(SBM_ERR_HIP, "graph join failed");
@@ -1493,8 +1616,10 @@ sbm_ctx::GraphEntry graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     uint32_t thr_bits;
     memcpy(&thr_bits, &m.thr, 4);
     // (the template loop has no frame stride: what its launches depend on instead is the form every level is held in)
+    // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
+    const bool sparse_grad = kind > 0 && plans_sparse_gradient(c, m.mask, m.stride, m.frames, m.frame_stride, nullptr, false);
     return sbm_ctx::GraphEntry{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
-                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0};
+                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0, sparse_grad};
 }
 
 // The launches of a match call on stream s: a replay of the graph captured for its argument tuple where one is wanted --
@@ -1514,7 +1639,8 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             if (int e = ensure_local_forms(c, s)) return e;
         }
         bool launched = false;
-        if (int e = graph_replay(c, graph_key(c, m, kind), s, &launched, [&](hipGraph_t* g) {
+        const sbm_ctx::GraphEntry key = graph_key(c, m, kind);
+        if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
                 hipStream_t st = c->stream;
                 HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
                 const int rc = kind == 0  ? enqueue_match_forked(c, m)
@@ -1527,7 +1653,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is captured only
             // where the one-launch builder takes every level; the template loop builds nothing
             if (kind >= 0) {
-                record_match(c, kind > 0);
+                record_match(c, kind > 0, key.sparse_grad);
                 c->last_frames = m.frames;
             }
             return 0;

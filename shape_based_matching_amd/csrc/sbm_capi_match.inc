@@ -740,6 +740,9 @@ int sbm_set_quantized(sbm_ctx* c, int32_t level, const uint8_t* q, int32_t rows,
     if (int e = order_after_caller_work(c)) return e;
     if (int e = ensure_level(c, level, rows, cols)) return e;
     if (c->profiling && !c->profiling_keep && level == 0) c->clear_timings();
+    // (a sparse call's other frames stay readable: their maps are completed before frame 0's is replaced)
+    if (level == 0)
+        if (int e = ensure_level0_map(c, c->stream)) return e;
     HIP_TRY(hipMemcpyAsync(c->d_quant[level].p, q, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
     if (int e = launch_build_lm(c, c->stream, level)) return e;
     c->forms[level].set(LM_PLANES8);
@@ -754,6 +757,8 @@ int sbm_get_quantized(sbm_ctx* c, int32_t level, uint8_t* out)
     if (!c || !out || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = order_after_caller_work(c)) return e;
+    if (level == 0)
+        if (int e = ensure_level0_map(c, c->stream)) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(out, c->d_quant[level].p, (size_t)c->rows[level] * c->cols[level], hipMemcpyDeviceToHost));
     return 0;
@@ -766,6 +771,10 @@ int sbm_get_quantized_frame(sbm_ctx* c, int32_t level, int32_t frame, uint8_t* o
     if (frame < 0 || frame >= c->last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->last_frames);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     HIP_TRY(hipDeviceSynchronize()); // the batch may have been built on the caller's stream
+    if (level == 0) { // a sparse call left the map in pieces: the whole launch on the retained source, once
+        if (int e = ensure_level0_map(c, c->stream)) return e;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     const size_t n = (size_t)c->rows[level] * c->cols[level];
     HIP_TRY(hipMemcpy(out, c->d_quant[level].as<uint8_t>() + (size_t)frame * n, n, hipMemcpyDeviceToHost));
     return 0;

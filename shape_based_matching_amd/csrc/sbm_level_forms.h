@@ -89,6 +89,12 @@ struct PlanInputs {
     bool full_lm = false, strip_lm = true, lm_allty = true, fused_bits = true; // SBM_FULL_LM, SBM_STRIP_LM, SBM_LM_ALLTY, SBM_FUSED_BITS
     int local_bits = -1;                                                       // SBM_LOCAL_BITS
     bool sparse_strips = false; // level 0 of a two-level pyramid as LM_BIT_STRIPS_SPARSE (off here; on in a context unless SBM_SPARSE_STRIPS=0)
+    // Level 0's gradient stage only where the flagged tiles' strip builders read its map (sbm_quantize_stream.h, QS_SOURCE and
+    // QS_SPARSE): the knob (off here; on in a context that holds the retained source buffer unless SBM_SPARSE_GRADIENT=0 or
+    // SBM_SPARSE_STRIPS=0), and what the caller says of ONE call: its level-0 launches take the streaming kernel, it brings a
+    // mask (a level-0 mask is the caller's memory too, gone when a later reader asks for the whole map), it is banded
+    bool sparse_gradient = false;
+    bool l0_stream = false, l0_mask = false, banded = false;
     int W(int l) const { return cols[l] / T[l]; }
     int H(int l) const { return rows[l] / T[l]; }
 };
@@ -118,11 +124,15 @@ inline bool local_bits_wanted(const PlanInputs& p, int l)
 struct BuildPlan {
     LmForm form[LF_MAX_LEVELS];
     bool pack_spread; // the coarsest level is LM_SPREAD and k_pack_bitplanes_spread makes the bit planes from it
+    // level 0's orientation map is made between the coarse pass and the refinement, in the flagged tiles' reach only: the call
+    // leaves the map whole in no frame (the context's "level 0's map is whole" flag goes down; ensure_level0_map)
+    bool sparse_gradient;
 };
 inline BuildPlan plan_build(const PlanInputs& p, bool one_launch, bool match_entry)
 {
     BuildPlan b;
     b.pack_spread = false;
+    b.sparse_gradient = false;
     for (int l = 0; l < LF_MAX_LEVELS; ++l) b.form[l] = l < p.L ? LM_PLANES8 : LM_NONE;
     if (!one_launch) return b;
     // refinement-only levels: ONE plane of spread bytes, strip-interleaved when the grid width allows it (the refinement
@@ -135,6 +145,7 @@ inline BuildPlan plan_build(const PlanInputs& p, bool one_launch, bool match_ent
     // Two levels: the coarse candidates are the refinement's, so level 0's strips wait for them.  (Deeper pyramids keep the
     // whole build: refinement at an intermediate level moves the candidates before level 0 is read.)
     if (p.sparse_strips && p.L == 2 && b.form[0] == LM_BIT_STRIPS) b.form[0] = LM_BIT_STRIPS_SPARSE;
+    b.sparse_gradient = p.sparse_gradient && match_entry && b.form[0] == LM_BIT_STRIPS_SPARSE && p.l0_stream && !p.l0_mask && !p.banded;
     // the coarsest level of a coarse pass on bit planes: those only, inside the launch (a wave's 256 positions must not
     // straddle two sub-planes), else the spread plane and a pack launch; without either, the 8 planes (packed on demand)
     const int lc = p.L - 1;

@@ -45,6 +45,20 @@
 #define SBM_WAVE_HEADER "sbm_wave_gfx950.h"
 #endif
 #include SBM_WAVE_HEADER
+#include "sbm_refine_tiles.h"
+
+#ifdef SBM_WAVE_EMU
+// the streamed stores of the source pass in terms of the emulation's plain ones (the cache hint has no meaning on the CPU)
+namespace wv {
+inline void buf_store_u32_nt(const Buf& b, const V& voff, uint32_t soff, const V& v) { buf_store_u32(b, voff, soff, v); }
+inline void buf_store_u32x3_nt(const Buf& b, const V& voff, uint32_t soff, const V& v0, const V& v1, const V& v2)
+{
+    buf_store_u32(b, voff, soff, v0);
+    buf_store_u32(b, voff, soff + 4, v1);
+    buf_store_u32(b, voff, soff + 8, v2);
+}
+} // namespace wv
+#endif
 
 namespace sbm {
 
@@ -76,7 +90,22 @@ struct QSArgs {
     // the per-lane frame offset of loads and stores differ.  pack_groups = frame groups per row block.
     int32_t pack_lanes, pack_groups;
     int64_t mask_fs;     // bytes from one frame's mask to the next; 0: the frames share one mask (and 0 when mask is null)
+    // The two reduced forms (QSStage below); all zero for the whole row loop.
+    uint8_t* keep;             // QS_SOURCE: frame 0 of the retained copy of the source, rows x cols x CH packed (row stride cols * CH)
+    int64_t keep_fs;           // ... bytes from one frame of it to the next
+    const uint8_t* tile_flags; // QS_SPARSE: n_tiles byte flags per frame (sbm_refine_tiles.h); null: every work item runs
+    int32_t n_tiles, grid_t, grid_w, grid_h; // ... and the T, W, H of the strip level the tiles belong to
 };
+
+// Which part of the row loop a kernel instance holds (compile time):
+//   QS_WHOLE   everything (the header comment above)
+//   QS_SOURCE  load, widen, cv::pyrDown, and the lane's loaded source dwords stored into QSArgs::keep (the useful lanes, the
+//              item's own rows): no Gaussian, Sobel, label or vote, none of their carried state, a loop of its own
+//              (quantize_source_wave).  The next level gets its image and the context keeps the bytes that QS_SPARSE -- or a
+//              later whole launch -- reads
+//   QS_SPARSE  everything but cv::pyrDown; a work item returns before its first load unless it writes a pixel that the strip
+//              builder of a flagged tile of its frame (a packed wave: of any of its frames) loads (gradient_item_needed)
+enum QSStage : int { QS_WHOLE = 0, QS_SOURCE = 1, QS_SPARSE = 2 };
 
 // Gaussian / pyrDown weights as packed pairs (lo | hi << 16)
 #define QS_K(lo, hi) ((uint32_t)(lo) | ((uint32_t)(hi) << 16))
@@ -116,13 +145,179 @@ __device__ __forceinline__ wv::V qs_vote_word(wv::V v, wv::P keep)
     return select(keep, w, 1u);
 }
 
+// QS_SOURCE, one work item: strip `strip`, rows [R0, R1) of the retained copy and rows [R0 / 2, R1 / 2) of cv::pyrDown, for frame
+// `frame` (nseg > 0: the packed last strip of frames frame .. frame+nseg-1) -- the lane layout, the loads and the pyrDown
+// arithmetic of quantize_stream_wave, and nothing else of it.
+// The pass is bound by memory, not by instruction issue, so its loop is built for the memory pipeline: straight-line code with
+// no branch around a load or a store -- a row that is not the item's own, or a pyrDown row that is not, is stored with an offset
+// the buffer range check discards -- so that the compiler's wait counts leave the QS_PREFETCH loads and the stores of the rows
+// before in flight (a store inside a branch made every row wait for all but one outstanding operation: one memory latency per
+// row).  No constant-row shortcut: there is no arithmetic worth skipping.  The window holds 6 rows (pyrDown reads 5), two rows per
+// pyrDown row, so a group of 6 iterations has static register indices and a static row parity: the item's first loaded row
+// R0 - 2 is even (hs and row_lo are), and pyrDown row oy is due when source row 2 oy + 2 has entered the window.
+template <int CH>
+__device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip, int rb, int frame, int nseg)
+{
+    using namespace wv;
+    constexpr int ND = CH == 3 ? 3 : 1;
+    const int rows = a.rows, cols = a.cols;
+    int R0 = a.row_lo + rb * a.hs;
+    if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
+    const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
+    const int cb = strip * QS_USEFUL - QS_HALO_LANES * QS_LANE_PX;
+    const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
+    const int drows = rows >> 1, dcols = cols >> 1;
+
+    const V lane = lane_id();
+    V lseg = lane, segv = splat(0u);
+    const uint32_t seg_lanes = nseg ? (uint32_t)a.pack_lanes : 64u;
+    if (nseg) {
+        for (uint32_t k = 1; k * seg_lanes < 64u; ++k) segv = segv + select(ge_i(lane, splat(k * seg_lanes)), 1u, 0u);
+        lseg = lane - segv * seg_lanes;
+    }
+    const P seg_ok = lt_i(segv, splat(nseg ? (uint32_t)nseg : 1u));
+    const V segc = select(seg_ok, segv, 0u);
+    const V c0 = splat((uint32_t)cb) + (lseg << 2);
+    const V lcol = clamp_i(c0, 0, cols - 4);
+    const V ld_off = (CH == 3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs;
+    const P left_out = lt_i(c0, splat(0u)), right_out = ge_i(c0, splat((uint32_t)cols));
+    const P outside = p_or(left_out, right_out);
+    const bool border_strip = nseg || cb < 0 || cb + 256 > cols;
+    const P store_ok = p_and(p_and(p_and(ge_i(lseg, splat((uint32_t)QS_HALO_LANES)), lt_i(lseg, splat(seg_lanes - QS_HALO_LANES))),
+                                   p_and(ge_i(c0, splat(0u)), lt_i(c0, splat((uint32_t)cols)))),
+                             seg_ok);
+    const uint32_t nfr = nseg ? (uint32_t)nseg : 1u;
+    const Buf pyr_buf = make_buf(a.pyr + (int64_t)frame * a.pyr_fs, nseg ? nfr * (uint32_t)a.pyr_fs : (uint32_t)drows * (uint32_t)dcols * CH);
+    const V pyr_off = select(store_ok, (CH == 3 ? (c0 >> 1) + ((c0 >> 1) << 1) : (c0 >> 1)) + segc * (uint32_t)a.pyr_fs, BUF_DROP);
+    // the retained copy: the lane's dwords as loaded (a useful lane's columns are inside the image: lcol == c0)
+    const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, nseg ? nfr * (uint32_t)a.keep_fs : (uint32_t)rows * (uint32_t)cols * CH);
+    const V keep_off = select(store_ok, (CH == 3 ? c0 + (c0 << 1) : c0) + segc * (uint32_t)a.keep_fs, BUF_DROP);
+    V selA = splat(0x03020100u), selB = splat(0x03020100u), selC = splat(0x07060504u);
+    if (CH == 3) {
+        selA = select(left_out, 0x00020100u, select(right_out, 0x05070605u, 0x03020100u));
+        selB = select(left_out, 0x01000201u, 0x06050706u);
+        selC = select(left_out, 0x02010002u, select(right_out, 0x07060507u, 0x07060504u));
+    } else {
+        selA = select(left_out, 0x00000000u, select(right_out, 0x03030303u, 0x03020100u));
+    }
+    const P pyr_first = eq(c0, splat(0u)), pyr_last = eq(c0, splat((uint32_t)(cols - 4)));
+    const uint32_t K4 = opaque(QS_K(4, 4));
+
+    V win[6][CH][2]; // source rows as u16 pairs, row i of the item in slot i % 6
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int c = 0; c < CH; ++c) win[k][c][0] = win[k][c][1] = splat(0u);
+    V dq[6][ND];
+    auto issue_load = [&](int i, V (&d)[ND]) {
+        int y = R0 - 2 + i;
+        y = y < 0 ? 0 : (y > rows - 1 ? rows - 1 : y);
+        const uint8_t* rowp = img + (int64_t)y * a.stride;
+#pragma unroll
+        for (int q = 0; q < ND; ++q) d[q] = load_u32(rowp + 4 * q, ld_off);
+    };
+    const int n_iter = R1 - R0 + 3; // source rows R0 - 2 .. R1
+#pragma unroll
+    for (int p = 0; p < QS_PREFETCH; ++p) issue_load(p, dq[p]);
+    const int n_groups = (n_iter + 5) / 6;
+    for (int grp = 0; grp < n_groups; ++grp) {
+        const int i0 = grp * 6;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            const int i = i0 + k, y = R0 - 2 + i;
+            issue_load(i + QS_PREFETCH, dq[(k + QS_PREFETCH) % 6]);
+            V d[ND];
+#pragma unroll
+            for (int q = 0; q < ND; ++q) d[q] = dq[k][q];
+            const V koff = y >= R0 && y < R1 ? keep_off : splat(BUF_DROP);
+            if (CH == 3) buf_store_u32x3_nt(keep_buf, koff, (uint32_t)(y * cols * CH), d[0], d[1 % ND], d[2 % ND]);
+            else buf_store_u32_nt(keep_buf, koff, (uint32_t)(y * cols * CH), d[0]);
+            if (border_strip) {
+                if (CH == 3) {
+                    const V n0 = perm(d[2 % ND], d[0], selA), n2 = perm(d[2 % ND], d[0], selC);
+                    const V n1 = select(outside, perm(d[2 % ND], d[0], selB), d[1 % ND]);
+                    d[0] = n0;
+                    d[1 % ND] = n1;
+                    d[2 % ND] = n2;
+                } else {
+                    d[0] = perm(d[0], d[0], selA);
+                }
+            }
+            if (CH == 3) {
+                win[k][0][0] = perm(d[1 % ND], d[0], 0x0c060c00u);
+                win[k][1 % CH][0] = perm(d[1 % ND], d[0], 0x0c070c01u);
+                win[k][2 % CH][0] = perm(d[2 % ND], d[0], 0x0c040c02u);
+                win[k][0][1] = perm(d[2 % ND], d[0], 0x0c050c03u);
+                win[k][1 % CH][1] = perm(d[2 % ND], d[1 % ND], 0x0c060c00u);
+                win[k][2 % CH][1] = perm(d[2 % ND], d[1 % ND], 0x0c070c01u);
+            } else {
+                win[k][0][0] = perm(d[0], d[0], 0x0c020c00u);
+                win[k][0][1] = perm(d[0], d[0], 0x0c030c01u);
+            }
+            if ((k & 1) != 0) continue; // i odd: y odd
+            // ---- cv::pyrDown row oy (source rows 2oy-2 .. 2oy+2 = item rows i-4 .. i), as in quantize_stream_wave ----
+            const int oy = (y - 2) >> 1;
+            const bool mine = oy >= (R0 >> 1) && oy < (R1 >> 1) && oy < drows;
+            uint32_t wr[5] = {1, 4, 6, 4, 1}; // REFLECT_101 at the top / bottom of the image folds taps onto rows inside the window
+            if (oy == 0) {
+                wr[0] = 0, wr[1] = 0, wr[3] = 8, wr[4] = 2;
+                if (rows == 2) wr[2] = 8, wr[4] = 0;
+            } else if (2 * oy + 2 >= rows) {
+                wr[2] = 7, wr[4] = 0;
+            }
+            V ob[CH];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                V ve = pk_mul(win[(k + 2) % 6][c][0], wr[0] * 0x00010001u);
+                V vo = pk_mul(win[(k + 2) % 6][c][1], wr[0] * 0x00010001u);
+#pragma unroll
+                for (int t = 1; t < 5; ++t) {
+                    ve = pk_mad(win[(k + 2 + t) % 6][c][0], wr[t] * 0x00010001u, ve);
+                    vo = pk_mad(win[(k + 2 + t) % 6][c][1], wr[t] * 0x00010001u, vo);
+                }
+                V pve = from_left(ve), pvo = from_left(vo), nve = from_right(ve);
+                if (border_strip) {
+                    pve = select(pyr_first, ve, pve);
+                    pvo = select(pyr_first, vo << 16, pvo);
+                    nve = select(pyr_last, ve >> 16, nve);
+                }
+                const V m2 = alignbit(ve, pve, 16), m1 = alignbit(vo, pvo, 16), p2 = alignbit(nve, ve, 16);
+                V sacc = m2 + p2;
+                sacc = pk_mad(m1 + vo, K4, sacc);
+                sacc = pk_mad(ve, QS_K(6, 6), sacc);
+                ob[c] = pk_lshr(sacc + QS_K(128, 128), 8);
+            }
+            const V poff = mine ? pyr_off : splat(BUF_DROP);
+            const uint32_t prow = (uint32_t)(oy * dcols * CH);
+            if (CH == 3) {
+                buf_store_u16(pyr_buf, poff, prow + 0, perm(ob[1 % CH], ob[0], 0x0c0c0400u));
+                buf_store_u16(pyr_buf, poff, prow + 2, perm(ob[2 % CH], ob[0], 0x0c0c0204u));
+                buf_store_u16(pyr_buf, poff, prow + 4, perm(ob[2 % CH], ob[1 % CH], 0x0c0c0602u));
+            } else {
+                buf_store_u16(pyr_buf, poff, prow, perm(ob[0], ob[0], 0x0c0c0200u));
+            }
+        }
+    }
+}
+
 // One work item: strip `strip`, output rows [rb*hs, min(rb*hs+hs, rows)), frame `frame`.
 // nseg == 0: the whole wave is strip `strip` of frame `frame`; nseg > 0: packed last strip of frames frame .. frame+nseg-1
-template <int CH>
+template <int CH, int STAGE = QS_WHOLE>
 __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0)
 {
     using namespace wv;
     constexpr int ND = CH == 3 ? 3 : 1; // source dwords per lane and row
+    if (STAGE == QS_SOURCE) { // a loop of its own
+        quantize_source_wave<CH>(a, strip, rb, frame, nseg);
+        return;
+    }
+    if (STAGE == QS_SPARSE && a.tile_flags) { // wave-uniform: a few byte loads
+        bool need = false;
+        for (int g = 0; g < (nseg ? nseg : 1); ++g)
+            need = need || gradient_item_needed(a.tile_flags + (int64_t)(frame + g) * a.n_tiles, strip, rb, a.hs, QS_USEFUL, a.rows, a.cols,
+                                                a.grid_t, a.grid_w, a.grid_h);
+        if (!need) return;
+    }
     const int rows = a.rows, cols = a.cols;
     // Every work item owns exactly min(hs, row_hi - row_lo) output rows: the last row block is moved up to end at the
     // launch's last row (it then recomputes a few rows of the block above -- the same bytes, stored twice).  All items of a launch run
@@ -133,7 +328,7 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     const int cb = strip * QS_USEFUL - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
     const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
     uint8_t* out = a.out + (int64_t)frame * a.out_fs;
-    uint8_t* pyr = a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;
+    uint8_t* pyr = STAGE != QS_SPARSE && a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;
     // the frame's own mask (quantize(): one mask per match() call).  No select on a.mask: without a mask mask_fs is 0, so the
     // sum is the null pointer itself and takes the argument's place in the scalar registers -- nothing more stays live
     const uint8_t* mask = a.mask + (int64_t)frame * a.mask_fs;
@@ -546,7 +741,7 @@ __host__ __device__ inline int quantize_stream_items(const QSArgs& a)
     return n_full * a.n_rblocks * a.frames + (a.pack_lanes ? a.n_rblocks * a.pack_groups : 0);
 }
 
-template <int CH>
+template <int CH, int STAGE = QS_WHOLE>
 __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
 {
     // Order: row block slowest, then frame, then strip.  All work items are resident at once (one round) and the
@@ -558,13 +753,13 @@ __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
     const int per_rb = n_full * a.frames, n_plain = per_rb * a.n_rblocks;
     if (item < n_plain) {
         const int rb = item / per_rb, r = item - rb * per_rb;
-        quantize_stream_wave<CH>(a, r % n_full, rb, r / n_full, 0);
+        quantize_stream_wave<CH, STAGE>(a, r % n_full, rb, r / n_full, 0);
     } else {
         const int j = item - n_plain;
         if (!a.pack_lanes || j >= a.n_rblocks * a.pack_groups) return;
         const int rb = j / a.pack_groups, grp = j - rb * a.pack_groups, per = 64 / a.pack_lanes, f0 = grp * per;
         const int nseg = a.frames - f0 < per ? a.frames - f0 : per;
-        quantize_stream_wave<CH>(a, a.n_strips - 1, rb, f0, nseg);
+        quantize_stream_wave<CH, STAGE>(a, a.n_strips - 1, rb, f0, nseg);
     }
 }
 
@@ -584,13 +779,13 @@ __host__ __device__ inline int quantize_stream_pack_lanes(int rows, int cols, in
 
 #ifndef SBM_WAVE_EMU
 // grid = ceil(work items / 4), block = 256 = four independent waves
-template <int CH>
+template <int CH, int STAGE = QS_WHOLE>
 __global__ __launch_bounds__(256) void k_quantize_stream(const QSArgs a)
 {
     // the wave index is the same in all 64 lanes: tell the compiler, so that everything derived from the work item
     // (row counters, stage gating, row base addresses) lives in SGPRs and branches are scalar
     const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    quantize_stream_item<CH>(a, item);
+    quantize_stream_item<CH, STAGE>(a, item);
 }
 #endif
 

@@ -2,6 +2,8 @@
 // reads.  A match call whose plan holds level 0 as LM_BIT_STRIPS_SPARSE (sbm_level_forms.h) builds the strips only in the
 // tiles that k_mark_refine_tiles flags by this arithmetic.  Plain integer code, no HIP types: the kernels use it on the
 // device, tests/test_refine_tiles.py compiles it for the CPU suite.
+// Further down: which pixels of the level's orientation map a tile's strip builder loads, and which work items of the streaming
+// gradient kernel write them (gradient_item_needed: the sparse gradient pass of sbm_quantize_stream.h, tests/test_sparse_gradient.py).
 //
 // A TILE is one workgroup of build_lm_strip4_allty<true> (sbm_lm_kernels.h): RT_STRIPS strips of 16 cells x RT_ROWS grid
 // rows, for all 128 (sub-plane, orientation) planes; tile (tx, ty) of a W x H grid has index ty * ((W + 31) / 32) + tx, the
@@ -90,6 +92,59 @@ SBM_RT_HD void refine_tiles_for_each(const RefineTiles& t, int W, int H, F mark)
     if (t.over >= 0)
         for (int s = t.s0 + 1; s <= t.s1 + 1; ++s)
             for (int ty = 0; ty <= t.over / RT_ROWS; ++ty) mark(ty * n_cb + (s % ns) / RT_STRIPS);
+}
+
+// ---- which pixels of the level's orientation map a tile's strip builder loads, and which gradient work items make them ----
+// The workgroup of tile (tx, ty) of build_lm_strip4_allty<true> (T = 4, W a multiple of 16): thread (row, kk) owns the 4 cells
+// k = tx * 8 + kk of grid row gy = ty * RT_ROWS + row (gy < H) and loads, of the map, pixel rows gy * T .. gy * T + 2T - 2 that lie
+// below `rows`, columns k * 4T .. k * 4T + 4T - 1 and -- short of the last column -- the T pixels to their right (the spread's
+// reach).  Over the workgroup that is one rectangle [x0, x1) x [y0, y1):
+struct PixelRect {
+    int x0, y0, x1, y1;
+};
+SBM_RT_HD PixelRect refine_tile_pixels(int tx, int ty, int rows, int cols, int T, int W, int H)
+{
+    const int cells = 16 * RT_STRIPS;
+    const int gx1 = (tx + 1) * cells < W ? (tx + 1) * cells : W, gy1 = (ty + 1) * RT_ROWS < H ? (ty + 1) * RT_ROWS : H;
+    const int x1 = gx1 * T + T, y1 = gy1 * T + T - 1; // right halo; the last grid row's window of 2T - 1 rows
+    return PixelRect{tx * cells * T, ty * RT_ROWS * T, x1 < cols ? x1 : cols, y1 < rows ? y1 : rows};
+}
+
+// some flagged tile's builder loads a pixel of [x0, x1) x [y0, y1).  flags: one byte per tile of one frame.
+SBM_RT_HD bool refine_rect_needed(const uint8_t* flags, int x0, int y0, int x1, int y1, int rows, int cols, int T, int W, int H)
+{
+    const int n_cb = refine_tile_cols(W), n_rb = refine_tile_rows(H), tw = 16 * RT_STRIPS * T, th = RT_ROWS * T;
+    if (x0 >= x1 || y0 >= y1) return false;
+    // the first tile column / row whose rectangle can reach x0 / y0 (it ends T, T - 1 pixels past the tile), the last that starts before x1 / y1
+    const int tx_lo = x0 >= T ? (x0 - T) / tw : 0, ty_lo = y0 >= T - 1 ? (y0 - (T - 1)) / th : 0;
+    const int tx_hi = (x1 - 1) / tw < n_cb - 1 ? (x1 - 1) / tw : n_cb - 1, ty_hi = (y1 - 1) / th < n_rb - 1 ? (y1 - 1) / th : n_rb - 1;
+    for (int ty = ty_lo; ty <= ty_hi; ++ty)
+        for (int tx = tx_lo; tx <= tx_hi; ++tx) {
+            if (!flags[ty * n_cb + tx]) continue;
+            const PixelRect r = refine_tile_pixels(tx, ty, rows, cols, T, W, H);
+            if (r.x0 < x1 && x0 < r.x1 && r.y0 < y1 && y0 < r.y1) return true;
+        }
+    return false;
+}
+
+// Output rows [*r0, *r1) of row block rb of a whole-level launch of the streaming gradient kernel with hs rows per work item
+// (sbm_quantize_stream.h: the last block is moved up to end at the last row)
+SBM_RT_HD void gradient_item_rows(int rb, int hs, int rows, int* r0, int* r1)
+{
+    int a = rb * hs;
+    if (a + hs > rows) a = rows > hs ? rows - hs : 0;
+    *r0 = a;
+    *r1 = a + hs < rows ? a + hs : rows;
+}
+
+// The gradient work item (strip, rb) -- `useful` output columns per strip, hs rows per item -- writes a pixel that the strip
+// builder of a flagged tile loads.  The kernel and tests/test_sparse_gradient.py share this function.
+SBM_RT_HD bool gradient_item_needed(const uint8_t* flags, int strip, int rb, int hs, int useful, int rows, int cols, int T, int W, int H)
+{
+    int r0, r1;
+    gradient_item_rows(rb, hs, rows, &r0, &r1);
+    const int x0 = strip * useful, x1 = x0 + useful < cols ? x0 + useful : cols;
+    return refine_rect_needed(flags, x0, r0, x1, r1, rows, cols, T, W, H);
 }
 
 } // namespace sbm

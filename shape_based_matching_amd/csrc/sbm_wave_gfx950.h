@@ -141,6 +141,14 @@ __device__ __forceinline__ Buf make_buf(uint8_t* base, uint32_t bytes)
 }
 // address = base + voff (per lane) + soff (wave-uniform); 4- / 2-byte aligned by construction
 __device__ __forceinline__ void buf_store_u32(const Buf& b, V voff, uint32_t soff, V v) { __builtin_amdgcn_raw_buffer_store_b32(v, b.rsrc, (int)voff, (int)soff, 0); }
+// ... streamed (nt): bytes written once and read, if ever, by a later launch -- they need not stay in the caches on the way.
+// Three consecutive dwords of a lane in one instruction: a wave's store is then one run of 768 bytes, not three interleaved ones.
+typedef uint32_t wv_u32x3 __attribute__((ext_vector_type(3)));
+__device__ __forceinline__ void buf_store_u32_nt(const Buf& b, V voff, uint32_t soff, V v) { __builtin_amdgcn_raw_buffer_store_b32(v, b.rsrc, (int)voff, (int)soff, 2); }
+__device__ __forceinline__ void buf_store_u32x3_nt(const Buf& b, V voff, uint32_t soff, V v0, V v1, V v2)
+{
+    __builtin_amdgcn_raw_buffer_store_b96(wv_u32x3{v0, v1, v2}, b.rsrc, (int)voff, (int)soff, 2);
+}
 __device__ __forceinline__ void buf_store_u16(const Buf& b, V voff, uint32_t soff, V v)
 {
     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, b.rsrc, (int)voff, (int)soff, 0);
