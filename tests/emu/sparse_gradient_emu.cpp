@@ -55,14 +55,18 @@ extern "C" int sbm_emu_whole_pass(const uint8_t* img, int frames, int rows, int 
     return a.pack_lanes;
 }
 
-// the source pass over `frames` packed frames: pyr = the next level's images, keep = the retained copy
-extern "C" int sbm_emu_source_pass(const uint8_t* img, int frames, int rows, int cols, int ch, int hs, int pack, uint8_t* pyr, uint8_t* keep)
+// the source pass over `frames` frames in the caller's layout (rows of `stride` bytes, frames `img_fs` bytes apart):
+// pyr = the next level's images, keep = the retained copy, both packed
+extern "C" int sbm_emu_source_pass(const uint8_t* img, int frames, int rows, int cols, int ch, int hs, int pack, int stride, int64_t img_fs,
+                                   uint8_t* pyr, uint8_t* keep)
 {
-    if (bad_geometry(frames, rows, cols, ch, hs)) return -1;
+    if (bad_geometry(frames, rows, cols, ch, hs) || stride < cols * ch || img_fs < (int64_t)rows * stride) return -1;
     QSArgs a = batch_args(img, frames, rows, cols, ch, 0.f, hs, pack);
+    a.stride = stride;
+    a.img_fs = img_fs;
     a.pyr = pyr;
     a.keep = keep;
-    a.keep_fs = a.img_fs;
+    a.keep_fs = (int64_t)rows * cols * ch;
     for (int item = 0; item < quantize_stream_items(a); ++item) {
         if (ch == 3) quantize_stream_item<3, QS_SOURCE>(a, item);
         else quantize_stream_item<1, QS_SOURCE>(a, item);

@@ -31,6 +31,24 @@ def test_sequence_fuzz_slice():
     assert fuzz_sequence.run(12, 5, 25, verbose=False) > 2000
 
 
+def test_sparse_sequence_fuzz_slice():
+    """8 sequences x 30 steps of the sparse profile (tests/test_sequence_generator.py counts what the slice contains): the
+    (4, 8) pyramid in stream mode, padded and interleaved caller layouts, cut tile columns, readers behind sparse calls and
+    behind overwritten caller buffers"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fuzz_sequence
+
+    from test_sequence_generator import SPARSE_SLICE, sparse_counts
+
+    seed, n, steps = SPARSE_SLICE
+    assert fuzz_sequence.run(n, seed, steps, verbose=False, profile="sparse") > 2000
+    # the calls drawn as profiled ran under sbm_set_profiling: every sparse-eligible one made the sparse path's three
+    # gradient launches (the Runner fails on any other count), and the Runner saw as many as the generator drew
+    if fuzz_sequence.LAST_RUN["sparse_on"]:
+        assert fuzz_sequence.LAST_RUN["sparse_proven"] == sum(sparse_counts(seed, n, steps)["profiled"].values()) >= 8
+
+
 def big_frames(case1, n=2):
     img = case1["test"]
     offs = [(300, 500), (1500, 1200), (900, 100)]

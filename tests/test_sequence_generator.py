@@ -1,5 +1,6 @@
 """tools/fuzz_sequence.py's generator on the CPU (no torch.cuda, no GPU): deterministic operation lists, coverage of every
-operation kind, pyramid and graph mode over the GPU slice's seeds, the stream rule, and replayable prefixes."""
+operation kind, pyramid and graph mode over the GPU slice's seeds, the stream rule, and replayable prefixes; the "sparse"
+profile's slice counted against the conditions it exists for (sparse-eligible calls per entry point, readers behind them)."""
 import os
 import shlex
 import sys
@@ -93,3 +94,129 @@ def test_printed_replay_line_parses_back_to_the_same_prefix():
         assert (a.n, a.seed, a.only, a.steps, a.stop) == (1, seed, i, steps, stop)
         # Runner.run(seed, only, steps, stop) applies generate(seed, only, steps)[1][: stop + 1]
         assert F.generate(a.seed, a.only, a.steps)[1][: a.stop + 1] == F.generate(seed, i, steps)[1][: stop + 1]
+
+
+# ---- the sparse profile -------------------------------------------------------------------------------------------------
+
+SPARSE_SLICE = (3, 8, 30)  # seed, sequences, steps of tests/test_gpu_sequences.py::test_sparse_sequence_fuzz_slice
+NEW_GEOS = {"P": (448, 576, 3), "Q": (512, 704, 1)}
+
+
+def eligible(T, qmode, op):
+    """the issue's predicate, restated: T = (4, 8), stream mode, a 16-cell-aligned geometry, no mask, not banded"""
+    return (T == (4, 8) and qmode == "stream" and op["op"] in ("match", "match_device", "match_batch_device", "match_batch_host")
+            and (F.ALL_GEOS[op["geo"]][1] // 4) % 16 == 0 and not op["mask"])
+
+
+def sparse_counts(seed, n, steps):
+    """what the sparse slice contains, from the operation lists alone"""
+    FRAME_TAKING = ("match", "match_device", "match_batch_device", "match_batch_host", "match_banded", "build_pyramid")
+    READERS = ("get_quantized", "get_quantized_frame", "match_templates", "match_templates_device", "set_quantized")
+    c = {"eligible": 0, "by": {}, "readers": 0, "clobbered_readers": 0, "grow": 0, "shrink": 0, "channel_switch_readers": 0,
+         "geos": set(), "row_pads": set(), "frame_pads": set(), "left_and_back": 0, "frame_reads_past_0": 0, "profiled": {}}
+    for i in range(n):
+        T, ops = F.generate(seed, i, steps, "sparse")
+        assert T == (4, 8) and len(ops) == steps
+        assert ops[0]["op"] == "set_quantize_mode" and ops[0]["mode"] == "stream" and ops[0]["hs"] in (8, 18, 32)
+        qmode = "auto"
+        behind_sparse_batch = clobbered = False  # no frame-taking call since a sparse-eligible device batch / a clobber since it
+        last_eligible_B = None                   # frames of the last eligible device batch of this sequence
+        last_ch = None                           # channels of the last frame-taking call
+        switched = False                         # ... which differed from those of the one before; no frame-taking call since
+        last_B = 0
+        for k, o in enumerate(ops):
+            name = o["op"]
+            if name == "set_quantize_mode":
+                c["left_and_back"] += qmode != "stream" and o["mode"] == "stream" and k > 0
+                qmode = o["mode"]
+            is_reader = name in READERS or (name in ("get_linear_memories", "similarity_local") and o["level"] == 0)
+            if name in ("get_quantized", "get_quantized_frame") and o["level"] != 0:
+                is_reader = False
+            if is_reader:
+                c["readers"] += behind_sparse_batch
+                c["clobbered_readers"] += behind_sparse_batch and clobbered
+                c["channel_switch_readers"] += switched
+                switched = False
+            if name == "get_quantized_frame":
+                assert 0 <= o["frame"] < max(last_B, 1), (i, k)
+                c["frame_reads_past_0"] += o["frame"] > 0
+            if name == "clobber_inputs":
+                assert ops[k - 1]["op"] == "checkpoint", (i, k)
+                clobbered = True
+            if name in FRAME_TAKING or name == "set_quantized":
+                ch = F.ALL_GEOS[o["geo"]][2]
+                if name != "set_quantized":
+                    switched = last_ch is not None and ch != last_ch
+                    last_ch = ch
+                behind_sparse_batch = clobbered = False
+                last_B = len(o["vars"]) if name == "match_batch_device" else 1
+                c["geos"].add(o["geo"])
+                if "row_pad" in o:
+                    c["row_pads"].add(o["row_pad"])
+                if "frame_pad" in o:
+                    c["frame_pads"].add(o["frame_pad"])
+                assert ("row_pad" in o) == (name in ("match_device", "match_batch_device", "match_banded")), (i, k)
+                assert ("frame_pad" in o) == (name in ("match_batch_device", "match_banded")), (i, k)
+            if name in FRAME_TAKING and eligible(T, qmode, o):
+                c["eligible"] += 1
+                c["by"][name] = c["by"].get(name, 0) + 1
+                if o["profiled"]:  # the Runner counts the gradient launches of these
+                    c["profiled"][name] = c["profiled"].get(name, 0) + 1
+                if name == "match_batch_device":
+                    B = len(o["vars"])
+                    if last_eligible_B is not None:
+                        c["grow"] += B > last_eligible_B
+                        c["shrink"] += B < last_eligible_B
+                    last_eligible_B = B
+                    behind_sparse_batch = True
+    return c
+
+
+def test_sparse_profile_is_deterministic_and_leaves_the_default_profile_alone():
+    seed, n, steps = SPARSE_SLICE
+    for i in range(n):
+        assert F.generate(seed, i, steps, "sparse") == F.generate(seed, i, steps, "sparse")
+        assert F.generate(seed, i, steps + 7, "sparse")[1][:steps] == F.generate(seed, i, steps, "sparse")[1]
+        assert F.generate(seed, i, steps, "default") == F.generate(seed, i, steps)
+        assert F.generate(seed, i, steps, "sparse") != F.generate(seed, i, steps)
+    for name, g in NEW_GEOS.items():
+        assert F.SPARSE_GEOS[name] == g and name not in F.GEOS  # the default profile draws from GEOS: it must not grow
+        assert (g[1] // 4) % 32 == 16                            # a cut last tile column
+    assert set(F.SPARSE_GEOS) == {"A", "B", "G", "P", "Q"}
+    a = F.parse_args(shlex.split(F.replay_command(seed, 3, steps, 11, "sparse"))[2:])
+    assert (a.n, a.seed, a.only, a.steps, a.stop, a.profile) == (1, seed, 3, steps, 11, "sparse")
+    assert F.parse_args(shlex.split(F.replay_command(seed, 3, steps, 11))[2:]).profile == "default"
+
+
+def test_default_slice_has_no_sparse_eligible_call():
+    """why the second profile exists: the default slice never takes the sparse level-0 path"""
+    seed, n, steps = SLICE
+    total = 0
+    for i in range(n):
+        T, ops = F.generate(seed, i, steps)
+        qmode = "auto"
+        for o in ops:
+            if o["op"] == "set_quantize_mode":
+                qmode = o["mode"]
+            total += eligible(T, qmode, o)
+            assert eligible(T, qmode, o) == F.sparse_eligible(T, qmode, o) if "geo" in o and "mask" in o else True
+    assert total == 0
+
+
+def test_sparse_slice_meets_its_conditions():
+    """conditions on the generator (not measurements), for the pinned seed of the GPU slice"""
+    seed, n, steps = SPARSE_SLICE
+    assert n <= 8 and steps <= 30
+    c = sparse_counts(seed, n, steps)
+    assert c["eligible"] >= 40, c
+    for entry in ("match_batch_device", "match_device", "match", "match_batch_host"):
+        assert c["by"].get(entry, 0) >= 4, c
+    assert c["readers"] >= 10, c
+    assert c["clobbered_readers"] >= 3, c
+    assert c["grow"] >= 3 and c["shrink"] >= 3, c
+    assert c["channel_switch_readers"] >= 2, c
+    assert c["geos"] >= set(NEW_GEOS), c
+    assert c["row_pads"] == {0, 13, 64} and c["frame_pads"] == {0, 1000, -1}, c
+    assert c["left_and_back"] >= 1 and c["frame_reads_past_0"] >= 1, c
+    for entry in ("match_batch_device", "match_device", "match", "match_batch_host"):
+        assert c["profiled"].get(entry, 0) >= 2, c  # ... each proven sparse on the GPU by its launch count

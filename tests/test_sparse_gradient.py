@@ -5,7 +5,7 @@ Three parts, all compiled here for the CPU (tests/emu/sparse_gradient_emu.cpp):
               every pixel that the tile's workgroup of build_lm_strip4_allty<true> loads (the loads enumerated thread by thread
               from that kernel's index arithmetic), and a single tile never keeps more than a bounded share of the items
   emulation   sbm_quantize_stream.h on wave_emu.h: the source pass (QS_SOURCE) gives the whole kernel's cv::pyrDown output and
-              an exact copy of the input; the sparse pass (QS_SPARSE) over that copy gives the whole kernel's map bit for bit
+              an exact, packed copy of the input -- also from padded rows and padded or interleaved frames; the sparse pass (QS_SPARSE) over that copy gives the whole kernel's map bit for bit
               with every tile flagged, and with some tiles flagged the map on every pixel those tiles' builders load and a
               poison pattern wherever it wrote nothing
   plan        sbm_level_forms.h: BuildPlan::sparse_gradient is set exactly when level 0 is planned LM_BIT_STRIPS_SPARSE by a
@@ -15,12 +15,16 @@ import itertools
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
 from shape_based_matching_amd import synth
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from fuzz_sequence import padded_layout  # noqa: E402
 
 CSRC = os.path.join(ROOT, "shape_based_matching_amd", "csrc")
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
@@ -40,7 +44,7 @@ def emu(tmp_path_factory):
     L = C.CDLL(so)
     vp, i = C.c_void_p, C.c_int
     L.sbm_emu_whole_pass.argtypes = [vp, i, i, i, i, C.c_float, i, i, vp, vp]
-    L.sbm_emu_source_pass.argtypes = [vp, i, i, i, i, i, i, vp, vp]
+    L.sbm_emu_source_pass.argtypes = [vp, i, i, i, i, i, i, i, C.c_int64, vp, vp]
     L.sbm_emu_sparse_pass.argtypes = [vp, i, i, i, i, C.c_float, i, i, vp, i, i, i, vp]
     L.sbm_emu_footprint.argtypes = [i, i, i, i, i, vp, vp]
     L.sbm_emu_footprint.restype = C.c_int64
@@ -55,13 +59,14 @@ def emu(tmp_path_factory):
 HS = list(range(2, 132, 2)) + [256, 1024]
 
 
-@pytest.mark.parametrize("cols", [512, 640, 1024])
+@pytest.mark.parametrize("cols", [512, 640, 1024, 448, 576, 704])
 def test_kept_items_cover_every_pixel_a_flagged_tiles_builder_loads(emu, cols):
-    """widths: 512 (two full strips and a 32-column last strip, the packed one), 640, 1024; 3 .. 8 tile rows, the last one whole
-    and cut; every hs; every single flagged tile"""
+    """widths: 512 (two full strips and a 32-column last strip, the packed one), 640, 1024, and 448, 576, 704, whose last tile
+    column is cut to 16 cells; 3 .. 8 tile rows, the last one whole and cut; every hs; every single flagged tile"""
     kept, loaded = C.c_int32(0), C.c_int64(0)
     n_cb = (cols // T + 31) // 32
-    assert n_cb in (4, 5, 8)
+    assert n_cb == {512: 4, 640: 5, 1024: 8, 448: 4, 576: 5, 704: 6}[cols]
+    assert ((cols // T) % 32 == 16) == (cols in (448, 576, 704))
     for tile_rows in range(3, 9):
         for rows in (tile_rows * 128, tile_rows * 128 - 80):
             n_rb = (rows // T + 31) // 32
@@ -106,7 +111,8 @@ def make_frames(n, rows, cols, ch, seed):
 
 
 CASES = [(96, 512, 3, 1), (96, 512, 3, 3), (96, 512, 1, 3), (96, 512, 1, 1), (70, 260, 3, 1), (70, 260, 3, 3), (70, 260, 1, 1), (70, 260, 1, 3),
-         (272, 512, 1, 2)]  # the last: three tile rows, so that whole row blocks are skipped
+         (272, 512, 1, 2),  # three tile rows, so that whole row blocks are skipped
+         (96, 576, 3, 3)]   # a cut tile column; the 96-column last strip packed two frames per wave: a whole group and a partial one
 
 
 @pytest.mark.parametrize("rows,cols,ch,n", CASES)
@@ -123,8 +129,11 @@ def test_the_two_forms_reproduce_the_whole_kernel(emu, rows, cols, ch, n):
 
         pyr = np.full(shape_p, POISON, np.uint8)
         keep = np.full(frames.shape, POISON, np.uint8)
-        lanes = emu.sbm_emu_source_pass(frames.ctypes.data, n, rows, cols, ch, hs_src, pack, pyr.ctypes.data, keep.ctypes.data)
-        assert lanes >= 0 and (lanes > 0) == (pack == 1 and n > 1 and cols in (260, 512))
+        lanes = emu.sbm_emu_source_pass(frames.ctypes.data, n, rows, cols, ch, hs_src, pack, cols * ch, rows * cols * ch, pyr.ctypes.data,
+                                        keep.ctypes.data)
+        assert lanes >= 0 and (lanes > 0) == (pack == 1 and n > 1 and cols in (260, 512, 576))
+        if cols == 576 and lanes:
+            assert 64 // lanes == 2 and n % 2 == 1  # the last group holds one frame
         assert np.array_equal(pyr, want_pyr), np.argwhere(pyr != want_pyr)[:5]
         assert np.array_equal(keep, frames), np.argwhere(keep != frames)[:5]
 
@@ -151,6 +160,30 @@ def test_the_two_forms_reproduce_the_whole_kernel(emu, rows, cols, ch, n):
         assert ((got == want) | (got == POISON)).all()  # written = right, everything else untouched
         if n_cb * n_rb >= 4 and hs <= 18:
             assert (got == POISON).sum() > got.size // 8, (got == POISON).mean()  # ... and work was skipped
+
+
+LAYOUTS = [(13, 0), (64, 0), (0, 1000), (0, -1), (13, -1), (64, 1000)]  # (row pad, frame pad; -1: a whole, inverted frame between)
+
+
+@pytest.mark.parametrize("rows,cols,ch,n", [(96, 576, 3, 3), (96, 576, 1, 3), (70, 260, 3, 3), (70, 260, 1, 2), (70, 260, 3, 1)])
+def test_source_pass_reads_the_callers_layout_and_writes_packed(emu, rows, cols, ch, n):
+    """the source pass on padded rows and padded or interleaved frames: the retained copy is the packed input, cv::pyrDown is
+    the whole kernel's on the packed frames, and no byte of the padding (0xA5, or the inverted frame) shows in either"""
+    frames = make_frames(n, rows, cols, ch, 23 + rows + ch)
+    shape_p = (n, rows // 2, cols // 2) + ((3,) if ch == 3 else ())
+    for hs_src, pack in ((32, 1), (18, 1), (4, 0)):
+        want_pyr = np.full(shape_p, POISON, np.uint8)
+        scratch = np.full((n, rows, cols), POISON, np.uint8)
+        assert emu.sbm_emu_whole_pass(frames.ctypes.data, n, rows, cols, ch, 30.0, 18, pack, scratch.ctypes.data, want_pyr.ctypes.data) >= 0
+        for row_pad, frame_pad in LAYOUTS:
+            buf, stride, fs = padded_layout(list(frames), row_pad, frame_pad)
+            assert buf.size > frames.size and stride == cols * ch + row_pad
+            pyr = np.full(shape_p, POISON, np.uint8)
+            keep = np.full(frames.shape, POISON, np.uint8)
+            lanes = emu.sbm_emu_source_pass(buf.ctypes.data, n, rows, cols, ch, hs_src, pack, stride, fs, pyr.ctypes.data, keep.ctypes.data)
+            assert lanes >= 0 and (lanes > 0) == (pack == 1 and n > 1), (row_pad, frame_pad, lanes)
+            assert np.array_equal(keep, frames), (row_pad, frame_pad, hs_src, np.argwhere(keep != frames)[:5])
+            assert np.array_equal(pyr, want_pyr), (row_pad, frame_pad, hs_src, np.argwhere(pyr != want_pyr)[:5])
 
 
 # ---- plan -----------------------------------------------------------------------------------------------------------------

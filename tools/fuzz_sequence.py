@@ -30,7 +30,12 @@ The operation list of a sequence is a pure function of (seed, sequence index, st
 a GPU.  On the first failure run() raises with the seed, the step, the operation log up to it and a command line that
 replays exactly that prefix; nothing is retried.
 
-usage: python tools/fuzz_sequence.py [n_sequences] [seed] [--steps S] [--only I] [--stop K]
+A second generator profile, "sparse" (_generate_sparse), stays on the (4, 8) pyramid with the streaming gradient kernel forced,
+where a frame-taking match call makes level 0 only where its coarse candidates read it: padded and interleaved caller layouts,
+two geometries with a cut tile column, batches that grow and shrink, readers of level 0 behind such a call -- also after
+clobber_inputs overwrote the caller's device buffers -- and get_quantized_frame of every frame of the last device batch.
+
+usage: python tools/fuzz_sequence.py [n_sequences] [seed] [--steps S] [--only I] [--stop K] [--profile default|sparse]
        (--only I: sequence I alone; --stop K: its first K + 1 steps)"""
 import argparse
 import os
@@ -48,6 +53,15 @@ PYRAMIDS = [(4, 8), (4,), (8, 8), (4, 8, 8)]
 # linear-memory builder, the strip and bit-strip forms give way to the byte fall-backs (single-frame entry points only)
 GEOS = {"A": (512, 768, 3), "B": (448, 640, 3), "G": (512, 768, 1), "O": (480, 608, 3)}
 BATCH_GEOS = ("A", "B", "G")
+# The sparse profile's geometries: A, B, G and two whose last refinement tile column is cut to 16 cells ((cols / 4) % 32 == 16).
+# "P": 3.5 x 4.5 tiles, a 96-column last strip packed two frames per wave; "Q": gray, 4 x 5.5 tiles.  Kept apart from GEOS: the
+# default profile draws from tuple(GEOS), and its output must not change.
+SPARSE_GEOS = {"A": GEOS["A"], "B": GEOS["B"], "G": GEOS["G"], "P": (448, 576, 3), "Q": (512, 704, 1)}
+ALL_GEOS = {**GEOS, **SPARSE_GEOS}
+PROFILES = ("default", "sparse")
+ROW_PADS = (0, 13, 64)        # bytes behind every row of a device frame
+FRAME_PADS = (0, 1000, -1)    # bytes behind every frame of a device batch; -1: one whole frame (the inverted frame lies there)
+SPARSE_HS = (8, 18, 32)
 N_VARIANTS = 4
 THRESHOLDS = (98.0, 90.0, 80.0, 60.0, 0.0, -5.0)
 GRAPH_MODES = (-1, 0, 1)
@@ -58,6 +72,18 @@ MATCH_OPS = ("match", "match_device", "match_batch_device", "match_batch_host", 
              "match_templates_device", "nms")
 STATE_OPS = ("build_pyramid", "set_quantized")
 READ_OPS = ("get_quantized", "get_linear_memories", "get_coarse_bitplanes", "similarity", "similarity_local")
+# the sparse profile's own operations: a frame of the last device batch read back, and the caller's device buffers of every
+# synchronised call overwritten (legal for a caller: the library keeps what it needs)
+SPARSE_ONLY_OPS = ("get_quantized_frame", "clobber_inputs")
+FRAME_MATCH_OPS = ("match", "match_device", "match_batch_device", "match_batch_host")  # entry points that can take the sparse path
+LEVEL0_READERS = ("get_quantized", "get_quantized_frame", "get_linear_memories", "match_templates", "match_templates_device",
+                  "similarity_local", "set_quantized")
+_SPARSE_WEIGHTS = {"match_batch_device": 10, "match_device": 5, "match": 4, "match_batch_host": 4, "match_banded": 1, "nms": 2,
+                   "match_templates": 2, "match_templates_device": 2, "get_quantized": 2, "get_quantized_frame": 4,
+                   "get_linear_memories": 2, "similarity_local": 2, "set_quantized": 2, "build_pyramid": 1, "set_graph_mode": 2,
+                   "set_pipeline_depth": 1, "set_quantize_mode": 1, "checkpoint": 2, "clobber_inputs": 2, "stall": 1}
+_SPARSE_FOLLOWERS = ("get_quantized", "get_quantized_frame", "get_quantized_frame", "get_linear_memories", "match_templates",
+                     "match_templates_device", "similarity_local", "set_quantized")
 TEMPLATE_OPS = ("upload_templates", "select_range", "select_classes", "select_templates", "select_empty", "select_all")
 MODE_OPS = ("set_coarse_mode", "set_refine_bits", "set_refine_order", "set_quantize_mode", "set_pipeline_depth", "set_graph_mode")
 SYNC_OPS = ("checkpoint", "switch_stream")
@@ -75,8 +101,19 @@ def sequence_seed(seed, index):
     return (int(seed) * 1000003 + int(index) * 7919 + 17) % (1 << 31)
 
 
-def generate(seed, index, steps):
+def sparse_eligible(T, qmode, op):
+    """the call can take the sparse level-0 path: a frame-taking match entry point on the (4, 8) pyramid, the streaming kernel
+    forced, level 0 a grid of whole 16-cell strips, no mask (a banded call is another operation)"""
+    return (tuple(T) == (4, 8) and qmode == "stream" and op["op"] in FRAME_MATCH_OPS and not op["mask"]
+            and (ALL_GEOS[op["geo"]][1] // 4) % 16 == 0)
+
+
+def generate(seed, index, steps, profile="default"):
     """(pyramid, [op dict]) of sequence `index` of `seed`: deterministic, no torch, no GPU"""
+    if profile == "sparse":
+        return _generate_sparse(seed, index, steps)
+    if profile != "default":
+        raise ValueError(f"profile {profile!r}: one of {PROFILES}")
     rs = np.random.RandomState(sequence_seed(seed, index))
     T = PYRAMIDS[index % len(PYRAMIDS)] if index < len(PYRAMIDS) else PYRAMIDS[int(rs.randint(len(PYRAMIDS)))]
     names = list(ALL_OPS)
@@ -192,6 +229,137 @@ def generate(seed, index, steps):
     return T, ops[:steps]
 
 
+def _generate_sparse(seed, index, steps):
+    """The sparse profile: the (4, 8) pyramid with the streaming kernel forced, so that most frame-taking calls take the sparse
+    level-0 path (source pass, mark tiles, flagged gradient, flagged strips) and the operations between them read, replace or
+    outlive what such a call leaves: padded and interleaved caller layouts, batches that grow and shrink, 1- and 3-channel
+    geometries in turn, readers right behind a sparse batch -- also after the caller's buffers were overwritten.  A call drawn
+    as "profiled" runs under sbm_set_profiling, and the Runner counts its gradient launches: three where it is sparse-eligible."""
+    rs = np.random.RandomState((sequence_seed(seed, index) ^ 0x5a17e5) % (1 << 31))
+    T = PYRAMIDS[0]
+    names = list(_SPARSE_WEIGHTS)
+    p = np.array([_SPARSE_WEIGHTS[n] for n in names], np.float64)
+    p /= p.sum()
+    geos = tuple(SPARSE_GEOS)
+    n_set = SET_SIZES[0]
+    qmode = "stream"
+    have_batch = False   # a device batch ran since the start: device NMS has lists to work on
+    last_B = 1           # frames of the last device batch still resident (1 after a single-frame call or a state call)
+    forced = []          # operations that follow the last one at once
+    since_sync = 0
+    ops = [{"op": "set_quantize_mode", "mode": "stream", "hs": int(rs.choice(SPARSE_HS))}]
+    if int(rs.randint(2)):
+        ops.append({"op": "set_graph_mode", "mode": int(GRAPH_MODES[int(rs.randint(3))])})
+    if int(rs.randint(2)):
+        ops.append({"op": "set_pipeline_depth", "depth": int(rs.choice([2, 4]))})
+
+    def thr():
+        return float(THRESHOLDS[int(rs.randint(4))])  # every template stays selected: thresholds above 0 only
+
+    while len(ops) < steps:
+        if forced:
+            name = forced.pop(0)
+        elif qmode != "stream" and rs.randint(3) == 0:
+            name = "set_quantize_mode"  # ... and back into stream mode
+        else:
+            name = names[int(rs.choice(len(names), p=p))]
+            if since_sync >= 6 and name not in ("checkpoint", "clobber_inputs") and rs.randint(3) == 0:
+                name = "checkpoint"
+        op = {"op": name}
+        if name in ("match", "match_device", "build_pyramid", "set_quantized"):
+            op["geo"], op["var"], op["mask"] = str(rs.choice(geos)), int(rs.randint(N_VARIANTS)), bool(rs.randint(8) == 0)
+            if name in ("match", "match_device"):
+                op["thr"] = thr()
+            if name == "match_device":
+                op["row_pad"] = int(rs.choice(ROW_PADS))
+            if name in ("match", "match_device"):
+                op["profiled"] = bool(rs.randint(3) == 0)
+            last_B = 1
+        elif name in ("match_batch_device", "match_batch_host", "match_banded"):
+            op["geo"] = str(rs.choice(geos))
+            op["mask"] = bool(rs.randint(5 if name == "match_batch_device" else 8) == 0)
+            if name == "match_banded":
+                if qmode == "tile":
+                    op["op"] = name = "match_batch_device"
+                else:
+                    op["geo"] = str(rs.choice(["A", "G"]))
+                    op["n_bands"] = int(rs.choice([2, 4, 8]))
+            B = int(rs.randint(1, 10 if name != "match_batch_host" else 6))
+            op["vars"] = [int(rs.randint(N_VARIANTS)) for _ in range(B)]
+            op["thr"] = thr()
+            if name == "match_batch_host":
+                op["sub_batch"] = int(rs.randint(1, 5))
+                op["split"] = bool(rs.randint(2))
+                op["pinned"] = bool(rs.randint(2))
+                last_B = 1  # (which sub-batch stays resident is not part of the ABI: frame 0 only, unchecked)
+            else:
+                op["row_pad"] = int(rs.choice(ROW_PADS))
+                op["frame_pad"] = int(rs.choice(FRAME_PADS))
+                have_batch = True
+                last_B = B if name == "match_batch_device" else 1
+            if name != "match_banded":
+                op["profiled"] = bool(rs.randint(3) == 0)
+            if name == "match_batch_device" and rs.randint(5) < 3:
+                # a reader right behind the batch, sometimes with the caller's buffers overwritten first
+                if rs.randint(5) < 2:
+                    forced += ["checkpoint", "clobber_inputs"]
+                forced.append(_SPARSE_FOLLOWERS[int(rs.randint(len(_SPARSE_FOLLOWERS)))])
+        elif name in ("match_templates", "match_templates_device"):
+            op["thr"] = thr()
+        elif name == "nms":
+            if not have_batch:
+                continue
+            op["score"] = float(rs.choice([0.0, 85.0, 95.0]))
+            op["nms"] = float(rs.choice([0.3, 0.5, 1.0]))
+        elif name in ("get_quantized", "get_linear_memories"):
+            op["level"] = int(rs.randint(4) == 0)  # level 0 three times in four
+        elif name == "get_quantized_frame":
+            op["level"] = int(rs.randint(4) == 0)
+            op["frame"] = int(rs.randint(last_B))
+        elif name == "similarity_local":
+            op["level"] = 0
+            op["t"] = int(rs.randint(n_set))
+            op["fx"], op["fy"] = float(rs.uniform(0.05, 0.95)), float(rs.uniform(0.05, 0.95))
+        elif name == "set_quantize_mode":
+            qmode = op["mode"] = "stream" if qmode != "stream" else str(rs.choice(["stream", "tile", "auto"]))
+            op["hs"] = int(rs.choice(SPARSE_HS))
+        elif name == "set_pipeline_depth":
+            op["depth"] = int(rs.choice([1, 2, 4]))
+        elif name == "set_graph_mode":
+            op["mode"] = int(GRAPH_MODES[int(rs.randint(3))])
+        elif name == "stall":
+            op["cycles"] = int(rs.choice([1_000_000, 10_000_000]))
+        elif name == "clobber_inputs":
+            # only buffers of synchronised calls: a checkpoint stands right in front
+            if ops[-1]["op"] != "checkpoint":
+                ops.append({"op": "checkpoint"})
+                if len(ops) >= steps:
+                    break
+            since_sync = 0
+        if name == "checkpoint":
+            since_sync = 0
+        elif name != "clobber_inputs":
+            since_sync += 1
+        ops.append(op)
+    return T, ops[:steps]
+
+
+def padded_layout(frames, row_pad, frame_pad):
+    """the frames (equal shapes, uint8) in one host buffer of a caller's layout: `row_pad` bytes behind every row, `frame_pad`
+    bytes behind every frame (-1: a whole frame, which holds the inverted frame); all padding is 0xA5.
+    -> (buffer, row stride, frame stride)"""
+    rows, line = frames[0].shape[0], frames[0].size // frames[0].shape[0]
+    stride = line + row_pad
+    fb = rows * stride
+    fs = 2 * fb if frame_pad < 0 else fb + frame_pad
+    buf = np.full(len(frames) * fs, 0xA5, np.uint8)
+    for f, fr in enumerate(frames):
+        buf[f * fs: f * fs + fb].reshape(rows, stride)[:, :line] = fr.reshape(rows, line)
+        if frame_pad < 0:
+            buf[f * fs + fb: f * fs + 2 * fb].reshape(rows, stride)[:, :line] = 255 - fr.reshape(rows, line)
+    return buf, stride, fs
+
+
 def fmt(op):
     return op["op"] + "(" + ", ".join(f"{k}={v}" for k, v in op.items() if k != "op") + ")"
 
@@ -235,6 +403,8 @@ class Runner:
         self.d_masks = {k: torch.from_numpy(v).to(self.dev) for k, v in masks.items()}
         self.want_cache = {}
         self.n_unchecked = 0  # results not compared: the resident frame is not known after a host or banded batch
+        self.n_sparse_proven = 0  # profiled sparse-eligible calls that made the sparse path's three gradient launches
+        self.sparse_on = os.environ.get("SBM_SPARSE_GRADIENT", "1") != "0" and os.environ.get("SBM_SPARSE_STRIPS", "1") != "0"
         torch.cuda.synchronize()
 
     # -- oracle -----------------------------------------------------------------------------------------------------
@@ -268,11 +438,11 @@ class Runner:
         return self.want_cache[k]
 
     # -- one sequence ------------------------------------------------------------------------------------------------
-    def run(self, seed, index, steps, stop=None):
+    def run(self, seed, index, steps, stop=None, profile="default"):
         from shape_based_matching_amd.templates import MATCH_DTYPE
 
         torch, capi = self.torch, self.capi
-        T, ops = generate(seed, index, steps)
+        T, ops = generate(seed, index, steps, profile)
         if stop is not None:
             ops = ops[: stop + 1]
         self.T, self.L = T, len(T)
@@ -296,6 +466,9 @@ class Runner:
         blm = False           # the coarsest level's bit planes of `resident` are there (True), not (False), unknown (None)
         coarse = "auto"
         last_batch = None     # pending record of the last batch call on the current stream
+        qmode = "auto"        # the gradient kernel asked for (set_quantize_mode)
+        batch_res = []        # (geo, var, mask) of every frame of the resident pyramid; None: unknown; []: nothing built
+        handed = []           # device buffers of frames handed to device entry points (the sparse profile's clobber_inputs)
         pending = []          # enqueued device calls whose results are not checked yet
         log = []
         n_cmp = 0
@@ -307,7 +480,7 @@ class Runner:
             where = f"step {step}" if step == seen else f"step {step} (seen at step {seen})"
             raise Finding(f"sequence fuzzer: seed {seed}, sequence {index} (pyramid {T}), {where}: {msg}\n"
                           + "\n".join(f"  {i:3d} {l}" for i, l in enumerate(log))
-                          + "\nreplay: " + replay_command(seed, index, steps, seen))
+                          + "\nreplay: " + replay_command(seed, index, steps, seen, profile))
 
         def cmp(step, what, got, want):
             nonlocal n_cmp
@@ -347,6 +520,37 @@ class Runner:
                 return
             fail(step, f"{what}: succeeded where the library must refuse with {code}")
 
+        def profiled(step, op, n_calls, wait=None):
+            """behind a call that ran under set_profiling: a sparse-eligible call made the sparse path's three gradient launches
+            (source pass, level 1, the flagged items), n_calls times for the sub-batches of a host batch"""
+            if wait is not None:
+                wait.synchronize()
+            n_q = sum(1 for n, _ in ctx.timings() if n == "k_quantize")
+            ctx.set_profiling(False)
+            if self.sparse_on and sparse_eligible(T, qmode, op):
+                if n_q != 3 * n_calls:
+                    fail(step, f"{op['op']}: {n_q} gradient launches, the sparse path makes {3 * n_calls}")
+                self.n_sparse_proven += 1
+
+        def laid_out(geo, variants, row_pad, frame_pad):
+            """the frames in a fresh device buffer of the caller's layout: `row_pad` bytes behind every row, `frame_pad` bytes
+            behind every frame (-1: a whole frame, which holds the inverted frame); all padding is 0xA5.  -> buffer, row
+            stride, frame stride"""
+            rows, cols, ch = ALL_GEOS[geo]
+            line = cols * ch
+            stride = line + row_pad
+            fb = rows * stride
+            fs = 2 * fb if frame_pad < 0 else fb + frame_pad
+            with torch.cuda.stream(streams[si]):
+                buf = torch.full((len(variants) * fs,), 0xA5, dtype=torch.uint8, device=self.dev)
+                for f, v in enumerate(variants):
+                    src = self.d_frames[geo, v].view(rows, line)
+                    buf[f * fs: f * fs + fb].view(rows, stride)[:, :line].copy_(src)
+                    if frame_pad < 0:
+                        buf[f * fs + fb: f * fs + 2 * fb].view(rows, stride)[:, :line].copy_(torch.bitwise_not(src))
+            handed.append(buf)
+            return buf, stride, fs
+
         def slot(n_frames):
             with torch.cuda.stream(streams[si]):
                 out = torch.empty(n_frames * CAP * self.rec, dtype=torch.uint8, device=self.dev)
@@ -368,6 +572,13 @@ class Runner:
                 elif name == "switch_stream":
                     si ^= 1
                     last_batch = None
+                elif name == "clobber_inputs":
+                    # every call that read these buffers was synchronised by the checkpoint in front
+                    assert not pending
+                    with torch.cuda.stream(s):
+                        for t in handed:
+                            t.fill_(0xFF)
+                    handed.clear()
                 elif name == "set_graph_mode":
                     ctx.set_graph_mode({-1: None, 0: False, 1: True}[op["mode"]])
                 elif name == "set_pipeline_depth":
@@ -381,6 +592,7 @@ class Runner:
                     ctx.set_refine_order(op["order"])
                 elif name == "set_quantize_mode":
                     ctx.set_quantize_mode(op["mode"], op["hs"])
+                    qmode = op["mode"]
                 elif name == "upload_templates":
                     self.set_id, self.ts = op["set"], self.sets[op["set"]]
                     ctx.upload_templates(self.ts)
@@ -403,22 +615,32 @@ class Runner:
                     self.active = list(range(self.ts.n_templates))
                 elif name in ("match", "match_device"):
                     fk = (op["geo"], op["var"], op["mask"])
-                    rows, cols, ch = GEOS[op["geo"]]
+                    rows, cols, ch = ALL_GEOS[op["geo"]]
+                    if op.get("profiled"):
+                        ctx.set_profiling(True)
                     if name == "match":
                         got = ctx.match(self.frames[op["geo"], op["var"]], op["thr"], mask=self.masks[op["geo"]] if op["mask"] else None)
                         pending.append({"step": step, "what": name, "lists": [got], "want": [self.want(fk, op["thr"])]})
                     else:
                         out, cnt = slot(1)
-                        ctx.match_device(self.d_frames[op["geo"], op["var"]].data_ptr(), rows, cols, cols * ch, ch, op["thr"], out.data_ptr(),
+                        d_img, stride = self.d_frames[op["geo"], op["var"]], cols * ch
+                        if "row_pad" in op:
+                            d_img, stride, _ = laid_out(op["geo"], [op["var"]], op["row_pad"], 0)
+                        ctx.match_device(d_img.data_ptr(), rows, cols, stride, ch, op["thr"], out.data_ptr(),
                                          CAP, cnt.data_ptr(), stream=sp,
                                          d_mask=self.d_masks[op["geo"]].data_ptr() if op["mask"] else 0)
-                        pending.append({"step": step, "what": name, "out": out, "cnt": cnt, "want": [self.want(fk, op["thr"])]})
+                        pending.append({"step": step, "what": name, "out": out, "cnt": cnt, "want": [self.want(fk, op["thr"])], "keep": d_img})
+                    if op.get("profiled"):
+                        profiled(step, op, 1, None if name == "match" else s)
                     resident = fk
+                    batch_res = [fk]
                     blm = (op["thr"] >= 0 and coarse in ("auto", "bits")) if self.active else None
                 elif name in ("match_batch_device", "match_banded", "match_batch_host"):
-                    rows, cols, ch = GEOS[op["geo"]]
+                    rows, cols, ch = ALL_GEOS[op["geo"]]
                     B = len(op["vars"])
                     wants = [self.want((op["geo"], v, op["mask"]), op["thr"]) for v in op["vars"]]
+                    if op.get("profiled"):
+                        ctx.set_profiling(True)
                     if name == "match_batch_host":
                         stack = np.stack([self.frames[op["geo"], v] for v in op["vars"]])
                         if op["pinned"]:
@@ -427,27 +649,37 @@ class Runner:
                         lists = ctx.match_batch_host(list(stack), op["thr"], cap=CAP, sub_batch=op["sub_batch"],
                                                      mask=self.masks[op["geo"]] if op["mask"] else None, split=op["split"])
                         pending.append({"step": step, "what": name, "lists": lists, "want": wants})
-                        resident, blm = "unknown", None  # (which sub-batch's frame stays resident is not part of the ABI)
+                        if op.get("profiled"):
+                            sub = max(1, min(op["sub_batch"], B))
+                            profiled(step, op, -(-B // sub))
+                        resident, blm, batch_res = "unknown", None, None  # (which sub-batch's frame stays resident is not part of the ABI)
                     else:
-                        with torch.cuda.stream(s):
-                            d_imgs = torch.stack([self.d_frames[op["geo"], v] for v in op["vars"]])
+                        if "row_pad" in op:
+                            d_imgs, stride, fs = laid_out(op["geo"], op["vars"], op["row_pad"], op["frame_pad"])
+                        else:
+                            with torch.cuda.stream(s):
+                                d_imgs = torch.stack([self.d_frames[op["geo"], v] for v in op["vars"]])
+                            stride, fs = cols * ch, rows * cols * ch
                         dm = self.d_masks[op["geo"]].data_ptr() if op["mask"] else 0
                         if name == "match_batch_device":
                             out, cnt = slot(B)
-                            ctx.match_batch_device(d_imgs.data_ptr(), rows * cols * ch, B, rows, cols, cols * ch, ch, op["thr"], out.data_ptr(),
+                            ctx.match_batch_device(d_imgs.data_ptr(), fs, B, rows, cols, stride, ch, op["thr"], out.data_ptr(),
                                                    CAP, cnt.data_ptr(), stream=sp, d_mask=dm)
                             p = {"step": step, "what": name, "out": out, "cnt": cnt, "want": wants, "keep": d_imgs}
                             resident = (op["geo"], op["vars"][0], op["mask"])
+                            batch_res = [(op["geo"], v, op["mask"]) for v in op["vars"]]
+                            if op.get("profiled"):
+                                profiled(step, op, 1, s)
                             blm = (op["thr"] >= 0 and coarse in ("auto", "bits")) if self.active else None
                         else:
                             hdr = (8 * B + 15) // 16 * 16
                             with torch.cuda.stream(s):
                                 buf = torch.full((hdr + B * CAP * self.rec,), 0xff, dtype=torch.uint8, device=self.dev)
-                            ctx.match_batch_device_banded(d_imgs.data_ptr(), rows * cols * ch, B, rows, cols, cols * ch, ch, op["thr"],
+                            ctx.match_batch_device_banded(d_imgs.data_ptr(), fs, B, rows, cols, stride, ch, op["thr"],
                                                           buf.data_ptr(), CAP, n_bands=op["n_bands"], stream=sp, d_mask=dm)
                             p = {"step": step, "what": name, "out": buf[hdr:], "cnt": buf[: 8 * B].view(torch.int32), "want": wants,
                                  "keep": d_imgs}
-                            resident, blm = "unknown", None  # (the banded build's resident frame is not part of the ABI either)
+                            resident, blm, batch_res = "unknown", None, None  # (the banded build's resident frame is not part of the ABI either)
                         pending.append(p)
                         last_batch = {"p": p, "B": B, "ts": self.ts}
                 elif name in ("match_templates", "match_templates_device"):
@@ -493,7 +725,20 @@ class Runner:
                         p = self.pyr(T, *fk)
                         for l in range(self.L):
                             ctx.set_quantized(l, p.quantized(l))
-                    resident, blm = fk, False
+                    resident, blm, batch_res = fk, False, [fk]
+                elif name == "get_quantized_frame":
+                    if batch_res == []:
+                        expect_refusal(step, name, lambda: ctx.get_quantized_frame(op["level"], op["frame"]), -4)
+                        continue
+                    got = ctx.get_quantized_frame(op["level"], op["frame"])
+                    if batch_res is None:
+                        self.n_unchecked += 1
+                        continue
+                    want = self.pyr(T, *batch_res[op["frame"]]).quantized(op["level"])
+                    if got.shape != want.shape or not np.array_equal(got, want):
+                        bad = int(np.count_nonzero(got != want)) if got.shape == want.shape else -1
+                        fail(step, f"{name}: differs from the oracle in {bad} elements (shape {got.shape} vs {want.shape})")
+                    n_cmp += 1
                 elif name in READ_OPS:
                     if resident is None:
                         fn = {"get_quantized": lambda: ctx.get_quantized(op["level"]),
@@ -570,7 +815,7 @@ def setup():
     img = np.load(os.path.join(ROOT, "tests", "golden", "case1_test_bgr.npz"))["bgr"]
     frames, masks = {}, {}
     offs = [(40, 60), (100, 180), (0, 0)]
-    for g, (rows, cols, ch) in GEOS.items():
+    for g, (rows, cols, ch) in ALL_GEOS.items():
         h, w = min(rows, img.shape[0]), min(cols, img.shape[1])
         for v in range(N_VARIANTS):
             if v < 3:
@@ -585,32 +830,38 @@ def setup():
     return Runner(O, capi, torch, frames, masks, all_ts, {})
 
 
-def run(n_sequences, seed, steps=25, verbose=True, only=None, stop=None):
-    """n_sequences sequences of `steps` operations, one context each; returns the number of matches compared"""
+LAST_RUN = {}  # what the last run() counted, beside the matches it returns
+
+
+def run(n_sequences, seed, steps=25, verbose=True, only=None, stop=None, profile="default"):
+    """n_sequences sequences of `steps` operations of the profile, one context each; returns the number of matches compared"""
     runner = setup()
     t0 = time.time()
     n = 0
-    runner.n_unchecked = 0
+    runner.n_unchecked = runner.n_sparse_proven = 0
     idx = [only] if only is not None else range(n_sequences)
     try:
         for i in idx:
-            c = runner.run(seed, i, steps, stop)
+            c = runner.run(seed, i, steps, stop, profile)
             n += c
             if verbose:
-                print(f"ok sequence {i} pyramid {generate(seed, i, steps)[0]}: {c} compared ({time.time() - t0:.0f} s)", flush=True)
+                print(f"ok sequence {i} pyramid {generate(seed, i, steps, profile)[0]}: {c} compared ({time.time() - t0:.0f} s)", flush=True)
     finally:
         for p in runner.pyr_cache.values():
             p.free()
         runner.pyr_cache.clear()
+    LAST_RUN.update(compared=n, unchecked=runner.n_unchecked, sparse_proven=runner.n_sparse_proven, sparse_on=runner.sparse_on)
     if verbose:
-        print(f"{len(idx)} sequences x {steps} steps, seed {seed}: {n} matches compared, {runner.n_unchecked} results unchecked "
-              f"(resident frame unknown after a host or banded batch), {time.time() - t0:.0f} s", flush=True)
+        print(f"{len(idx)} sequences x {steps} steps, seed {seed}, profile {profile}: {n} matches compared, {runner.n_unchecked} results unchecked "
+              f"(resident frame unknown after a host or banded batch), {runner.n_sparse_proven} profiled calls on the sparse path, "
+              f"{time.time() - t0:.0f} s", flush=True)
     return n
 
 
-def replay_command(seed, index, steps, stop):
-    """the command line that replays sequence `index` of `seed` up to and including step `stop`"""
-    return f"python tools/fuzz_sequence.py 1 {seed} --only {index} --steps {steps} --stop {stop}"
+def replay_command(seed, index, steps, stop, profile="default"):
+    """the command line that replays sequence `index` of `seed` (of the profile) up to and including step `stop`"""
+    return (f"python tools/fuzz_sequence.py 1 {seed} --only {index} --steps {steps} --stop {stop}"
+            + (f" --profile {profile}" if profile != "default" else ""))
 
 
 def parse_args(argv):
@@ -620,9 +871,10 @@ def parse_args(argv):
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--stop", type=int, default=None)
+    ap.add_argument("--profile", choices=PROFILES, default="default")
     return ap.parse_args(argv)
 
 
 if __name__ == "__main__":
     a = parse_args(sys.argv[1:])
-    run(a.n, a.seed, a.steps, only=a.only, stop=a.stop)
+    run(a.n, a.seed, a.steps, only=a.only, stop=a.stop, profile=a.profile)
