@@ -167,8 +167,10 @@ int sbm_match_device(sbm_ctx* ctx, const void* d_img, int32_t rows, int32_t cols
  * the per-launch cost is shared by n_frames frames.  Results of frame f: records at d_out + f * cap,
  * {n_matches, overflow} at d_counts + 2 * f (int32); a result mirror (sbm_set_result_mirror) must hold
  * n_frames * cap records and n_frames * 2 int32, laid out the same way.  The mask, if any, is shared by
- * the frames (one mask per frame: sbm_match_batch_device_masked).  Needs the register-only linear-memory kernel: T in {4, 8}, level widths multiples of 16.
- * Each frame's list is what sbm_match_device returns for that frame alone. */
+ * the frames (one mask per frame: sbm_match_batch_device_masked).  Takes every geometry sbm_match_device takes with strides up to 16: T in {4, 8} on
+ * level widths that are multiples of 16 through the register-only linear-memory kernel, any other stride or width
+ * through the batched any-stride one (spread bytes instead of strips and bit strips).  A stride above 16:
+ * SBM_ERR_INVALID for more than one frame.  Each frame's list is what sbm_match_device returns for that frame alone. */
 int sbm_match_batch_device(sbm_ctx* ctx, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows,
                            int32_t cols, int32_t stride, int32_t channels, const void* d_mask, float threshold,
                            void* d_out, int64_t cap, void* d_counts, void* stream);

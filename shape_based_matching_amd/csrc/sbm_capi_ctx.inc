@@ -688,6 +688,16 @@ bool all_rows_ok(const sbm_ctx* c)
     return true;
 }
 
+// A batch of frames on this pyramid takes the batched any-stride builder k_build_lm_any (sbm_lm_any.h): some level is off
+// the one-launch builder's grid, and every stride is one that kernel's LDS tiles are sized for
+bool any_batch_ok(const sbm_ctx* c)
+{
+    if (all_rows_ok(c)) return false;
+    for (int l = 0; l < c->L; ++l)
+        if (c->cfg.T[l] > LMA_MAX_T) return false;
+    return true;
+}
+
 // what the form of every level's linear memories follows from (sbm_level_forms.h)
 PlanInputs plan_inputs(const sbm_ctx* c)
 {
@@ -942,6 +952,7 @@ PlanInputs call_plan_inputs(const sbm_ctx* c, const uint8_t* mask, int stride0, 
                     quantize_stream_rows(c, rows, cols, ch, frames, false, fs, cols * ch) != 0;
     pin.l0_mask = mask != nullptr;
     pin.banded = bands != nullptr || level0_done;
+    pin.any_batch = frames > 1 && any_batch_ok(c);
     return pin;
 }
 
@@ -949,6 +960,40 @@ PlanInputs call_plan_inputs(const sbm_ctx* c, const uint8_t* mask, int stride0, 
 bool plans_sparse_gradient(const sbm_ctx* c, const uint8_t* mask, int stride0, int frames, int64_t img0_fs, const Bands* bands, bool level0_done)
 {
     return plan_build(call_plan_inputs(c, mask, stride0, frames, img0_fs, bands, level0_done), all_rows_ok(c), true).sparse_gradient;
+}
+
+// Every level of every frame of a batch in the forms of `plan` (LM_SPREAD or LM_PLANES8 per level), in one launch of
+// k_build_lm_any: block ranges per level, coarsest first as in the one-launch builder, the frame as grid.y.  reset_count != null:
+// the launch also zeroes the per-frame counters and the caller's counts (counters_fresh).
+int launch_lm_any(sbm_ctx* c, hipStream_t s, const BuildPlan& plan, int frames, int32_t* reset_count)
+{
+    LmaArgs a;
+    memset(&a, 0, sizeof a);
+    int64_t blocks = 0;
+    int smem = 0;
+    for (int l = c->L - 1; l >= 0; --l) {
+        const int T = c->cfg.T[l], W = c->cols[l] / T, H = c->rows[l] / T;
+        const LmForm f = plan.form[l];
+        if (T > LMA_MAX_T || (f != LM_SPREAD && f != LM_PLANES8) || (f == LM_SPREAD && !c->d_lmc[l].p))
+            return fail(SBM_ERR_STATE, "level %d (T = %d, form %d) is not one the batched any-stride builder makes", l, T, (int)f);
+        const LmaShape sh = lma_shape(T);
+        const int64_t stride = c->lm_stride[l];
+        a.lv[a.n_levels] = LmaLevel{c->d_quant[l].as<uint8_t>(), f == LM_SPREAD ? c->d_lmc[l].as<uint8_t>() : c->d_lm[l].as<uint8_t>(), stride,
+                                    (int64_t)c->rows[l] * c->cols[l], (f == LM_SPREAD ? 1 : 8) * stride, c->rows[l], c->cols[l], W, H, T,
+                                    sh.cells, sh.grows, (int32_t)f};
+        a.block_begin[a.n_levels++] = (int32_t)blocks;
+        blocks += lma_level_blocks(W, H, sh);
+        smem = std::max(smem, lma_lds_bytes(T, sh.cells, sh.grows));
+    }
+    if (blocks >= (int64_t)INT32_MAX) return fail(SBM_ERR_INVALID, "pyramid too large for one linear-memory launch");
+    if (reset_count) {
+        a.counters = c->d_counters.as<int32_t>();
+        a.out_count = reset_count;
+        c->counters_fresh = true;
+    }
+    SBM_LAUNCH(c, "k_build_lm", k_build_lm_any, dim3((unsigned)blocks, frames), dim3(LMA_THREADS), (size_t)smem, s, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0,
@@ -965,7 +1010,16 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
     // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch, and its T = 4 strip levels as bit strips.
     // The stage entry points keep the 8 response planes there (the bit planes are then packed from them on demand).
-    const BuildPlan plan = plan_build(call_plan_inputs(c, d_mask0, stride0, frames, img0_fs, bands, level0_gradient_done), all_rows, reset_count != nullptr);
+    const PlanInputs pin = call_plan_inputs(c, d_mask0, stride0, frames, img0_fs, bands, level0_gradient_done);
+    const BuildPlan plan = plan_build(pin, all_rows, reset_count != nullptr);
+    // off the one-launch builder's grid a batch takes k_build_lm_any, which is sized for strides up to LMA_MAX_T
+    if (!all_rows && frames > 1 && !pin.any_batch) {
+        for (int l = 0; l < c->L; ++l)
+            if (c->cfg.T[l] > LMA_MAX_T)
+                return fail(SBM_ERR_INVALID, "batched match: level %d has T = %d, and a pyramid with a stride other than 4 or 8 or a level that is not "
+                            "16-column-aligned batches up to T = %d only", l, c->cfg.T[l], LMA_MAX_T);
+        return fail(SBM_ERR_STATE, "batched match: no linear-memory builder for this pyramid");
+    }
     // (the linear memories of a level right behind its gradient launch -- two launches per batch, the orientation map still
     // in the caches -- measure the same as one launch for all levels at the end: tools/r03_lm_early.sh)
     for (int l = 0; l < c->L; ++l) {
@@ -988,8 +1042,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
             }
             if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, mask_fs, frames, img_fs, lo, hi)) return e;
         }
-        if (!all_rows && frames > 1) return fail(SBM_ERR_INVALID, "batched match needs T in {4, 8} and 16-column-aligned levels");
-        if (!all_rows)
+        if (!all_rows && !pin.any_batch)
             if (int e = launch_build_lm(c, s, l)) return e;
     }
     if (bands && bands->between)
@@ -1019,13 +1072,15 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
         }
         SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
-        if (plan.pack_spread) { // the spread plane is row-major, the flat order of the byte planes
-            const int l = c->L - 1;
-            const int n_dwords = (int)(((int64_t)c->rows[l] * c->cols[l] + 31) / 32);
-            SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
-                       c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
-            HIP_TRY(hipGetLastError());
-        }
+    } else if (pin.any_batch) {
+        if (int e = launch_lm_any(c, s, plan, frames, reset_count)) return e;
+    }
+    if (plan.pack_spread) { // the spread plane is row-major, the flat order of the byte planes
+        const int l = c->L - 1;
+        const int n_dwords = (int)(((int64_t)c->rows[l] * c->cols[l] + 31) / 32);
+        SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
+                   c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
+        HIP_TRY(hipGetLastError());
     }
     record_build(c->forms, c->L, plan);
     c->levels_valid = c->L;
@@ -1565,9 +1620,12 @@ int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
 
 // what a match entry point leaves resident, for the calls that replay its launches as a captured graph
 // sparse_grad: the captured call made level 0's map sparsely (its graph key says so)
-void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad)
+// any_batch: the captured call was a batch through k_build_lm_any (PlanInputs::any_batch)
+void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch)
 {
-    record_match(c->forms, plan_inputs(c), one_launch, c->h_active.empty());
+    PlanInputs pin = plan_inputs(c);
+    pin.any_batch = any_batch;
+    record_match(c->forms, pin, one_launch, c->h_active.empty());
     c->levels_valid = c->L;
     c->map0_whole = !sparse_grad;
     if (sparse_grad) c->src0_ch = c->channels;
@@ -1650,10 +1708,10 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             }))
             return e;
         if (launched) {
-            // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is captured only
-            // where the one-launch builder takes every level; the template loop builds nothing
+            // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is the one-launch
+            // builder's where that takes every level, else the batched any-stride builder's; the template loop builds nothing
             if (kind >= 0) {
-                record_match(c, kind > 0, key.sparse_grad);
+                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c));
                 c->last_frames = m.frames;
             }
             return 0;

@@ -427,8 +427,9 @@ static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_
                 masks ? (int64_t)mask_bytes : 0};
     if (int e = begin_host_match(c, m, c->citems_dirty)) return e;
     // geometries the one-launch linear-memory builder does not take (level widths that are not multiples of 16, other
-    // strides): one frame per "sub-batch" through the generic kernels -- the uploads still overlap the kernels
-    if (!all_rows_ok(c)) sub = 1;
+    // strides) batch through the any-stride builder (k_build_lm_any) up to T = 16; a pyramid with a larger stride goes one
+    // frame per "sub-batch" through the generic kernels -- the uploads still overlap the kernels
+    if (!all_rows_ok(c) && !any_batch_ok(c)) sub = 1;
     if (int e = ensure_copy_stream(c)) return e;
     for (int i = 0; i < 2; ++i)
         if (int e = c->d_in[i].ensure((size_t)sub * frame_bytes)) return e;

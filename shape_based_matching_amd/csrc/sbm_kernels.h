@@ -8,6 +8,7 @@
 //   k_pyrdown             cv::pyrDown in ColorGradientPyramid::pyrDown line2Dup.cpp:431-433
 //   k_resize_mask         resize(mask, INTER_NEAREST)                  line2Dup.cpp:439
 //   k_build_lm            spread + computeResponseMaps + linearize     line2Dup.cpp:616-630, 637-747, 749-777
+//   k_build_lm_any        the same, every level of every frame of a batch, any stride up to 16 (sbm_lm_any.h)
 //   k_spread/k_response/k_linearize   the same three, unfused (stage entry points)
 //   k_prep_features       accessLinearMemory address arithmetic        line2Dup.cpp:782-805
 //   k_similarity_coarse   similarity / similarity_64 + candidate scan  line2Dup.cpp:807-858, 924-984, 1199-1216
@@ -19,5 +20,6 @@
 #include "sbm_common.h"
 #include "sbm_quantize_tile.h"
 #include "sbm_lm_kernels.h"
+#include "sbm_lm_any.h"
 #include "sbm_similarity_kernels.h"
 #include "sbm_coarse_bits.h"

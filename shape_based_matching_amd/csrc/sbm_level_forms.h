@@ -95,6 +95,11 @@ struct PlanInputs {
     // mask (a level-0 mask is the caller's memory too, gone when a later reader asks for the whole map), it is banded
     bool sparse_gradient = false;
     bool l0_stream = false, l0_mask = false, banded = false;
+    // A batch of frames on a pyramid that the one-launch builder does not take (one_launch false: a stride other than 4 or 8,
+    // a level whose width is no multiple of 16), strides up to 16: the batched any-stride builder k_build_lm_any
+    // (sbm_lm_any.h) makes every level of every frame.  What one call says; off for a single frame, which keeps the generic
+    // single-frame builder and its 8 response planes.
+    bool any_batch = false;
     int W(int l) const { return cols[l] / T[l]; }
     int H(int l) const { return rows[l] / T[l]; }
 };
@@ -118,7 +123,11 @@ inline bool local_bits_wanted(const PlanInputs& p, int l)
 
 // In which form a build of the pyramid makes every level.
 //   one_launch   every level takes the one-launch builder k_build_lm_rows (T in {4, 8}, 16-column-aligned rows); else -- and
-//                in the captured single-frame graph -- the generic builder makes the 8 response planes of every level
+//                in the captured single-frame graph -- the generic builder makes the 8 response planes of every level,
+//                unless the call is a batch (PlanInputs::any_batch): then k_build_lm_any makes, in the forms the batched
+//                readers take at any stride and width, one plane of spread bytes of a refinement level, the same of the
+//                coarsest level of a coarse pass on bit planes (which k_pack_bitplanes_spread packs), else the 8 planes.
+//                No strips, no bit strips, no sparse level 0 and no fused bit planes: those need T = 4 and aligned grids.
 //   match_entry  a match entry point (it has set the threshold, and its launch resets the counters): refinement levels may
 //                become bit strips, the coarsest level its bit planes.  Stage entry points keep to bytes.
 struct BuildPlan {
@@ -134,6 +143,13 @@ inline BuildPlan plan_build(const PlanInputs& p, bool one_launch, bool match_ent
     b.pack_spread = false;
     b.sparse_gradient = false;
     for (int l = 0; l < LF_MAX_LEVELS; ++l) b.form[l] = l < p.L ? LM_PLANES8 : LM_NONE;
+    if (!one_launch && p.any_batch) {
+        for (int l = 0; l < p.L - 1; ++l)
+            if (!p.full_lm && p.has_spread[l]) b.form[l] = LM_SPREAD;
+        const int lc = p.L - 1;
+        if (match_entry && coarse_on_bits(p) && p.fused_bits && !p.full_lm && p.has_spread[lc]) b.form[lc] = LM_SPREAD, b.pack_spread = true;
+        return b;
+    }
     if (!one_launch) return b;
     // refinement-only levels: ONE plane of spread bytes, strip-interleaved when the grid width allows it (the refinement
     // pass reads 16 x 16 cells per feature: 2 - 4 cache lines instead of 16), or bit strips

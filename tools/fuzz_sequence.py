@@ -35,7 +35,14 @@ where a frame-taking match call makes level 0 only where its coarse candidates r
 two geometries with a cut tile column, batches that grow and shrink, readers of level 0 behind such a call -- also after
 clobber_inputs overwrote the caller's device buffers -- and get_quantized_frame of every frame of the last device batch.
 
-usage: python tools/fuzz_sequence.py [n_sequences] [seed] [--steps S] [--only I] [--stop K] [--profile default|sparse]
+A third profile, "anygeo" (_generate_anygeo), draws the pyramids and frame geometries that the one-launch linear-memory builder
+does not take -- strides 1, 2, 5 beside 4 and 8, level widths that are no multiple of 16, an odd width -- where a batch of
+frames goes through the batched any-stride builder (csrc/sbm_lm_any.h): device and host batches and device NMS at every one
+of them, geometry changes to and from an aligned frame, and the maps and coarse bit planes of any frame of the last device
+batch.  Its templates are cut from the orientation maps of one of its own scene frames (the case1 templates are larger than
+most of its frames).
+
+usage: python tools/fuzz_sequence.py [n_sequences] [seed] [--steps S] [--only I] [--stop K] [--profile default|sparse|anygeo]
        (--only I: sequence I alone; --stop K: its first K + 1 steps)"""
 import argparse
 import os
@@ -57,8 +64,17 @@ BATCH_GEOS = ("A", "B", "G")
 # "P": 3.5 x 4.5 tiles, a 96-column last strip packed two frames per wave; "Q": gray, 4 x 5.5 tiles.  Kept apart from GEOS: the
 # default profile draws from tuple(GEOS), and its output must not change.
 SPARSE_GEOS = {"A": GEOS["A"], "B": GEOS["B"], "G": GEOS["G"], "P": (448, 576, 3), "Q": (512, 704, 1)}
-ALL_GEOS = {**GEOS, **SPARSE_GEOS}
-PROFILES = ("default", "sparse")
+# The anygeo profile's pyramids and geometries: per pyramid the frames that meet the reference's three conditions at every
+# level (rows % T == 0, cols % T == 0, rows * cols % 16 == 0).  All but "c" under (4, 8) and (2, 4) have a level off the
+# one-launch builder's grid; "c" is there for the change to an aligned geometry and back.  The first geometry of a pyramid
+# is the one its templates are cut from.
+ANYGEO_ONLY_GEOS = {"a": (208, 272, 3), "b": (208, 272, 1), "c": (240, 320, 3), "d": (200, 264, 1), "e": (384, 416, 3), "f": (256, 288, 3),
+                    "g": (208, 211, 1)}
+ANYGEO_PYRAMIDS = [(4, 8), (2, 4), (5, 8), (4, 8, 8), (1,)]
+ANYGEO_GEOS = {(4, 8): ("a", "b", "c", "e", "f", "O"), (2, 4): ("d", "a", "b", "c", "f", "O"), (5, 8): ("c",), (4, 8, 8): ("e", "f", "O"),
+               (1,): ("g", "a", "b", "d")}
+ALL_GEOS = {**GEOS, **SPARSE_GEOS, **ANYGEO_ONLY_GEOS}
+PROFILES = ("default", "sparse", "anygeo")
 ROW_PADS = (0, 13, 64)        # bytes behind every row of a device frame
 FRAME_PADS = (0, 1000, -1)    # bytes behind every frame of a device batch; -1: one whole frame (the inverted frame lies there)
 SPARSE_HS = (8, 18, 32)
@@ -84,6 +100,11 @@ _SPARSE_WEIGHTS = {"match_batch_device": 10, "match_device": 5, "match": 4, "mat
                    "set_pipeline_depth": 1, "set_quantize_mode": 1, "checkpoint": 2, "clobber_inputs": 2, "stall": 1}
 _SPARSE_FOLLOWERS = ("get_quantized", "get_quantized_frame", "get_quantized_frame", "get_linear_memories", "match_templates",
                      "match_templates_device", "similarity_local", "set_quantized")
+_ANYGEO_WEIGHTS = {"match": 2, "match_device": 4, "match_batch_device": 10, "match_batch_host": 5, "match_templates": 2,
+                   "match_templates_device": 3, "nms": 3, "build_pyramid": 1, "set_quantized": 1, "get_quantized": 1, "get_quantized_frame": 4,
+                   "get_linear_memories": 3, "get_coarse_bitplanes": 4, "similarity": 1, "similarity_local": 2, "upload_templates": 1,
+                   "select_range": 1, "select_classes": 1, "select_all": 1, "set_coarse_mode": 2, "set_quantize_mode": 1,
+                   "set_pipeline_depth": 1, "set_graph_mode": 3, "checkpoint": 2, "stall": 1}
 TEMPLATE_OPS = ("upload_templates", "select_range", "select_classes", "select_templates", "select_empty", "select_all")
 MODE_OPS = ("set_coarse_mode", "set_refine_bits", "set_refine_order", "set_quantize_mode", "set_pipeline_depth", "set_graph_mode")
 SYNC_OPS = ("checkpoint", "switch_stream")
@@ -112,6 +133,8 @@ def generate(seed, index, steps, profile="default"):
     """(pyramid, [op dict]) of sequence `index` of `seed`: deterministic, no torch, no GPU"""
     if profile == "sparse":
         return _generate_sparse(seed, index, steps)
+    if profile == "anygeo":
+        return _generate_anygeo(seed, index, steps)
     if profile != "default":
         raise ValueError(f"profile {profile!r}: one of {PROFILES}")
     rs = np.random.RandomState(sequence_seed(seed, index))
@@ -344,6 +367,113 @@ def _generate_sparse(seed, index, steps):
     return T, ops[:steps]
 
 
+def _generate_anygeo(seed, index, steps):
+    """The anygeo profile: one of ANYGEO_PYRAMIDS, frames of ANYGEO_GEOS for it.  Device batches (padded caller layouts too),
+    host batches and device NMS at every geometry, no banded call (it refuses these geometries); behind a device batch often a
+    reader of what it left: the map or the coarse bit planes of any of its frames, linear memories, the template loop."""
+    rs = np.random.RandomState((sequence_seed(seed, index) ^ 0x0a9e0) % (1 << 31))
+    T = ANYGEO_PYRAMIDS[index % len(ANYGEO_PYRAMIDS)] if index < len(ANYGEO_PYRAMIDS) else ANYGEO_PYRAMIDS[int(rs.randint(len(ANYGEO_PYRAMIDS)))]
+    geos = ANYGEO_GEOS[T]
+    names = list(_ANYGEO_WEIGHTS)
+    p = np.array([_ANYGEO_WEIGHTS[n] for n in names], np.float64)
+    p /= p.sum()
+    n_set = SET_SIZES[0]
+    n_active = n_set
+    have_batch = False
+    last_B = 1
+    forced = []
+    since_sync = 0
+    followers = ("get_quantized_frame", "get_coarse_bitplanes", "get_coarse_bitplanes", "get_linear_memories", "match_templates",
+                 "match_templates_device", "similarity_local")
+    ops = [{"op": "set_graph_mode", "mode": int(GRAPH_MODES[int(rs.randint(3))])}]
+    if int(rs.randint(2)):
+        ops.append({"op": "set_pipeline_depth", "depth": int(rs.choice([2, 4]))})
+
+    def thr():
+        t = float(THRESHOLDS[int(rs.randint(len(THRESHOLDS)))])
+        return t if t > 0 or n_active <= 1 else float(THRESHOLDS[int(rs.randint(4))])
+
+    while len(ops) < steps:
+        if forced:
+            name = forced.pop(0)
+        else:
+            name = names[int(rs.choice(len(names), p=p))]
+            if since_sync >= 6 and name != "checkpoint" and rs.randint(3) == 0:
+                name = "checkpoint"
+        op = {"op": name}
+        if name in ("match", "match_device", "build_pyramid", "set_quantized"):
+            op["geo"], op["var"], op["mask"] = str(rs.choice(geos)), int(rs.randint(N_VARIANTS)), bool(rs.randint(5) == 0)
+            if name in ("match", "match_device"):
+                op["thr"] = thr()
+            if name == "match_device":
+                op["row_pad"] = int(rs.choice(ROW_PADS))
+            last_B = 1
+        elif name in ("match_batch_device", "match_batch_host"):
+            op["geo"], op["mask"] = str(rs.choice(geos)), bool(rs.randint(5) == 0)
+            B = int(rs.randint(1, 8 if name == "match_batch_device" else 6))
+            op["vars"] = [int(rs.randint(N_VARIANTS)) for _ in range(B)]
+            op["thr"] = thr()
+            if name == "match_batch_host":
+                op["sub_batch"] = int(rs.randint(1, 5))
+                op["split"] = bool(rs.randint(2))
+                op["pinned"] = bool(rs.randint(2))
+                last_B = 1
+            else:
+                op["row_pad"] = int(rs.choice(ROW_PADS))
+                op["frame_pad"] = int(rs.choice(FRAME_PADS))
+                have_batch = True
+                last_B = B
+                if rs.randint(5) < 3:
+                    forced.append(followers[int(rs.randint(len(followers)))])
+        elif name in ("match_templates", "match_templates_device"):
+            op["thr"] = thr()
+        elif name == "nms":
+            if not have_batch:
+                continue
+            op["score"] = float(rs.choice([0.0, 85.0, 95.0]))
+            op["nms"] = float(rs.choice([0.3, 0.5, 1.0]))
+        elif name in ("get_quantized", "get_linear_memories"):
+            op["level"] = int(rs.randint(len(T)))
+        elif name == "get_quantized_frame":
+            op["level"] = int(rs.randint(len(T)))
+            op["frame"] = int(rs.randint(last_B))
+        elif name == "get_coarse_bitplanes":
+            op["frame"] = int(rs.randint(last_B))
+        elif name == "similarity":
+            op["t"] = int(rs.randint(n_set))
+        elif name == "similarity_local":
+            op["level"] = int(rs.randint(len(T)))
+            op["t"] = int(rs.randint(n_set))
+            op["fx"], op["fy"] = float(rs.uniform(0.05, 0.95)), float(rs.uniform(0.05, 0.95))
+        elif name == "upload_templates":
+            op["set"] = int(rs.randint(2))
+            n_set = n_active = SET_SIZES[op["set"]]
+            have_batch = False  # device NMS sizes boxes by the templates uploaded now: only lists of this upload
+        elif name == "select_range":
+            op["count"] = int(rs.choice([1, 2, 3, 9, 20]))
+            op["first"] = int(rs.randint(0, n_set - op["count"] + 1))
+            n_active = op["count"]
+        elif name == "select_classes":
+            op["classes"] = [[0], [1], [0, 1]][int(rs.randint(3))]
+            n_active = sum((n_set + 1 - c) // 2 for c in op["classes"])
+        elif name == "select_all":
+            n_active = n_set
+        elif name == "set_coarse_mode":
+            op["mode"] = str(rs.choice(COARSE_MODES))
+        elif name == "set_quantize_mode":
+            op["mode"] = str(rs.choice(["auto", "tile", "stream"]))
+            op["hs"] = int(rs.choice([0, 8, 16]))
+        elif name == "set_pipeline_depth":
+            op["depth"] = int(rs.choice([1, 2, 4]))
+        elif name == "set_graph_mode":
+            op["mode"] = int(GRAPH_MODES[int(rs.randint(3))])
+        elif name == "stall":
+            op["cycles"] = int(rs.choice([1_000_000, 10_000_000]))
+        since_sync = 0 if name == "checkpoint" else since_sync + 1
+        ops.append(op)
+    return T, ops[:steps]
+
+
 def padded_layout(frames, row_pad, frame_pad):
     """the frames (equal shapes, uint8) in one host buffer of a caller's layout: `row_pad` bytes behind every row, `frame_pad`
     bytes behind every frame (-1: a whole frame, which holds the inverted frame); all padding is 0xA5.
@@ -388,6 +518,21 @@ def template_set(all_ts, which, T):
                            "pyramid_level": l, "features": feats})
             pyrs.append(lv)
         ts = from_pyramids(pyrs, "t")
+    n = ts.n_templates
+    return TemplateSet(ts.n_levels, ts.levels, ts.features, (np.arange(n) % 2).astype(np.int32), ts.template_id, ["a", "b"])
+
+
+def anygeo_template_set(O, frames, which, T):
+    """set 0 / set 1 of the anygeo profile: SET_SIZES templates cut from the orientation maps of the scene frame (variant 3) of
+    the pyramid's first geometry, so that they score 100 there and something between on every other frame; classes alternate"""
+    from shape_based_matching_amd import synth
+    from shape_based_matching_amd.templates import TemplateSet
+
+    L = len(T)
+    pyr = O.Pyramid.build(frames[ANYGEO_GEOS[tuple(T)][0], 3], list(T), 30.0)
+    qs = [pyr.quantized(l) for l in range(L)]
+    pyr.free()
+    ts, _ = synth.templates_from_maps(qs, [48, 24, 12][:L], 64 if L < 3 else 128, SET_SIZES[which], 11 + which)
     n = ts.n_templates
     return TemplateSet(ts.n_levels, ts.levels, ts.features, (np.arange(n) % 2).astype(np.int32), ts.template_id, ["a", "b"])
 
@@ -447,7 +592,10 @@ class Runner:
             ops = ops[: stop + 1]
         self.T, self.L = T, len(T)
         self.rec = MATCH_DTYPE.itemsize
-        self.sets = [template_set(self.all_ts, 0, T), template_set(self.all_ts, 1, T)]
+        if profile == "anygeo":
+            self.sets = [anygeo_template_set(self.O, self.frames, 0, T), anygeo_template_set(self.O, self.frames, 1, T)]
+        else:
+            self.sets = [template_set(self.all_ts, 0, T), template_set(self.all_ts, 1, T)]
         self.set_id, self.ts = 0, self.sets[0]
         self.active = list(range(self.ts.n_templates))
         self.want_cache = {}
@@ -464,6 +612,7 @@ class Runner:
         si = 0
         resident = None       # (geo, var, mask) of frame 0 of the resident pyramid, "unknown", or None (nothing built)
         blm = False           # the coarsest level's bit planes of `resident` are there (True), not (False), unknown (None)
+        blm_all = False       # ... and those of every frame of batch_res: the last pyramid was a device batch that made them
         coarse = "auto"
         last_batch = None     # pending record of the last batch call on the current stream
         qmode = "auto"        # the gradient kernel asked for (set_quantize_mode)
@@ -635,6 +784,7 @@ class Runner:
                     resident = fk
                     batch_res = [fk]
                     blm = (op["thr"] >= 0 and coarse in ("auto", "bits")) if self.active else None
+                    blm_all = False
                 elif name in ("match_batch_device", "match_banded", "match_batch_host"):
                     rows, cols, ch = ALL_GEOS[op["geo"]]
                     B = len(op["vars"])
@@ -653,6 +803,7 @@ class Runner:
                             sub = max(1, min(op["sub_batch"], B))
                             profiled(step, op, -(-B // sub))
                         resident, blm, batch_res = "unknown", None, None  # (which sub-batch's frame stays resident is not part of the ABI)
+                        blm_all = False
                     else:
                         if "row_pad" in op:
                             d_imgs, stride, fs = laid_out(op["geo"], op["vars"], op["row_pad"], op["frame_pad"])
@@ -671,6 +822,7 @@ class Runner:
                             if op.get("profiled"):
                                 profiled(step, op, 1, s)
                             blm = (op["thr"] >= 0 and coarse in ("auto", "bits")) if self.active else None
+                            blm_all = blm is True
                         else:
                             hdr = (8 * B + 15) // 16 * 16
                             with torch.cuda.stream(s):
@@ -680,6 +832,7 @@ class Runner:
                             p = {"step": step, "what": name, "out": buf[hdr:], "cnt": buf[: 8 * B].view(torch.int32), "want": wants,
                                  "keep": d_imgs}
                             resident, blm, batch_res = "unknown", None, None  # (the banded build's resident frame is not part of the ABI either)
+                            blm_all = False
                         pending.append(p)
                         last_batch = {"p": p, "B": B, "ts": self.ts}
                 elif name in ("match_templates", "match_templates_device"):
@@ -726,6 +879,7 @@ class Runner:
                         for l in range(self.L):
                             ctx.set_quantized(l, p.quantized(l))
                     resident, blm, batch_res = fk, False, [fk]
+                    blm_all = False
                 elif name == "get_quantized_frame":
                     if batch_res == []:
                         expect_refusal(step, name, lambda: ctx.get_quantized_frame(op["level"], op["frame"]), -4)
@@ -758,15 +912,17 @@ class Runner:
                         if blm is False:
                             expect_refusal(step, name, lambda: ctx.get_coarse_bitplanes(), -4)
                             continue
+                        # a frame behind the first only where the last pyramid was a device batch that made every frame's planes
+                        fr = op.get("frame", 0) if blm_all and batch_res and op.get("frame", 0) < len(batch_res) else 0
                         try:
-                            got = ctx.get_coarse_bitplanes()
+                            got = ctx.get_coarse_bitplanes(fr)
                         except capi.SbmError as e:
                             if blm is None and e.code == -4:
                                 continue
                             raise
                         from test_gpu_coarse_bits import packed
 
-                        want = p and packed(p.lm(lc))
+                        want = p and packed((self.pyr(T, *batch_res[fr]) if fr else p).lm(lc))
                     elif name == "similarity":
                         got = ctx.similarity(op["t"])
                         want = p and p.similarity(self.ts.levels[op["t"], lc], self.ts.features, lc)
@@ -818,7 +974,11 @@ def setup():
     for g, (rows, cols, ch) in ALL_GEOS.items():
         h, w = min(rows, img.shape[0]), min(cols, img.shape[1])
         for v in range(N_VARIANTS):
-            if v < 3:
+            if g in ANYGEO_ONLY_GEOS and v in (0, 1):
+                # the scene (variant 3, which the profile's templates are cut from) rolled: lists that differ from frame to frame
+                sc = synth.scene_bgr(1000 + rows + cols, rows, cols)
+                fr = np.roll(sc, 12, axis=1) if v == 0 else np.roll(np.roll(sc, 8, axis=0), -20, axis=1)
+            elif v < 3:
                 r0, c0 = min(offs[v][0], rows - h), min(offs[v][1], cols - w)
                 fr = synth.embed(img[:h, :w], rows, cols, r0, c0)
             else:
@@ -871,7 +1031,7 @@ def parse_args(argv):
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--stop", type=int, default=None)
-    ap.add_argument("--profile", choices=PROFILES, default="default")
+    ap.add_argument("--profile", choices=PROFILES, default="default")  # default | sparse | anygeo
     return ap.parse_args(argv)
 
 
