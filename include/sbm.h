@@ -389,6 +389,13 @@ int sbm_get_linear_memories(sbm_ctx* ctx, int32_t level, uint8_t* out_host, int6
  * out_host: 16 * lm_stride / 8 bytes.  Fails with SBM_ERR_STATE when the last call did not produce them (a threshold < 0,
  * or sbm_set_coarse_mode picked a byte kernel).  A parity-test accessor. */
 int sbm_get_coarse_bitplanes(sbm_ctx* ctx, int32_t frame, uint8_t* out_host, int64_t cap_bytes);
+/* Which kernel form the last coarse pass of this context ran (every form is timed as "k_similarity_coarse"):
+ * out = {kind, P, wide, dw}.  kind: 0 none launched yet, 1 the byte kernel with four waves per item, 2 the byte kernel
+ * with one wave per item, 3 the bit-plane kernel with one wave per item, 4 the bit-plane kernel with eight waves per
+ * item.  P: counter planes (7, 10 or 13; kinds 3 and 4), wide: 1 for the wide batch schedule, dw: dwords per lane (1 or
+ * 2; kind 3); 0 where they do not apply.  A call replayed from a captured graph reports the form it was captured with.
+ * Reads a host-side record: no device work, no synchronisation, no state change.  A parity-test accessor. */
+int sbm_get_coarse_form(sbm_ctx* ctx, int32_t out[4]);
 int sbm_level_dims(sbm_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols);
 
 /* Second half of match(): Detector::matchClass over the selected templates

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
     "sbm_match_batch_device_masked", "sbm_match_batch_host_begin_masked", "sbm_match_batch_host_masked", "sbm_get_quantized_frame",
+    "sbm_get_coarse_form",
 ]
 
 
@@ -181,6 +182,7 @@ def lib() -> C.CDLL:
     L.sbm_get_quantized.argtypes = [vp, i32, vp]
     L.sbm_get_linear_memories.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     L.sbm_get_coarse_bitplanes.argtypes = [vp, i32, vp, i64]
+    L.sbm_get_coarse_form.argtypes = [vp, vp]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
     L.sbm_quantized_orientations.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -639,6 +641,13 @@ class Context:
         out = np.empty((16, s.value // 8), np.uint8)
         _check(lib().sbm_get_coarse_bitplanes(self._h, frame, _p(out), out.nbytes))
         return out
+
+    def coarse_form(self) -> Tuple[int, int, int, int]:
+        """(kind, P, wide, dw) of the coarse kernel the last call launched: kind 0 none yet, 1 bytes with four waves per item,
+        2 bytes with one wave per item, 3 bit planes with one wave per item, 4 bit planes with eight waves per item"""
+        out = np.zeros(4, np.int32)
+        _check(lib().sbm_get_coarse_form(self._h, _p(out)))
+        return tuple(int(v) for v in out)
 
     def match_templates(self, threshold: float) -> np.ndarray:
         out = np.empty(self._cap, MATCH_DTYPE)

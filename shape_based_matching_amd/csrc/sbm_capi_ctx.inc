@@ -272,12 +272,18 @@ struct sbm_ctx {
         hipGraphExec_t exec;
         uint64_t last_use;
         bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
+        int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     int quantize_mode = 0, quantize_hs = 0; // sbm_set_quantize_mode
     int pipeline_depth = 1;                 // sbm_set_pipeline_depth: batches the caller keeps in flight on this GPU
     int local_order = tuning().local_order; // -1 by the planes' size, 0 per-frame slots, 2 one frame-major list (sbm_set_refine_order)
+    int32_t coarse_form[4] = {0, 0, 0, 0};  // {kind, P, wide, dw} of the coarse kernel enqueue_coarse last launched (sbm_get_coarse_form)
+    void note_coarse_form(int kind, int P, bool wide, int dw)
+    {
+        coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw;
+    }
     int coarse_mode = tuning().coarse;      // 0 auto (bit planes), 1 four waves per item, 2 one wave per item, 3 bit planes, 4 byte kernels by launch size (SBM_COARSE: A/B knob)
     // hipGraph replay of an entry point's launches (sbm_set_graph_mode): -1 auto (default) = the batch entry point and the
     // template-loop entry point replay a captured graph once the caller keeps several calls in flight
@@ -1306,13 +1312,14 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             if (bits_block) {
                 const int chunks1 = coarse_chunks(bits_max_npos, CB_POS);
 #define SBM_COARSE_BITS_BLOCK(P_)                                                                                                    \
+                c->note_coarse_form(4, P_, false, 0);                                                                                 \
                 SBM_LAUNCH(c, "k_similarity_coarse", (k_similarity_coarse_bits_block<P_>), dim3(chunks1, cnt, frames), dim3(512), 0, s,   \
                            c->d_blm.as<uint32_t>(), c->lm_stride[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(), c->d_soff.as<int32_t>(),   \
                            c->d_citems.as<CoarseItem>() + first, cnt, c->d_rawkeep.as<int32_t>(), c->d_class.as<int32_t>(),             \
                            c->d_tid.as<int32_t>(), c->d_cands.as<Cand>(), counters, (int)c->cand_cap, (int64_t)(2 * c->lm_stride[lc]) / 4)
-                if (max_nf < 128) SBM_COARSE_BITS_BLOCK(7);
-                else if (max_nf < 1024) SBM_COARSE_BITS_BLOCK(10);
-                else SBM_COARSE_BITS_BLOCK(13);
+                if (max_nf < 128) { SBM_COARSE_BITS_BLOCK(7); }
+                else if (max_nf < 1024) { SBM_COARSE_BITS_BLOCK(10); }
+                else { SBM_COARSE_BITS_BLOCK(13); }
 #undef SBM_COARSE_BITS_BLOCK
                 continue;
             }
@@ -1322,11 +1329,14 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
 #define SBM_COARSE_BITS_W(P_, W_)                                                                                                    \
                 if (bits_dw == 2) SBM_COARSE_BITS_D(P_, W_, 2); else SBM_COARSE_BITS_D(P_, W_, 1)
 #define SBM_COARSE_BITS_D(P_, W_, D_)                                                                                                \
+                do {                                                                                                                  \
+                c->note_coarse_form(3, P_, W_, D_);                                                                                   \
                 SBM_LAUNCH(c, "k_similarity_coarse", (k_similarity_coarse_bits<P_, W_, D_>), dim3(chunks, (cnt + 3) / 4, frames), dim3(256), 0, s, \
                            c->d_blm.as<uint32_t>(), c->lm_stride[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(), c->d_soff.as<int32_t>(),   \
                            c->d_citems.as<CoarseItem>() + first, c->d_cfoff.as<int32_t>() + (size_t)first * 64, cnt,                     \
                            c->d_rawkeep.as<int32_t>(), c->d_class.as<int32_t>(), c->d_tid.as<int32_t>(), c->d_cands.as<Cand>(), counters, \
-                           (int)c->cand_cap, (int64_t)(2 * c->lm_stride[lc]) / 4)
+                           (int)c->cand_cap, (int64_t)(2 * c->lm_stride[lc]) / 4);                                                      \
+                } while (0)
                 if (max_nf < 128) SBM_COARSE_BITS(7);
                 else if (max_nf < 1024) SBM_COARSE_BITS(10);
                 else SBM_COARSE_BITS_W(13, true); // thousands of features: always the wide batches, one dword per lane
@@ -1338,6 +1348,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             // large launches: one wave per (chunk, template, frame); small ones (a single frame with a few hundred
             // templates): four waves share an item's features so that enough loads are in flight
             const bool per_wave = c->coarse_mode == 2 || (c->coarse_mode != 1 && (int64_t)chunks * cnt * frames >= 8192);
+            c->note_coarse_form(per_wave ? 2 : 1, 0, false, 0);
             if (per_wave)
                 SBM_LAUNCH(c, "k_similarity_coarse", k_similarity_coarse_wave, dim3(chunks, (cnt + 3) / 4, frames), dim3(256), 0, s,
                            c->d_lm[lc].as<uint8_t>(), c->lm_stride[lc], c->rows[lc], c->cols[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(),
@@ -1593,6 +1604,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
             (void)hipGraphDestroy(ge.graph);
             return fail(SBM_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(he));
         }
+        memcpy(ge.coarse_form, c->coarse_form, sizeof ge.coarse_form);
         c->graphs.push_back(ge);
         hit = &c->graphs.back();
     } else {
@@ -1600,6 +1612,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
     }
     hit->last_use = ++c->graph_clock;
     HIP_TRY(hipGraphLaunch(hit->exec, s));
+    memcpy(c->coarse_form, hit->coarse_form, sizeof c->coarse_form);
     *launched = true;
     return 0;
 }
