@@ -396,6 +396,12 @@ int sbm_get_coarse_bitplanes(sbm_ctx* ctx, int32_t frame, uint8_t* out_host, int
  * 2; kind 3); 0 where they do not apply.  A call replayed from a captured graph reports the form it was captured with.
  * Reads a host-side record: no device work, no synchronisation, no state change.  A parity-test accessor. */
 int sbm_get_coarse_form(sbm_ctx* ctx, int32_t out[4]);
+/* Which form of the source pass the last call of this context launched (both are timed as "k_quantize"): 0 none -- the call
+ * built level 0's map whole, or no call yet --, 1 the strided form of the streaming gradient kernel, 2 the line-shaped kernel
+ * that takes layouts whose first pixel, row stride and frame stride are multiples of 4 bytes, whose frame fits 32-bit offsets
+ * and whose width is a multiple of 64 (SBM_SOURCE_LINES=0 in the environment: never).  A call replayed from a captured graph
+ * reports the form it was captured with.  Reads a host-side record, like sbm_get_coarse_form.  A parity-test accessor. */
+int sbm_get_source_form(sbm_ctx* ctx, int32_t* out);
 int sbm_level_dims(sbm_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols);
 
 /* Second half of match(): Detector::matchClass over the selected templates

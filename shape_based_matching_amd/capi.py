@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
     "sbm_match_batch_device_masked", "sbm_match_batch_host_begin_masked", "sbm_match_batch_host_masked", "sbm_get_quantized_frame",
     "sbm_get_coarse_form",
+    "sbm_get_source_form",
 ]
 
 
@@ -183,6 +184,7 @@ def lib() -> C.CDLL:
     L.sbm_get_linear_memories.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     L.sbm_get_coarse_bitplanes.argtypes = [vp, i32, vp, i64]
     L.sbm_get_coarse_form.argtypes = [vp, vp]
+    L.sbm_get_source_form.argtypes = [vp, vp]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
     L.sbm_quantized_orientations.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -648,6 +650,12 @@ class Context:
         out = np.zeros(4, np.int32)
         _check(lib().sbm_get_coarse_form(self._h, _p(out)))
         return tuple(int(v) for v in out)
+
+    def source_form(self) -> int:
+        """the source pass of the last call: 0 none (level 0's map was built whole), 1 the strided form, 2 the line-shaped kernel"""
+        out = C.c_int32(0)
+        _check(lib().sbm_get_source_form(self._h, C.byref(out)))
+        return int(out.value)
 
     def match_templates(self, threshold: float) -> np.ndarray:
         out = np.empty(self._cap, MATCH_DTYPE)

@@ -103,11 +103,13 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //                             pass there (cv::pyrDown + retained copy) and the gradient of the flagged tiles' reach behind it
 //                             (sbm_quantize_stream.h, QS_SOURCE / QS_SPARSE); SBM_SPARSE_STRIPS=0 implies it
 //   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
+//   SBM_SOURCE_LINES=0        the source pass always in its strided form (QS_SOURCE), never as k_source_lines (sbm_source_lines.h), which
+//                             otherwise runs wherever the caller's layout admits it (source_lines_ok): the A/B knob of the two forms
 struct Tuning {
     int coarse = 0, quantize = 0, hs0 = 0, hs1 = 0, local_grid = 0, local_waves = 0, local_order = -1;
     bool qs_pack = true, full_lm = false, strip_lm = true, graph_fork = true, fused_bits = true, lm_allty = true;
     int bits_wide = -1, bits_dw = 0, bits_block = -1, match_bands = 0, local_bits = -1;
-    bool sparse_strips = true, sparse_gradient = true;
+    bool sparse_strips = true, sparse_gradient = true, source_lines = true;
     int src_hs = 0;
 };
 static const Tuning& tuning()
@@ -140,6 +142,7 @@ static const Tuning& tuning()
         k.sparse_strips = num("SBM_SPARSE_STRIPS", 1) != 0;
         k.sparse_gradient = k.sparse_strips && num("SBM_SPARSE_GRADIENT", 1) != 0;
         k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
+        k.source_lines = num("SBM_SOURCE_LINES", 1) != 0;
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
         k.bits_dw = num("SBM_BITS_DW", 0) == 2 ? 2 : (num("SBM_BITS_DW", 0) == 1 ? 1 : 0);
         return k;
@@ -273,6 +276,7 @@ struct sbm_ctx {
         uint64_t last_use;
         bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
         int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
+        int32_t source_form = 0;               // ... and the captured source pass
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
@@ -280,6 +284,7 @@ struct sbm_ctx {
     int pipeline_depth = 1;                 // sbm_set_pipeline_depth: batches the caller keeps in flight on this GPU
     int local_order = tuning().local_order; // -1 by the planes' size, 0 per-frame slots, 2 one frame-major list (sbm_set_refine_order)
     int32_t coarse_form[4] = {0, 0, 0, 0};  // {kind, P, wide, dw} of the coarse kernel enqueue_coarse last launched (sbm_get_coarse_form)
+    int32_t source_form = 0; // the source pass of the last call: 0 none, 1 the strided form QS_SOURCE, 2 k_source_lines (sbm_get_source_form)
     void note_coarse_form(int kind, int P, bool wide, int dw)
     {
         coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw;
@@ -609,6 +614,34 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0, mask_fs);
     if (form && (!hs || band || d_mask)) return fail(SBM_ERR_STATE, "a reduced gradient form needs a whole, unmasked launch of the streaming kernel");
     if (form && form->stage == QS_SOURCE) hs = source_pass_rows();
+    // The source pass as whole lines (sbm_source_lines.h) wherever the caller's layout admits it; every other layout -- a row pad
+    // of 13 bytes, an odd frame stride -- stays with the strided form below.
+    if (form && form->stage == QS_SOURCE && tuning().source_lines &&
+        source_lines_ok((uint64_t)(uintptr_t)d_img, stride, img_fs, frames, rows, cols, ch)) {
+        QSArgs a;
+        memset(&a, 0, sizeof a);
+        a.img = d_img;
+        a.pyr = d_pyr;
+        a.img_fs = img_fs;
+        a.pyr_fs = pyr_fs;
+        a.rows = rows;
+        a.cols = cols;
+        a.stride = stride;
+        a.hs = hs;
+        a.row_lo = 0;
+        a.row_hi = rows;
+        a.n_strips = sl_strips(cols);
+        a.n_rblocks = sl_row_blocks(0, rows, hs);
+        a.frames = frames;
+        a.keep = form->keep;
+        a.keep_fs = form->keep_fs;
+        const dim3 g((unsigned)((sl_items(cols, a.n_rblocks, frames) + 3) / 4));
+        if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines<1>), g, dim3(256), 0, s, a);
+        else SBM_LAUNCH(c, "k_quantize", (k_source_lines<3>), g, dim3(256), 0, s, a);
+        HIP_TRY(hipGetLastError());
+        c->source_form = 2;
+        return 0;
+    }
     if (hs) {
         QSArgs a;
         memset(&a, 0, sizeof a);
@@ -656,6 +689,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         else SBM_QS(3);
 #undef SBM_QS
         HIP_TRY(hipGetLastError());
+        if (stage == QS_SOURCE) c->source_form = 1;
         return 0;
     }
     if (band && !tile_band) return fail(SBM_ERR_INVALID, "a row band needs the streaming gradient kernel (cols %% 4 == 0, no float outputs)");
@@ -1011,6 +1045,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     const uint8_t* mask = d_mask0;
     int64_t mask_fs = d_mask0 ? mask0_fs : 0;
     c->last_frames = frames;
+    c->source_form = 0;
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
@@ -1605,6 +1640,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
             return fail(SBM_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(he));
         }
         memcpy(ge.coarse_form, c->coarse_form, sizeof ge.coarse_form);
+        ge.source_form = c->source_form;
         c->graphs.push_back(ge);
         hit = &c->graphs.back();
     } else {
@@ -1613,6 +1649,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
     hit->last_use = ++c->graph_clock;
     HIP_TRY(hipGraphLaunch(hit->exec, s));
     memcpy(c->coarse_form, hit->coarse_form, sizeof c->coarse_form);
+    c->source_form = hit->source_form;
     *launched = true;
     return 0;
 }

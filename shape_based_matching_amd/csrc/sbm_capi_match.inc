@@ -816,6 +816,13 @@ int sbm_get_coarse_form(sbm_ctx* c, int32_t out[4])
     return 0;
 }
 
+int sbm_get_source_form(sbm_ctx* c, int32_t* out)
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    *out = c->source_form;
+    return 0;
+}
+
 int sbm_level_dims(sbm_ctx* c, int32_t level, int32_t* rows, int32_t* cols)
 {
     if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");

@@ -44,6 +44,9 @@ __device__ __forceinline__ V dont_care()
 __device__ __forceinline__ V from_left(V x) { return (V)__builtin_amdgcn_mov_dpp((int)x, 0x138, 0xf, 0xf, true); }
 // lane i <- lane i+1 (wave_shl:1 bound_ctrl:0); lane 63 reads 0
 __device__ __forceinline__ V from_right(V x) { return (V)__builtin_amdgcn_mov_dpp((int)x, 0x130, 0xf, 0xf, true); }
+// no instruction moves across this point: keeps the memory operations of a software-pipelined loop in the order they were
+// written, so that the wait in front of a row's first use counts exactly the operations issued behind that row's loads
+__device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 // a wave-uniform constant the optimiser must not look into (keeps it an SGPR operand of the instruction written)
 __device__ __forceinline__ uint32_t opaque(uint32_t k)
 {
@@ -152,6 +155,27 @@ __device__ __forceinline__ void buf_store_u32x3_nt(const Buf& b, V voff, uint32_
 __device__ __forceinline__ void buf_store_u16(const Buf& b, V voff, uint32_t soff, V v)
 {
     __builtin_amdgcn_raw_buffer_store_b16((unsigned short)v, b.rsrc, (int)voff, (int)soff, 0);
+}
+// ... three consecutive dwords that a later launch reads soon: no cache hint
+__device__ __forceinline__ void buf_store_u32x3(const Buf& b, V voff, uint32_t soff, V v0, V v1, V v2)
+{
+    __builtin_amdgcn_raw_buffer_store_b96(wv_u32x3{v0, v1, v2}, b.rsrc, (int)voff, (int)soff, 0);
+}
+
+// Loads through a buffer resource (sbm_source_lines.h): one, two or three consecutive dwords of a lane in one instruction, at a
+// 4-byte aligned address.  A lane whose offset is >= the buffer size (BUF_DROP) loads nothing and reads 0, so the lanes of a cut
+// strip, and all but the edge lanes of an edge load, need no branch.
+typedef uint32_t wv_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ V buf_load_u32(const Buf& b, V voff, uint32_t soff) { return __builtin_amdgcn_raw_buffer_load_b32(b.rsrc, (int)voff, (int)soff, 0); }
+__device__ __forceinline__ void buf_load_u32x2(const Buf& b, V voff, uint32_t soff, V& v0, V& v1)
+{
+    const wv_u32x2 r = __builtin_amdgcn_raw_buffer_load_b64(b.rsrc, (int)voff, (int)soff, 0);
+    v0 = r.x, v1 = r.y;
+}
+__device__ __forceinline__ void buf_load_u32x3(const Buf& b, V voff, uint32_t soff, V& v0, V& v1, V& v2)
+{
+    const wv_u32x3 r = __builtin_amdgcn_raw_buffer_load_b96(b.rsrc, (int)voff, (int)soff, 0);
+    v0 = r.x, v1 = r.y, v2 = r.z;
 }
 
 } // namespace wv
