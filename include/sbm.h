@@ -396,6 +396,15 @@ int sbm_get_coarse_bitplanes(sbm_ctx* ctx, int32_t frame, uint8_t* out_host, int
  * 2; kind 3); 0 where they do not apply.  A call replayed from a captured graph reports the form it was captured with.
  * Reads a host-side record: no device work, no synchronisation, no state change.  A parity-test accessor. */
 int sbm_get_coarse_form(sbm_ctx* ctx, int32_t out[4]);
+/* Which kernel form the last refinement pass of this context ran at `level` (a level below the coarsest; every form is timed
+ * as "k_similarity_local"): out = {kind, LW, order, t8, sparse, slots}.  kind: 0 nothing launched for this level yet, 1 the
+ * byte kernel on the 8 response planes, 2 on the plane of spread bytes row-major, 3 on the same plane in strips, 4 the
+ * bit-strip kernel.  LW: waves per candidate (1 for kind 4, else 4 or 16), order: 0 per-frame slots or 2 the frame-major list,
+ * t8: 1 for the strip kernel's T = 8 instantiation, sparse: 1 where level 0's bit strips were built for this call's
+ * candidates only, slots: candidate slots per frame of the grid.  A call replayed from a captured graph reports the form it
+ * was captured with.  SBM_ERR_INVALID for the coarsest level or a level outside the pyramid.  Reads a host-side record: no
+ * device work, no synchronisation, no state change.  A parity-test accessor. */
+int sbm_get_refine_form(sbm_ctx* ctx, int32_t level, int32_t out[6]);
 /* Which form of the source pass the last call of this context launched (both are timed as "k_quantize"): 0 none -- the call
  * built level 0's map whole, or no call yet --, 1 the strided form of the streaming gradient kernel, 2 the line-shaped kernel
  * that takes layouts whose first pixel, row stride and frame stride are multiples of 4 bytes, whose frame fits 32-bit offsets

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_device_masked", "sbm_match_batch_host_begin_masked", "sbm_match_batch_host_masked", "sbm_get_quantized_frame",
     "sbm_get_coarse_form",
     "sbm_get_source_form",
+    "sbm_get_refine_form",
 ]
 
 
@@ -185,6 +186,7 @@ def lib() -> C.CDLL:
     L.sbm_get_coarse_bitplanes.argtypes = [vp, i32, vp, i64]
     L.sbm_get_coarse_form.argtypes = [vp, vp]
     L.sbm_get_source_form.argtypes = [vp, vp]
+    L.sbm_get_refine_form.argtypes = [vp, i32, vp]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
     L.sbm_quantized_orientations.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -649,6 +651,13 @@ class Context:
         2 bytes with one wave per item, 3 bit planes with one wave per item, 4 bit planes with eight waves per item"""
         out = np.zeros(4, np.int32)
         _check(lib().sbm_get_coarse_form(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
+    def refine_form(self, level: int = 0) -> Tuple[int, int, int, int, int, int]:
+        """(kind, LW, order, t8, sparse, slots) of the refinement kernel the last call launched at ``level``: kind 0 none yet,
+        1 the 8 response planes, 2 the spread plane row-major, 3 the spread plane in strips, 4 bit strips"""
+        out = np.zeros(6, np.int32)
+        _check(lib().sbm_get_refine_form(self._h, level, _p(out)))
         return tuple(int(v) for v in out)
 
     def source_form(self) -> int:

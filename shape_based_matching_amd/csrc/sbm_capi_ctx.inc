@@ -277,6 +277,7 @@ struct sbm_ctx {
         bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
         int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
         int32_t source_form = 0;               // ... and the captured source pass
+        int32_t refine_form[SBM_MAX_LEVELS][6] = {}; // ... and what the captured enqueue_local launched per level
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
@@ -285,6 +286,14 @@ struct sbm_ctx {
     int local_order = tuning().local_order; // -1 by the planes' size, 0 per-frame slots, 2 one frame-major list (sbm_set_refine_order)
     int32_t coarse_form[4] = {0, 0, 0, 0};  // {kind, P, wide, dw} of the coarse kernel enqueue_coarse last launched (sbm_get_coarse_form)
     int32_t source_form = 0; // the source pass of the last call: 0 none, 1 the strided form QS_SOURCE, 2 k_source_lines (sbm_get_source_form)
+    // {kind, LW, order, t8, sparse, slots} of the refinement kernel enqueue_local last launched for every level (sbm_get_refine_form)
+    int32_t refine_form[SBM_MAX_LEVELS][6] = {};
+    void note_refine_form(int l, LmForm reads, int LW, int order, bool t8, bool sparse, int slots)
+    {
+        const int kind = reads == LM_BIT_STRIPS ? 4 : reads == LM_SPREAD_STRIP ? 3 : reads == LM_SPREAD ? 2 : 1;
+        const int32_t f[6] = {kind, LW, order, t8 ? 1 : 0, sparse ? 1 : 0, slots};
+        memcpy(refine_form[l], f, sizeof f);
+    }
     void note_coarse_form(int kind, int P, bool wide, int dw)
     {
         coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw;
@@ -1466,6 +1475,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
             if (order == 2) SBM_LOCAL_BITS(2);
             else SBM_LOCAL_BITS(0);
 #undef SBM_LOCAL_BITS
+            c->note_refine_form(l, reads, 1, order, false, l == 0 && sparse0, slots);
         }
         else if (reads == LM_SPREAD_STRIP) { SBM_LOCAL(2, c->d_lmc[l].as<uint8_t>(), 1); }
         else if (reads == LM_SPREAD) { SBM_LOCAL(1, c->d_lmc[l].as<uint8_t>(), 1); }
@@ -1474,6 +1484,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
 #undef SBM_LOCAL_LW
 #undef SBM_LOCAL_O
 #undef SBM_LOCAL_T
+        if (reads != LM_BIT_STRIPS) c->note_refine_form(l, reads, small_blocks ? 4 : LOCAL_WAVES, order, reads == LM_SPREAD_STRIP && T == 8, false, local_grid);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -1641,6 +1652,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
         }
         memcpy(ge.coarse_form, c->coarse_form, sizeof ge.coarse_form);
         ge.source_form = c->source_form;
+        memcpy(ge.refine_form, c->refine_form, sizeof ge.refine_form);
         c->graphs.push_back(ge);
         hit = &c->graphs.back();
     } else {
@@ -1650,6 +1662,7 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
     HIP_TRY(hipGraphLaunch(hit->exec, s));
     memcpy(c->coarse_form, hit->coarse_form, sizeof c->coarse_form);
     c->source_form = hit->source_form;
+    memcpy(c->refine_form, hit->refine_form, sizeof c->refine_form);
     *launched = true;
     return 0;
 }

@@ -816,6 +816,14 @@ int sbm_get_coarse_form(sbm_ctx* c, int32_t out[4])
     return 0;
 }
 
+int sbm_get_refine_form(sbm_ctx* c, int32_t level, int32_t out[6])
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    if (level < 0 || level >= c->L - 1) return fail(SBM_ERR_INVALID, "level %d is no refinement level", level);
+    memcpy(out, c->refine_form[level], sizeof c->refine_form[level]);
+    return 0;
+}
+
 int sbm_get_source_form(sbm_ctx* c, int32_t* out)
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");

@@ -89,9 +89,11 @@ def test_geometries(oracle, ctx_form, case1, rows, cols):
 
 
 @pytest.mark.parametrize("nf,box", [([100, 40], 200), ([124, 60], 200), ([125, 61], 200), ([600, 200], 400), ([1020, 500], 500),
-                                    ([1021, 300], 500), ([3000, 900], 700), ([8191, 4095], 840)])
+                                    ([1021, 300], 500), ([3000, 900], 700), ([8191, 4095], 840),
+                                    ([252, 60], 200), ([253, 61], 200), ([2044, 500], 500), ([2045, 500], 500)])
 def test_feature_counts(oracle, ctx_form, nf, box):
-    """the kernel's counter widths change at 124 and 1020 features per template; the largest template the reference admits"""
+    """the kernel's counter widths change at 252 and 2044 features per template (a slot counts ceil(nf / 4) features: 63 and 511
+    fill 6 and 9 counter planes); 124 / 125 and 1020 / 1021 were an earlier kernel's; the largest template the reference admits"""
     img = synth.scene_bgr(21, 1024, 1024, n_shapes=400)
     pyr = oracle.Pyramid.build(img, [4, 8], 30.0)
     ts, got = templates_from_maps([pyr.quantized(0), pyr.quantized(1)], nf, box, 6, 7 + nf[0])
