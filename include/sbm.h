@@ -411,6 +411,14 @@ int sbm_get_refine_form(sbm_ctx* ctx, int32_t level, int32_t out[6]);
  * and whose width is a multiple of 64 (SBM_SOURCE_LINES=0 in the environment: never).  A call replayed from a captured graph
  * reports the form it was captured with.  Reads a host-side record, like sbm_get_coarse_form.  A parity-test accessor. */
 int sbm_get_source_form(sbm_ctx* ctx, int32_t* out);
+/* The sparse level-0 gradient launch of the last call of this context: out = {selection, working, launched}.  selection: 0 the
+ * call made no such launch (level 0's map was built whole, or no call yet), 1 its work items were chosen by the refinement-tile
+ * flags on the fixed strip grid, 2 by the record of need rectangles (per band of 8 pixel rows the hull of the map columns some
+ * coarse candidate's refinement depends on; SBM_SPARSE_RECTS=0 in the environment: never).  working: the work items that did
+ * not return at once, counted on the device only while profiling is enabled (sbm_set_profiling), -1 otherwise and for a call
+ * replayed from a captured graph; with sbm_match's overflow retry, the retry's launch.  launched: the work items of the grid.
+ * Waits for the device when a count is still outstanding.  A parity-test accessor. */
+int sbm_get_sparse_items(sbm_ctx* ctx, int32_t out[3]);
 int sbm_level_dims(sbm_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols);
 
 /* Second half of match(): Detector::matchClass over the selected templates

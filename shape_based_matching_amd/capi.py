@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "sbm_get_coarse_form",
     "sbm_get_source_form",
     "sbm_get_refine_form",
+    "sbm_get_sparse_items",
 ]
 
 
@@ -186,6 +187,7 @@ def lib() -> C.CDLL:
     L.sbm_get_coarse_bitplanes.argtypes = [vp, i32, vp, i64]
     L.sbm_get_coarse_form.argtypes = [vp, vp]
     L.sbm_get_source_form.argtypes = [vp, vp]
+    L.sbm_get_sparse_items.argtypes = [vp, vp]
     L.sbm_get_refine_form.argtypes = [vp, i32, vp]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
@@ -665,6 +667,13 @@ class Context:
         out = C.c_int32(0)
         _check(lib().sbm_get_source_form(self._h, C.byref(out)))
         return int(out.value)
+
+    def sparse_items(self) -> Tuple[int, int, int]:
+        """(selection, working, launched) of the last call's sparse level-0 gradient launch: selection 0 none, 1 by tile flags,
+        2 by the record of need rectangles; working items are counted under profiling only (-1 otherwise)"""
+        out = np.zeros(3, np.int32)
+        _check(lib().sbm_get_sparse_items(self._h, _p(out)))
+        return tuple(int(v) for v in out)
 
     def match_templates(self, threshold: float) -> np.ndarray:
         out = np.empty(self._cap, MATCH_DTYPE)

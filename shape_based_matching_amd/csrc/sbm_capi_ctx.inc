@@ -102,6 +102,8 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //   SBM_SPARSE_GRADIENT=0     match entry points run level 0's whole gradient stage in front of the coarse pass instead of the source
 //                             pass there (cv::pyrDown + retained copy) and the gradient of the flagged tiles' reach behind it
 //                             (sbm_quantize_stream.h, QS_SOURCE / QS_SPARSE); SBM_SPARSE_STRIPS=0 implies it
+//   SBM_SPARSE_RECTS=0        the sparse level-0 gradient pass takes its work items from the tile flags on the fixed strip grid instead of
+//                             from the record of need rectangles (sbm_refine_tiles.h: refine_need, gradient_rect_item_needed): the A/B knob
 //   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
 //   SBM_SOURCE_LINES=0        the source pass always in its strided form (QS_SOURCE), never as k_source_lines (sbm_source_lines.h), which
 //                             otherwise runs wherever the caller's layout admits it (source_lines_ok): the A/B knob of the two forms
@@ -109,7 +111,7 @@ struct Tuning {
     int coarse = 0, quantize = 0, hs0 = 0, hs1 = 0, local_grid = 0, local_waves = 0, local_order = -1;
     bool qs_pack = true, full_lm = false, strip_lm = true, graph_fork = true, fused_bits = true, lm_allty = true;
     int bits_wide = -1, bits_dw = 0, bits_block = -1, match_bands = 0, local_bits = -1;
-    bool sparse_strips = true, sparse_gradient = true, source_lines = true;
+    bool sparse_strips = true, sparse_gradient = true, source_lines = true, sparse_rects = true;
     int src_hs = 0;
 };
 static const Tuning& tuning()
@@ -141,6 +143,7 @@ static const Tuning& tuning()
         k.local_bits = num("SBM_LOCAL_BITS", -1);
         k.sparse_strips = num("SBM_SPARSE_STRIPS", 1) != 0;
         k.sparse_gradient = k.sparse_strips && num("SBM_SPARSE_GRADIENT", 1) != 0;
+        k.sparse_rects = k.sparse_gradient && num("SBM_SPARSE_RECTS", 1) != 0;
         k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
         k.source_lines = num("SBM_SOURCE_LINES", 1) != 0;
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
@@ -201,6 +204,13 @@ struct sbm_ctx {
     // behind the coarse pass reads them, and so does the whole launch that a later reader of d_quant[0] asks for
     // (ensure_level0_map) -- the caller's image may be gone by then.  map0_whole: d_quant[0] holds every frame's whole map.
     DevBuf d_src0;
+    // ... and of that map only the work items the refinement can read (SBM_SPARSE_RECTS): per frame and band of RT_BAND pixel rows the
+    // hull {xmin, xmax} of the map columns some candidate's refinement depends on, emptied where the tile flags are cleared, widened
+    // by k_mark_refine_tiles, read by the sparse gradient launch.  Device data: a replayed graph follows each call's candidates.
+    DevBuf d_rects;
+    DevBuf d_sparse_items;          // one int32: the working items of the last profiled sparse gradient launch
+    int32_t sparse_items[3] = {0, 0, 0}; // {selection: 0 none, 1 tiles, 2 need rectangles; working items (-1: not counted); items launched}
+    bool sparse_items_pending = false;   // the count is still on the device
     int src0_ch = 0;
     bool map0_whole = true;
     // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
@@ -275,6 +285,7 @@ struct sbm_ctx {
         hipGraphExec_t exec;
         uint64_t last_use;
         bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
+        bool sparse_rects = false; // ... with its work items taken from the record of need rectangles (other kernel arguments)
         int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
         int32_t source_form = 0;               // ... and the captured source pass
         int32_t refine_form[SBM_MAX_LEVELS][6] = {}; // ... and what the captured enqueue_local launched per level
@@ -458,6 +469,11 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             c->d_src0.release();
             if (c->d_tiles.p && c->L == 2 && tuning().sparse_gradient)
                 if (int e = c->d_src0.ensure(B * r * cc * channels)) return e;
+            c->d_rects.release();
+            if (c->d_src0.p && tuning().sparse_rects)
+                if (int e = c->d_rects.ensure(B * (size_t)refine_band_count(r) * 2 * sizeof(int32_t), true)) return e; // zeroed: every band empty
+            if (c->d_src0.p)
+                if (int e = c->d_sparse_items.ensure(256, true)) return e;
         }
         c->forms[l].forget();
     }
@@ -494,6 +510,7 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
     if (l == 0) {
         c->d_tiles.release();
         c->d_src0.release();
+        c->d_rects.release();
         c->map0_whole = true; // the caller sets the whole map
     }
     c->forms[l].forget();
@@ -600,6 +617,9 @@ struct QSForm {
     int64_t keep_fs;
     const uint8_t* tile_flags;
     int n_tiles, T, W, H;
+    const int32_t* need_rects = nullptr; // QS_SPARSE: the record of need rectangles, n_bands pairs per frame; null: the tile-driven items
+    int n_bands = 0;
+    int32_t* item_count = nullptr;       // QS_SPARSE: where the working items are counted (profiling), or null
 };
 
 // rows per work item of the source pass: its items run hs + 3 row iterations, in whole groups of 6
@@ -685,6 +705,16 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
             a.grid_t = form->T;
             a.grid_w = form->W;
             a.grid_h = form->H;
+            a.item_count = form->item_count;
+            if (form->need_rects) {
+                // an item is (k-th strip from the left end of its rows' hull, row block, frame); the packed last strip stays fixed
+                a.need_rects = form->need_rects;
+                a.n_bands = form->n_bands;
+            }
+            c->sparse_items[0] = form->need_rects ? 2 : 1;
+            c->sparse_items[1] = -1;
+            c->sparse_items[2] = quantize_stream_items(a);
+            c->sparse_items_pending = form->item_count != nullptr;
         }
         const dim3 g((unsigned)((quantize_stream_items(a) + 3) / 4));
         // (one timing name for all three forms: the launches of the gradient stage)
@@ -1055,6 +1085,8 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     int64_t mask_fs = d_mask0 ? mask0_fs : 0;
     c->last_frames = frames;
     c->source_form = 0;
+    c->sparse_items[0] = 0, c->sparse_items[1] = -1, c->sparse_items[2] = 0;
+    c->sparse_items_pending = false;
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
@@ -1118,6 +1150,8 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
             if (plan.form[0] == LM_BIT_STRIPS_SPARSE) {
                 a.clear_tiles = c->d_tiles.as<uint8_t>();
                 a.n_tiles = refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]);
+                a.clear_rects = c->d_rects.as<int32_t>(); // (null without the record)
+                a.n_bands = refine_band_count(c->rows[0]);
             }
         }
         SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
@@ -1306,7 +1340,8 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
     if (!c->counters_fresh && frames > 1) return fail(SBM_ERR_STATE, "batched template loop without a batched pyramid");
     if (!c->counters_fresh)
         hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, s, counters, d_count, clear_tiles ? c->d_tiles.as<uint8_t>() : (uint8_t*)nullptr,
-                           clear_tiles ? refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]) : 0);
+                           clear_tiles ? refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]) : 0,
+                           clear_tiles ? c->d_rects.as<int32_t>() : (int32_t*)nullptr, clear_tiles ? refine_band_count(c->rows[0]) : 0);
     c->counters_fresh = false;
     const int n_active = (int)c->h_active.size();
     if (n_active > 0) {
@@ -1504,15 +1539,23 @@ bool sparse_refine(const sbm_ctx* c)
 // workgroup whose flag is 0 returns at once).  The unflagged tiles keep whatever an earlier call left: nothing reads them.
 int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
 {
-    const int T = c->cfg.T[0], W = c->cols[0] / T, H = c->rows[0] / T, n_tiles = refine_tile_count(W, H);
+    const int T = c->cfg.T[0], W = c->cols[0] / T, H = c->rows[0] / T, n_tiles = refine_tile_count(W, H), n_bands = refine_band_count(c->rows[0]);
+    // the record of need rectangles only where this call's gradient launch reads it (the flags alone serve the strip builder)
+    int32_t* const rects = !c->map0_whole && tuning().sparse_rects ? c->d_rects.as<int32_t>() : nullptr;
     SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
-               (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles);
+               (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles, rects, n_bands);
     HIP_TRY(hipGetLastError());
     if (!c->map0_whole) {
         // the call ran the source pass only (BuildPlan::sparse_gradient): level 0's gradient stage now, from the retained
         // source, in the work items whose output the flagged tiles' builders load.  The map stays in pieces (map0_whole).
         const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
-        const QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
+        QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
+        form.need_rects = rects;
+        form.n_bands = n_bands;
+        if (c->profiling && c->d_sparse_items.p) { // (no capture while profiling: graph_wanted)
+            HIP_TRY(hipMemsetAsync(c->d_sparse_items.p, 0, sizeof(int32_t), s));
+            form.item_count = c->d_sparse_items.as<int32_t>();
+        }
         if (int e = launch_quantize(c, s, c->d_src0.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(),
                                     nullptr, nullptr, nullptr, frames, (int64_t)rows * cols * ch, 0, rows, false, 0, &form))
             return e;
@@ -1604,7 +1647,8 @@ bool graph_key_equal(const sbm_ctx::GraphEntry& g, const sbm_ctx::GraphEntry& k)
 {
     return g.img == k.img && g.rows == k.rows && g.cols == k.cols && g.stride == k.stride && g.ch == k.ch && g.mask == k.mask &&
            g.thr_bits == k.thr_bits && g.out == k.out && g.cap == k.cap && g.count == k.count && g.mo == k.mo && g.mc == k.mc &&
-           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride && g.sparse_grad == k.sparse_grad;
+           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride && g.sparse_grad == k.sparse_grad &&
+           g.sparse_rects == k.sparse_rects;
 }
 
 constexpr size_t GRAPH_CACHE = 16;
@@ -1684,8 +1728,12 @@ int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
 // what a match entry point leaves resident, for the calls that replay its launches as a captured graph
 // sparse_grad: the captured call made level 0's map sparsely (its graph key says so)
 // any_batch: the captured call was a batch through k_build_lm_any (PlanInputs::any_batch)
-void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch)
+// sparse_rects: ... with its work items taken from the record of need rectangles
+void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch, bool sparse_rects = false)
 {
+    c->sparse_items[0] = sparse_grad ? (sparse_rects ? 2 : 1) : 0;
+    c->sparse_items[1] = -1; // a replay counts nothing
+    c->sparse_items_pending = false;
     PlanInputs pin = plan_inputs(c);
     pin.any_batch = any_batch;
     record_match(c->forms, pin, one_launch, c->h_active.empty());
@@ -1739,8 +1787,10 @@ sbm_ctx::GraphEntry graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     // (the template loop has no frame stride: what its launches depend on instead is the form every level is held in)
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
     const bool sparse_grad = kind > 0 && plans_sparse_gradient(c, m.mask, m.stride, m.frames, m.frame_stride, nullptr, false);
-    return sbm_ctx::GraphEntry{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
-                               kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0, sparse_grad};
+    sbm_ctx::GraphEntry key{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
+                            kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0, sparse_grad};
+    key.sparse_rects = sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
+    return key;
 }
 
 // The launches of a match call on stream s: a replay of the graph captured for its argument tuple where one is wanted --
@@ -1774,7 +1824,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is the one-launch
             // builder's where that takes every level, else the batched any-stride builder's; the template loop builds nothing
             if (kind >= 0) {
-                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c));
+                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects);
                 c->last_frames = m.frames;
             }
             return 0;

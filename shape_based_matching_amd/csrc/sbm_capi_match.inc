@@ -831,6 +831,18 @@ int sbm_get_source_form(sbm_ctx* c, int32_t* out)
     return 0;
 }
 
+int sbm_get_sparse_items(sbm_ctx* c, int32_t out[3])
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    if (c->sparse_items_pending) { // the profiled launch counted on the device: fetch it once
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(&c->sparse_items[1], c->d_sparse_items.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+        c->sparse_items_pending = false;
+    }
+    memcpy(out, c->sparse_items, sizeof c->sparse_items);
+    return 0;
+}
+
 int sbm_level_dims(sbm_ctx* c, int32_t level, int32_t* rows, int32_t* cols)
 {
     if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");

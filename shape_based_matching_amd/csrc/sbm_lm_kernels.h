@@ -427,6 +427,10 @@ struct LmArgs {
     uint8_t* clear_tiles;
     const uint8_t* tile_flags;
     int32_t n_tiles;
+    // clear_rects (may be null): the record of need rectangles beside the flags, n_bands {xmin, xmax} pairs per frame, emptied
+    // where the flags are cleared
+    int32_t* clear_rects;
+    int32_t n_bands;
 };
 
 __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
@@ -439,6 +443,8 @@ __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
         if (threadIdx.x < 2 && a.out_count) a.out_count[frame * 2 + threadIdx.x] = 0;
         if (a.clear_tiles)
             for (int i = threadIdx.x; i < a.n_tiles; i += 256) a.clear_tiles[frame * a.n_tiles + i] = 0;
+        if (a.clear_rects)
+            for (int i = threadIdx.x; i < 2 * a.n_bands; i += 256) a.clear_rects[frame * a.n_bands * 2 + i] = (i & 1) ? 0 : 0x7fffffff;
     }
     // the level whose block range holds this block (the host orders the ranges heaviest blocks first)
     int l = 0, lb = -1;

@@ -95,6 +95,13 @@ struct QSArgs {
     int64_t keep_fs;           // ... bytes from one frame of it to the next
     const uint8_t* tile_flags; // QS_SPARSE: n_tiles byte flags per frame (sbm_refine_tiles.h); null: every work item runs
     int32_t n_tiles, grid_t, grid_w, grid_h; // ... and the T, W, H of the strip level the tiles belong to
+    // QS_SPARSE, beside the flags: the finer record of k_mark_refine_tiles, n_bands {xmin, xmax} pairs per frame (sbm_refine_tiles.h).
+    // With it a work item is (k-th strip from the left end of its rows' hull, row block, frame): see gradient_rect_item_needed.
+    // Null: the tile-driven selection on the fixed strip grid.  A packed last strip stays where it is and serves the last moved strip
+    // of each of its frames.
+    const int32_t* need_rects;
+    int32_t n_bands;
+    int32_t* item_count; // QS_SPARSE under profiling (else null): every work item that works adds 1 (a packed wave: 1 per frame that needs it)
 };
 
 // Which part of the row loop a kernel instance holds (compile time):
@@ -104,7 +111,9 @@ struct QSArgs {
 //              (quantize_source_wave).  The next level gets its image and the context keeps the bytes that QS_SPARSE -- or a
 //              later whole launch -- reads
 //   QS_SPARSE  everything but cv::pyrDown; a work item returns before its first load unless it writes a pixel that the strip
-//              builder of a flagged tile of its frame (a packed wave: of any of its frames) loads (gradient_item_needed)
+//              builder of a flagged tile of its frame (a packed wave: of any of its frames) loads (gradient_item_needed) -- or,
+//              with the record of need rectangles, unless its strip, counted from the left end of what the refinement can read
+//              in its rows, begins inside that hull and meets a flagged tile (gradient_rect_item_needed)
 enum QSStage : int { QS_WHOLE = 0, QS_SOURCE = 1, QS_SPARSE = 2 };
 
 // Gaussian / pyrDown weights as packed pairs (lo | hi << 16)
@@ -311,12 +320,30 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
         quantize_source_wave<CH>(a, strip, rb, frame, nseg);
         return;
     }
+    int x_first = strip * QS_USEFUL; // first useful column of the item's strip
     if (STAGE == QS_SPARSE && a.tile_flags) { // wave-uniform: a few byte loads
-        bool need = false;
-        for (int g = 0; g < (nseg ? nseg : 1); ++g)
-            need = need || gradient_item_needed(a.tile_flags + (int64_t)(frame + g) * a.n_tiles, strip, rb, a.hs, QS_USEFUL, a.rows, a.cols,
-                                                a.grid_t, a.grid_w, a.grid_h);
-        if (!need) return;
+        int working = 0;
+        // `working`: the frames of the wave (one, but for a packed last strip) whose item works
+        for (int g = 0; g < (nseg ? nseg : 1); ++g) {
+            const uint8_t* flags = a.tile_flags + (int64_t)(frame + g) * a.n_tiles;
+            if (a.need_rects) {
+                // `strip` counts from the left end of the hull of the item's rows.  A packed wave stays on the fixed last strip: a
+                // frame's last moved strip, xa + 240 (n_strips - 1) .. cols, lies inside it whatever xa is
+                int x;
+                const bool n = gradient_rect_item_needed(a.need_rects + (int64_t)(frame + g) * a.n_bands * 2, flags, strip, rb, a.hs, QS_USEFUL,
+                                                         a.rows, a.cols, a.grid_t, a.grid_w, a.grid_h, &x);
+                if (n && !nseg) x_first = x;
+                working += n;
+            } else {
+                working += gradient_item_needed(flags, strip, rb, a.hs, QS_USEFUL, a.rows, a.cols, a.grid_t, a.grid_w, a.grid_h);
+            }
+        }
+        if (!working) return;
+#ifndef SBM_WAVE_EMU
+        if (a.item_count && (threadIdx.x & 63) == 0) atomicAdd(a.item_count, working);
+#else
+        if (a.item_count) *a.item_count += working;
+#endif
     }
     const int rows = a.rows, cols = a.cols;
     // Every work item owns exactly min(hs, row_hi - row_lo) output rows: the last row block is moved up to end at the
@@ -325,7 +352,7 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     int R0 = a.row_lo + rb * a.hs;
     if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
     const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
-    const int cb = strip * QS_USEFUL - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
+    const int cb = x_first - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
     const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
     uint8_t* out = a.out + (int64_t)frame * a.out_fs;
     uint8_t* pyr = STAGE != QS_SPARSE && a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;

@@ -4,6 +4,8 @@
 // device, tests/test_refine_tiles.py compiles it for the CPU suite.
 // Further down: which pixels of the level's orientation map a tile's strip builder loads, and which work items of the streaming
 // gradient kernel write them (gradient_item_needed: the sparse gradient pass of sbm_quantize_stream.h, tests/test_sparse_gradient.py).
+// Last: the finer record of what the refinement reads -- per band of pixel rows the hull of the needed map columns (refine_need) --
+// and the work items of the sparse gradient pass placed by it (gradient_rect_item_needed, tests/test_sparse_rects.py).
 //
 // A TILE is one workgroup of build_lm_strip4_allty<true> (sbm_lm_kernels.h): RT_STRIPS strips of 16 cells x RT_ROWS grid
 // rows, for all 128 (sub-plane, orientation) planes; tile (tx, ty) of a W x H grid has index ty * ((W + 31) / 32) + tx, the
@@ -145,6 +147,85 @@ SBM_RT_HD bool gradient_item_needed(const uint8_t* flags, int strip, int rb, int
     gradient_item_rows(rb, hs, rows, &r0, &r1);
     const int x0 = strip * useful, x1 = x0 + useful < cols ? x0 + useful : cols;
     return refine_rect_needed(flags, x0, r0, x1, r1, rows, cols, T, W, H);
+}
+
+// ---- the finer record: per band of RT_BAND pixel rows, the hull of the map columns some candidate's refinement depends on ----
+// Of the two dwords local_best_bits loads per patch row, a response is formed from the 16 cells gx0 .. gx0 + 15 only (the pair is
+// shifted right by gx0 & 15 and cut to 16 bits), in grid rows gy0 .. gy0 + 15: the other cells of strips s and s + 1 are loaded and
+// dropped.  Over a candidate's in-bounds features that is the CELL rectangle [x_lo / T, x_hi / T + 15] x [y_lo / T, y_hi / T + 15],
+// where refine_tiles works at strip precision.  Cell (gx, gy) -- all T * T sub-planes of it -- is spread from the map pixels
+// [gx T, gx T + 2T - 2] x [gy T, gy T + 2T - 2] (pixel p of the response plane ORs the pixels p .. p + T - 1).
+// The record: int32 pairs {xmin, xmax} per band and frame, columns [xmin, xmax), empty when xmin >= xmax (cleared to
+// {INT32_MAX, 0}; a zeroed record is empty too).  The wrap cases of the flat index (a patch that passes row H - 1, a strip index past
+// the last strip), H < 16 and a grid of cut strips keep the strip-precise footprint of refine_tiles: a superset is always correct.
+constexpr int RT_BAND = 8; // pixel rows per band
+SBM_RT_HD int refine_band_count(int rows) { return (rows + RT_BAND - 1) / RT_BAND; }
+
+struct BandRect {
+    int b0, b1, x0, x1; // bands b0 .. b1 (none when b1 < b0), columns [x0, x1)
+};
+// the map pixels the cells [gx0, gx1] x [gy0, gy1] are spread from, as bands and columns
+SBM_RT_HD BandRect refine_cells_bands(int gx0, int gx1, int gy0, int gy1, int rows, int cols, int T)
+{
+    const int x1 = gx1 * T + 2 * T - 1, y1 = gy1 * T + 2 * T - 2;
+    return BandRect{gy0 * T / RT_BAND, (y1 < rows - 1 ? y1 : rows - 1) / RT_BAND, gx0 * T, x1 < cols ? x1 : cols};
+}
+struct RefineNeed {
+    BandRect r[2]; // r[1]: the flat overrun of a wrap case, else none
+};
+SBM_RT_HD RefineNeed refine_need(const RefineOrigin& o, int width, int height, int rows, int cols, int T, int W, int H)
+{
+    RefineNeed n{{{0, -1, 0, 0}, {0, -1, 0, 0}}};
+    const RefineTiles t = refine_tiles(o, width, height, rows, cols, T, W, H);
+    if (!t.any) return n;
+    const int ns = W >> 4;
+    if (H >= 16 && t.over < 0 && t.s1 < ns && (W & 15) == 0) { // no wrap: cell precision
+        const int x_lo = o.ox > 0 ? o.ox : 0, x_hi = o.ox + width - 1 < cols - 1 ? o.ox + width - 1 : cols - 1;
+        n.r[0] = refine_cells_bands(x_lo / T, x_hi / T + 15, t.r0, t.r1, rows, cols, T);
+        return n;
+    }
+    // strips s0 .. s1, rows r0 .. r1; a strip index that wraps may be any strip of the row: every column
+    const bool all0 = t.s1 >= ns || (W & 15) != 0 || H < 16;
+    n.r[0] = refine_cells_bands(all0 ? 0 : t.s0 * 16, all0 ? W - 1 : t.s1 * 16 + 15, t.r0, t.r1, rows, cols, T);
+    if (all0) n.r[0].x1 = cols;
+    if (t.over >= 0) { // strips s0 + 1 .. s1 + 1, rows 0 .. over
+        const bool all1 = all0 || t.s1 + 1 >= ns;
+        n.r[1] = refine_cells_bands(all1 ? 0 : (t.s0 + 1) * 16, all1 ? W - 1 : (t.s1 + 1) * 16 + 15, 0, t.over, rows, cols, T);
+        if (all1) n.r[1].x1 = cols;
+    }
+    return n;
+}
+
+// The hull [*xa, *xb) of the bands that the pixel rows [r0, r1) meet; false: all of them are empty.  iv: one frame's record.
+SBM_RT_HD bool refine_rows_hull(const int32_t* iv, int r0, int r1, int* xa, int* xb)
+{
+    int a = 0x7fffffff, b = 0;
+    for (int band = r0 / RT_BAND; band <= (r1 - 1) / RT_BAND; ++band) {
+        const int lo = iv[2 * band], hi = iv[2 * band + 1];
+        if (lo >= hi) continue;
+        a = lo < a ? lo : a;
+        b = hi > b ? hi : b;
+    }
+    *xa = a & ~3; // a lane of the gradient kernel holds 4 pixels: 12 source bytes, dword-aligned only at a multiple of 4
+    *xb = b;
+    return a < b;
+}
+
+// The rect-driven item (k, rb) of the sparse gradient pass: its strip of `useful` columns starts at *x0 = xa + useful * k, xa the
+// left end of the hull of its rows, and it works when the strip begins left of the hull's right end AND some flagged tile's
+// builder loads a pixel of its rectangle (the tile-driven test on the moved strip: two distant objects in the same rows leave
+// the strips between them out, as the tile flags do).  The kernel and tests/test_sparse_rects.py share this function.
+SBM_RT_HD bool gradient_rect_item_needed(const int32_t* iv, const uint8_t* flags, int k, int rb, int hs, int useful, int rows, int cols, int T,
+                                         int W, int H, int* x0)
+{
+    int r0, r1, xa, xb;
+    gradient_item_rows(rb, hs, rows, &r0, &r1);
+    *x0 = 0;
+    if (!refine_rows_hull(iv, r0, r1, &xa, &xb)) return false;
+    const int s0 = xa + k * useful, s1 = s0 + useful < cols ? s0 + useful : cols;
+    *x0 = s0;
+    if (s0 >= xb) return false;
+    return refine_rect_needed(flags, s0, r0, s1, r1, rows, cols, T, W, H);
 }
 
 } // namespace sbm

@@ -399,13 +399,17 @@ __global__ __launch_bounds__(256) void k_copy_bytes(const uint8_t* __restrict__ 
 
 // zero the per-call counters (one launch instead of two memsets)
 // tiles (may be null): frame 0's refinement-tile flags (sbm_refine_tiles.h), cleared for k_mark_refine_tiles
-__global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ out_count, uint8_t* __restrict__ tiles, int n_tiles)
+// rects (may be null): ... and its record of need rectangles, n_bands {xmin, xmax} pairs, emptied
+__global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ out_count, uint8_t* __restrict__ tiles, int n_tiles,
+                        int32_t* __restrict__ rects, int n_bands)
 {
     top_wave_priority();
     for (int i = threadIdx.x; i < CTR_STRIDE; i += blockDim.x) counters[i] = 0; // layout: sbm_common.h CTR_*
     if (threadIdx.x < 2) out_count[threadIdx.x] = 0;
     if (tiles)
         for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) tiles[i] = 0;
+    if (rects)
+        for (int i = threadIdx.x; i < 2 * n_bands; i += blockDim.x) rects[i] = (i & 1) ? 0 : 0x7fffffff;
 }
 
 // Between the coarse pass and the refinement of a level held as sparse bit strips (LM_BIT_STRIPS_SPARSE): a thread per coarse
@@ -416,21 +420,88 @@ __global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ ou
 // uploaded template may declare any box), while the clamps use the declared one as the refinement pass does.
 __global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restrict__ cands, const int32_t* __restrict__ counters, int cand_cap,
                                                            int rows, int cols, int T, int W, int H, const uint32_t* __restrict__ fext, int L,
-                                                           int l, uint8_t* __restrict__ tiles, int n_tiles)
+                                                           int l, uint8_t* __restrict__ tiles, int n_tiles, int32_t* __restrict__ rects,
+                                                           int n_bands)
 {
     raise_wave_priority();
     const size_t frame = blockIdx.y;
     const int n_all = counters[frame * CTR_STRIDE + CTR_COUNT];
     const int n = n_all < cand_cap ? n_all : cand_cap;
     uint8_t* const flags = tiles + frame * n_tiles;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const Cand c = cands[frame * cand_cap + i];
-        if (c.raw < 0) continue;
-        const RefineOrigin o = refine_origin(c.x, c.y, c.next_width, c.next_height, rows, cols, T);
-        const uint32_t ext = fext[(size_t)c.t * L + l];
-        refine_tiles_for_each(refine_tiles(o, (int)(ext & 0xffff) + 1, (int)(ext >> 16) + 1, rows, cols, T, W, H), W, H, [&](int tile) {
-            if (tile >= 0 && tile < n_tiles) flags[tile] = 1;
-        });
+    int32_t* const iv = rects ? rects + frame * (size_t)n_bands * 2 : nullptr;
+    // The need rectangles (sbm_refine_tiles.h: refine_need) of the workgroup's candidates meet in LDS first: a candidate touches
+    // some 55 bands and the candidates of a frame touch the same ones, so a thread per candidate with global atomics would queue
+    // them on a few addresses of one L2 channel, and a thread that walks its candidate's bands alone leaves most of the workgroup
+    // idle (a frame of the bench has 105 candidates).  So the rectangles are listed in LDS, every wave takes every fourth of them
+    // with a lane per band -- one conflict-free ds_min / ds_max pair per rectangle -- and a thread per band then sends one
+    // non-returning atomic pair.  A level of more than MARK_LDS_BANDS bands (8192 rows) widens the record directly.
+    constexpr int MARK_LDS_BANDS = 1024;
+    __shared__ int32_t s_lo[MARK_LDS_BANDS], s_hi[MARK_LDS_BANDS];
+    __shared__ int4 s_rect[512];
+    __shared__ int s_n;
+    const bool in_lds = n_bands <= MARK_LDS_BANDS;
+    // (the trip count is the workgroup's: every thread reaches the barriers below)
+    for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {
+        const int i = base + (int)threadIdx.x;
+        RefineNeed need{{{0, -1, 0, 0}, {0, -1, 0, 0}}};
+        if (iv && in_lds) {
+            for (int b = threadIdx.x; b < n_bands; b += 256) s_lo[b] = 0x7fffffff, s_hi[b] = 0;
+            if (threadIdx.x == 0) s_n = 0;
+            __syncthreads();
+        }
+        if (i < n) {
+            const Cand c = cands[frame * cand_cap + i];
+            if (c.raw >= 0) {
+                const RefineOrigin o = refine_origin(c.x, c.y, c.next_width, c.next_height, rows, cols, T);
+                const uint32_t ext = fext[(size_t)c.t * L + l];
+                const int fw = (int)(ext & 0xffff) + 1, fh = (int)(ext >> 16) + 1;
+                refine_tiles_for_each(refine_tiles(o, fw, fh, rows, cols, T, W, H), W, H, [&](int tile) {
+                    if (tile >= 0 && tile < n_tiles) flags[tile] = 1;
+                });
+                if (iv) need = refine_need(o, fw, fh, rows, cols, T, W, H);
+            }
+        }
+        if (!iv) continue;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const BandRect r = need.r[q];
+            const int b0 = r.b0 > 0 ? r.b0 : 0, b1 = r.b1 < n_bands - 1 ? r.b1 : n_bands - 1;
+            if (b1 < b0) continue;
+            if (in_lds) {
+                s_rect[atomicAdd(&s_n, 1)] = int4{b0, b1, r.x0, r.x1};
+            } else {
+                for (int band = b0; band <= b1; ++band) {
+                    atomicMin(&iv[2 * band], r.x0);
+                    atomicMax(&iv[2 * band + 1], r.x1);
+                }
+            }
+        }
+        if (in_lds) {
+            __syncthreads();
+            const int n_rect = s_n;
+            for (int k = threadIdx.x >> 6; k < n_rect; k += 4) {
+                const int4 r = s_rect[k];
+                for (int band = r.x + (int)(threadIdx.x & 63); band <= r.y; band += 64) {
+                    atomicMin(&s_lo[band], r.z);
+                    atomicMax(&s_hi[band], r.w);
+                }
+            }
+            __syncthreads();
+            // A frame whose candidates fit one round of one workgroup (the usual case) is this workgroup's alone: plain 8-byte
+            // stores of every band, empty ones included.  (32 atomics on each 128-byte line of the record took the L2 longer than the
+            // rest of the launch.)
+            const bool alone = n <= 256;
+            for (int b = threadIdx.x; b < n_bands; b += 256) {
+                const int lo = s_lo[b], hi = s_hi[b];
+                if (alone) {
+                    *(int2*)&iv[2 * b] = int2{lo, hi};
+                } else if (lo < hi) {
+                    atomicMin(&iv[2 * b], lo);
+                    atomicMax(&iv[2 * b + 1], hi);
+                }
+            }
+            __syncthreads(); // (before the next round empties the arrays)
+        }
     }
 }
 
