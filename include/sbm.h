@@ -188,6 +188,33 @@ int sbm_match_batch_device_masked(sbm_ctx* ctx, const void* d_imgs, int64_t fram
                                   int64_t mask_stride, float threshold, void* d_out, int64_t cap, void* d_counts,
                                   void* stream);
 
+/* sbm_match_batch_device for frames that are not one block: the loop of Detector::match (line2Dup.cpp:1078) over frames
+ * that lie anywhere in device memory -- separately allocated tensors, the slots of a capture ring in any order,
+ * equal-sized windows cut out of larger frames.  d_frame_ptrs is a DEVICE array of n_frames 64-bit addresses; entry f is
+ * the first pixel of frame f.  All frames share rows, cols, stride (bytes per row, >= cols * channels, so a window's stride
+ * is its canvas's row) and channels; they may overlap, repeat, lie in different allocations and be more than 4 GiB apart.
+ * d_mask_ptrs is NULL or a device array of n_frames addresses of rows x cols masks (non-zero = keep, applied as
+ * sbm_match_batch_device_masked applies them); two entries may be equal, a zero entry is NOT allowed -- the caller's
+ * obligation, which the host cannot check without a synchronisation.
+ * The host never dereferences either table: the level-0 gradient kernels read them on `stream`, when they run.  The tables,
+ * the frames and the masks must stay valid and unchanged until the call's work on the stream has finished.  A replayed
+ * graph reads the tables at replay time, and its key holds the two table ADDRESSES and `flags` in place of d_imgs,
+ * frame_stride, d_masks and mask_stride -- not the tables' contents: one captured graph serves a stream of batches whose
+ * frames move, the caller rewriting the table (on the same stream) between replays.  The first-call rule of
+ * sbm_match_device is unchanged.
+ * flags: 0 or SBM_PTRS_ALIGNED4, the caller's promise that every frame pointer is a multiple of 4.  With it, stride % 4
+ * == 0, cols % 64 == 0 and a frame below 0x7ff00000 bytes, the source pass of the sparse level-0 path moves whole lines
+ * (sbm_get_source_form reports 2); without it the strided form runs (1).  Same results either way.  A BROKEN PROMISE IS
+ * UNDEFINED BEHAVIOUR: the line form loads dwords at the addresses it is given.
+ * d_out, cap, d_counts and the result mirror are laid out as for sbm_match_batch_device, and frame f's list is what
+ * sbm_match_device returns for that frame alone under its mask; the context is left in the state that call leaves.
+ * SBM_ERR_INVALID: NULL d_frame_ptrs, n_frames < 1, unknown flag bits, stride < cols * channels, and every geometry
+ * sbm_match_batch_device refuses (a stride above 16 with more than one frame). */
+#define SBM_PTRS_ALIGNED4 1
+int sbm_match_batch_device_ptrs(sbm_ctx* ctx, const void* d_frame_ptrs, int32_t n_frames, int32_t rows, int32_t cols,
+                                int32_t stride, int32_t channels, const void* d_mask_ptrs, int32_t flags,
+                                float threshold, void* d_out, int64_t cap, void* d_counts, void* stream);
+
 /* hipGraph replay of an entry point's launches: the kernel sequence of a call is recorded once per distinct argument
  * tuple (stream capture) and replayed with one hipGraphLaunch.
  *   enabled = -1 (default, "auto"): sbm_match_batch_device and sbm_match_templates_device replay once the caller keeps

@@ -43,7 +43,11 @@ ABI_SYMBOLS = [
     "sbm_get_source_form",
     "sbm_get_refine_form",
     "sbm_get_sparse_items",
+    "sbm_match_batch_device_ptrs",
 ]
+
+# sbm_match_batch_device_ptrs flags: the caller promises that every frame pointer is a multiple of 4
+SBM_PTRS_ALIGNED4 = 1
 
 
 class SbmConfig(C.Structure):
@@ -175,6 +179,7 @@ def lib() -> C.CDLL:
     L.sbm_match_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp]
     L.sbm_match_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp]
     L.sbm_match_batch_device_masked.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, f32, vp, i64, vp, vp]
+    L.sbm_match_batch_device_ptrs.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, i64, vp, vp]
     L.sbm_match_batch_host_begin_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, i64, i32]
     L.sbm_match_batch_host_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, i32]
     L.sbm_get_quantized_frame.argtypes = [vp, i32, i32, vp]
@@ -349,6 +354,17 @@ class Context:
                                                    channels, C.c_void_p(d_masks) if d_masks else None, mask_stride,
                                                    C.c_float(threshold), C.c_void_p(d_out), cap, C.c_void_p(d_counts),
                                                    C.c_void_p(stream) if stream else None))
+
+    def match_batch_device_ptrs(self, d_frame_ptrs: int, n_frames: int, rows: int, cols: int, stride: int, channels: int,
+                                threshold: float, d_out: int, cap: int, d_counts: int, d_mask_ptrs: int = 0, flags: int = 0,
+                                stream: int = 0):
+        """match_batch_device for frames that are not one block: d_frame_ptrs is a DEVICE array of n_frames 64-bit addresses
+        (entry f: frame f's first pixel), d_mask_ptrs 0 or a device array of n_frames mask addresses (no zero entry); the
+        kernels read both on the stream, the host never does.  flags: 0 or SBM_PTRS_ALIGNED4."""
+        _check(lib().sbm_match_batch_device_ptrs(self._h, C.c_void_p(d_frame_ptrs) if d_frame_ptrs else None, n_frames, rows, cols,
+                                                 stride, channels, C.c_void_p(d_mask_ptrs) if d_mask_ptrs else None, flags,
+                                                 C.c_float(threshold), C.c_void_p(d_out), cap, C.c_void_p(d_counts),
+                                                 C.c_void_p(stream) if stream else None))
 
     def nms_batch_device(self, d_recs: int, d_counts: int, cap: int, n_frames: int, d_out: int, out_cap: int, d_out_counts: int,
                          score_threshold: float, nms_threshold: float, eta: float = 1.0, top_k: int = 0, n_parts: int = 1,

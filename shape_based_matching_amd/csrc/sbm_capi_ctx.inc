@@ -552,6 +552,9 @@ int upload_geo(sbm_ctx* c, hipStream_t s)
 // segment lanes of the packed last strip (0: none); SBM_QS_PACK=0 is the A/B knob
 static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs, int stride, int64_t mask_fs)
 {
+    // frames named by a device table (sbm_frame_ptrs_plan.h) lie anywhere: no 32-bit offset reaches from one to the next.  The
+    // table form is launched unpacked (DESIGN.md section 5 has the measurement behind that choice)
+    if (fs_is_table(img_fs)) return 0;
     const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, ch, frames, mask_fs) : 0;
     if (!lanes) return 0;
     // the frames of a group are addressed by 32-bit per-lane offsets from the group's first frame: the caller's frame
@@ -633,6 +636,12 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     if (!d_mask) mask_fs = 0; // mask_fs: bytes between the frames' masks, 0 = one mask for all frames
     if (row_hi < 0) row_hi = rows;
     const bool band = row_lo > 0 || row_hi < rows;
+    // The table form (sbm_match_batch_device_ptrs): img_fs says so and holds the call's flags, d_img is the device array of frame
+    // addresses and d_mask, if not null, the array of mask addresses.  The caller's level-0 launch only -- whole, without float outputs.
+    const bool table = fs_is_table(img_fs);
+    if (table && (band || tile_band || d_mag || d_ori || (d_mask && !fs_is_table(mask_fs)) || (form && form->stage != QS_SOURCE)))
+        return fail(SBM_ERR_STATE, "a table of frame pointers names the frames of a whole level-0 launch only");
+    if (!table && fs_is_table(mask_fs)) return fail(SBM_ERR_STATE, "a table of mask pointers needs a table of frame pointers");
     // tile_band: rows [row_lo, row_hi) as a band of whole rows of 16 x 64 TILES (row_lo a multiple of 16, row_hi too or the
     // last row): the latency path of sbm_match, whose level-0 launches follow the frame's upload band by band
     const int tile_row0 = tile_band ? row_lo / QT_R : 0;
@@ -645,13 +654,15 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     if (form && form->stage == QS_SOURCE) hs = source_pass_rows();
     // The source pass as whole lines (sbm_source_lines.h) wherever the caller's layout admits it; every other layout -- a row pad
     // of 13 bytes, an odd frame stride -- stays with the strided form below.
-    if (form && form->stage == QS_SOURCE && tuning().source_lines &&
-        source_lines_ok((uint64_t)(uintptr_t)d_img, stride, img_fs, frames, rows, cols, ch)) {
+    // Behind a table the host cannot see the frames' addresses: the caller's promise (SBM_PTRS_ALIGNED4) stands in for them.
+    const bool lines = table ? frame_ptrs_source_lines(fs_table_flags(img_fs), stride, rows, cols, ch, tuning().source_lines != 0)
+                             : tuning().source_lines && source_lines_ok((uint64_t)(uintptr_t)d_img, stride, img_fs, frames, rows, cols, ch);
+    if (form && form->stage == QS_SOURCE && lines) {
         QSArgs a;
         memset(&a, 0, sizeof a);
         a.img = d_img;
         a.pyr = d_pyr;
-        a.img_fs = img_fs;
+        a.img_fs = table ? 0 : img_fs;
         a.pyr_fs = pyr_fs;
         a.rows = rows;
         a.cols = cols;
@@ -665,7 +676,9 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.keep = form->keep;
         a.keep_fs = form->keep_fs;
         const dim3 g((unsigned)((sl_items(cols, a.n_rblocks, frames) + 3) / 4));
-        if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines<1>), g, dim3(256), 0, s, a);
+        if (table && ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines_ptrs<1>), g, dim3(256), 0, s, a);
+        else if (table) SBM_LAUNCH(c, "k_quantize", (k_source_lines_ptrs<3>), g, dim3(256), 0, s, a);
+        else if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines<1>), g, dim3(256), 0, s, a);
         else SBM_LAUNCH(c, "k_quantize", (k_source_lines<3>), g, dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
         c->source_form = 2;
@@ -678,10 +691,10 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.mask = d_mask;
         a.out = d_out;
         a.pyr = d_pyr;
-        a.img_fs = img_fs;
+        a.img_fs = table ? 0 : img_fs;
         a.out_fs = out_fs;
         a.pyr_fs = pyr_fs;
-        a.mask_fs = mask_fs;
+        a.mask_fs = table ? 0 : mask_fs;
         a.rows = rows;
         a.cols = cols;
         a.stride = stride;
@@ -724,8 +737,17 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
             else if (stage == QS_SPARSE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SPARSE>), g, dim3(256), 0, s, a); \
             else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                     \
         } while (0)
-        if (ch == 1) SBM_QS(1);
+        // (the table form has the whole row loop and the source pass; the sparse launch reads the retained copy)
+#define SBM_QS_PTRS(CH_)                                                                                                    \
+        do {                                                                                                                \
+            if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_SOURCE>), g, dim3(256), 0, s, a); \
+            else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                \
+        } while (0)
+        if (table && ch == 1) SBM_QS_PTRS(1);
+        else if (table) SBM_QS_PTRS(3);
+        else if (ch == 1) SBM_QS(1);
         else SBM_QS(3);
+#undef SBM_QS_PTRS
 #undef SBM_QS
         HIP_TRY(hipGetLastError());
         if (stage == QS_SOURCE) c->source_form = 1;
@@ -735,19 +757,23 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     if (tile_band && (row_lo % QT_R || (row_hi % QT_R && row_hi != rows))) return fail(SBM_ERR_INVALID, "a band of tiles must start and end on tile rows");
     // many tiles per CU (a batch of frames): 512-thread blocks, four of them per CU; else 1024-thread blocks (tile latency)
     const bool many = (int64_t)grid.x * grid.y * grid.z >= 2048;
-#define SBM_QUANTIZE(CH_, WF_)                                                                                              \
+    // (the table form: d_img / d_mask are the tables, the two strides are not read)
+    const int64_t k_img_fs = table ? 0 : img_fs, k_mask_fs = table ? 0 : mask_fs;
+#define SBM_QUANTIZE(CH_, WF_, PTRS_)                                                                                       \
     do {                                                                                                                    \
         if (many)                                                                                                           \
-            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_THROUGHPUT>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, \
-                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);     \
+            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_THROUGHPUT, PTRS_>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, \
+                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs); \
         else                                                                                                                \
-            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
-                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);             \
+            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY, PTRS_>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
+                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);         \
     } while (0)
-    if (ch == 1 && !wf) SBM_QUANTIZE(1, false);
-    else if (ch == 1) SBM_QUANTIZE(1, true);
-    else if (!wf) SBM_QUANTIZE(3, false);
-    else SBM_QUANTIZE(3, true);
+    if (table && ch == 1) SBM_QUANTIZE(1, false, true);
+    else if (table) SBM_QUANTIZE(3, false, true);
+    else if (ch == 1 && !wf) SBM_QUANTIZE(1, false, false);
+    else if (ch == 1) SBM_QUANTIZE(1, true, false);
+    else if (!wf) SBM_QUANTIZE(3, false, false);
+    else SBM_QUANTIZE(3, true, false);
 #undef SBM_QUANTIZE
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1005,8 +1031,13 @@ int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const u
             const int n = c->rows[l] * c->cols[l];
             const int64_t dst_fs = mask_fs ? (int64_t)n : 0;
             if (mask_fs && frames > c->mask_frames) return fail(SBM_ERR_STATE, "level %d holds %d masks, the batch has %d frames", l, c->mask_frames, frames);
-            SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096), mask_fs ? frames : 1), dim3(256), 0, s, mask,
-                       c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l], mask_fs, dst_fs);
+            if (fs_is_table(mask_fs)) // level 0's masks are named by the caller's table; from here on they are the context's own
+                SBM_LAUNCH(c, "k_resize_mask", k_resize_mask_ptrs, dim3(std::min((n + 255) / 256, 4096), frames), dim3(256), 0, s,
+                           reinterpret_cast<const uint8_t* const*>(mask), c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l],
+                           c->cols[l], dst_fs);
+            else
+                SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096), mask_fs ? frames : 1), dim3(256), 0, s, mask,
+                           c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l], mask_fs, dst_fs);
             HIP_TRY(hipGetLastError());
             mask = c->d_mask[l].as<uint8_t>();
             mask_fs = dst_fs;
@@ -1256,6 +1287,8 @@ int check_match_call(const sbm_ctx* c, const MatchCall& m)
     if (m.frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
     if (int e = check_stride(m.stride, m.cols, m.ch)) return e;
     if (m.frames > 1 && m.frame_stride < (int64_t)m.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
+    // (one frame: the stride is not read -- but it must not be the mark of the table form, sbm_frame_ptrs_plan.h)
+    if (fs_is_table(m.frame_stride)) return fail(SBM_ERR_INVALID, "frame_stride out of range");
     if (m.mask_stride && (!m.mask || m.mask_stride < (int64_t)m.rows * m.cols)) return fail(SBM_ERR_INVALID, "mask_stride smaller than one mask");
     return 0;
 }

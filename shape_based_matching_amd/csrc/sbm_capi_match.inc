@@ -296,6 +296,23 @@ int sbm_match_batch_device_masked(sbm_ctx* c, const void* d_imgs, int64_t frame_
     return match_or_replay(c, s, m, n_frames);
 }
 
+// The frames (and masks) are named by device arrays of addresses that only the level-0 gradient launch reads, on the stream
+// (launch_quantize: the table forms of its kernels).  The call travels as every batch call does, with the tables' addresses in the
+// place of the image and mask pointers and the table form's mark -- which holds the flags -- in the place of the two strides
+// (sbm_frame_ptrs_plan.h): that tuple is also the key of its captured graph, and the tables' contents are no part of it.
+int sbm_match_batch_device_ptrs(sbm_ctx* c, const void* d_frame_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                int32_t channels, const void* d_mask_ptrs, int32_t flags, float threshold, void* d_out, int64_t cap,
+                                void* d_counts, void* stream)
+{
+    if (!c || !d_out || !d_counts) return fail(SBM_ERR_INVALID, "null argument");
+    if (const int e = frame_ptrs_check(d_frame_ptrs != nullptr, n_frames, cols, stride, channels, flags)) return fail(SBM_ERR_INVALID, "%s", frame_ptrs_error(e));
+    const MatchCall m{(const uint8_t*)d_frame_ptrs, rows, cols, stride, channels, (const uint8_t*)d_mask_ptrs, threshold, (sbm_match_rec*)d_out, cap,
+                      (int32_t*)d_counts, n_frames, frame_ptrs_fs(flags), d_mask_ptrs ? FP_TABLE_FS : 0};
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s)) return e;
+    return match_or_replay(c, s, m, n_frames);
+}
+
 int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
 {
     if (!c || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");

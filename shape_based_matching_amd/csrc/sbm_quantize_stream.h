@@ -37,6 +37,11 @@
 // and the work items are ordered row block first, so that the three workgroups a CU holds come from three regions of
 // the image (quantize_stream_item).
 //
+// Table form (PTRS, k_quantize_stream_ptrs): the frames of a batch are named by a device array of 64-bit addresses instead of
+// base + frame * img_fs -- QSArgs::img IS that array, and QSArgs::mask, when not null, an array of mask addresses.  A work item
+// reads its frame's entry once, with a scalar load (the frame is wave-uniform), and is otherwise the item of the contiguous form.
+// The last strip is never packed in this form: a packed wave addresses its frames by 32-bit lane offsets from the first.
+//
 // Requires cols % 4 == 0 and cols >= 4 (every pyramid level of a match() frame with T in {4, 8, ...} satisfies
 // it); other geometries and the float outputs (magnitude / angle of the stage API and of training) stay with
 // k_quantize.
@@ -68,8 +73,8 @@ constexpr int QS_USEFUL = (64 - 2 * QS_HALO_LANES) * QS_LANE_PX; // 240 useful c
 constexpr int QS_PREFETCH = 4;                                   // source rows in flight ahead of the one being consumed
 
 struct QSArgs {
-    const uint8_t* img;  // frame 0, level image, `stride` bytes per row, CH interleaved channels
-    const uint8_t* mask; // frame 0's, rows x cols, may be null
+    const uint8_t* img;  // frame 0, level image, `stride` bytes per row, CH interleaved channels (table form: the table of frame addresses)
+    const uint8_t* mask; // frame 0's, rows x cols, may be null (table form: the table of mask addresses, or null)
     uint8_t* out;        // rows x cols one-hot orientation bytes
     uint8_t* pyr;        // (rows/2) x (cols/2) x CH, may be null
     int64_t img_fs, out_fs, pyr_fs; // bytes from one frame of the batch to the next
@@ -115,6 +120,12 @@ struct QSArgs {
 //              with the record of need rectangles, unless its strip, counted from the left end of what the refinement can read
 //              in its rows, begins inside that hull and meets a flagged tile (gradient_rect_item_needed)
 enum QSStage : int { QS_WHOLE = 0, QS_SOURCE = 1, QS_SPARSE = 2 };
+
+// entry `frame` of a device table of frame (or mask) addresses: wave-uniform, one scalar load
+__device__ __forceinline__ const uint8_t* qs_table_entry(const uint8_t* table, int frame)
+{
+    return reinterpret_cast<const uint8_t* const*>(table)[frame];
+}
 
 // Gaussian / pyrDown weights as packed pairs (lo | hi << 16)
 #define QS_K(lo, hi) ((uint32_t)(lo) | ((uint32_t)(hi) << 16))
@@ -164,7 +175,7 @@ __device__ __forceinline__ wv::V qs_vote_word(wv::V v, wv::P keep)
 // row).  No constant-row shortcut: there is no arithmetic worth skipping.  The window holds 6 rows (pyrDown reads 5), two rows per
 // pyrDown row, so a group of 6 iterations has static register indices and a static row parity: the item's first loaded row
 // R0 - 2 is even (hs and row_lo are), and pyrDown row oy is due when source row 2 oy + 2 has entered the window.
-template <int CH>
+template <int CH, bool PTRS = false>
 __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip, int rb, int frame, int nseg)
 {
     using namespace wv;
@@ -174,7 +185,7 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
     if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
     const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
     const int cb = strip * QS_USEFUL - QS_HALO_LANES * QS_LANE_PX;
-    const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
     const int drows = rows >> 1, dcols = cols >> 1;
 
     const V lane = lane_id();
@@ -311,13 +322,13 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
 
 // One work item: strip `strip`, output rows [rb*hs, min(rb*hs+hs, rows)), frame `frame`.
 // nseg == 0: the whole wave is strip `strip` of frame `frame`; nseg > 0: packed last strip of frames frame .. frame+nseg-1
-template <int CH, int STAGE = QS_WHOLE>
+template <int CH, int STAGE = QS_WHOLE, bool PTRS = false>
 __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0)
 {
     using namespace wv;
     constexpr int ND = CH == 3 ? 3 : 1; // source dwords per lane and row
     if (STAGE == QS_SOURCE) { // a loop of its own
-        quantize_source_wave<CH>(a, strip, rb, frame, nseg);
+        quantize_source_wave<CH, PTRS>(a, strip, rb, frame, nseg);
         return;
     }
     int x_first = strip * QS_USEFUL; // first useful column of the item's strip
@@ -353,12 +364,13 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
     const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
     const int cb = x_first - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
-    const uint8_t* img = a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
     uint8_t* out = a.out + (int64_t)frame * a.out_fs;
     uint8_t* pyr = STAGE != QS_SPARSE && a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;
     // the frame's own mask (quantize(): one mask per match() call).  No select on a.mask: without a mask mask_fs is 0, so the
     // sum is the null pointer itself and takes the argument's place in the scalar registers -- nothing more stays live
-    const uint8_t* mask = a.mask + (int64_t)frame * a.mask_fs;
+    // (table form: the frame's entry of the mask table, where there is one)
+    const uint8_t* mask = PTRS ? (a.mask ? qs_table_entry(a.mask, frame) : nullptr) : a.mask + (int64_t)frame * a.mask_fs;
     const int drows = rows >> 1, dcols = cols >> 1;
 
     // ---- per-lane constants ----
@@ -768,9 +780,16 @@ __host__ __device__ inline int quantize_stream_items(const QSArgs& a)
     return n_full * a.n_rblocks * a.frames + (a.pack_lanes ? a.n_rblocks * a.pack_groups : 0);
 }
 
-template <int CH, int STAGE = QS_WHOLE>
+template <int CH, int STAGE = QS_WHOLE, bool PTRS = false>
 __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
 {
+    if (PTRS) { // never packed: (strip, row block, frame) in the order below and nothing else
+        const int per_rb = a.n_strips * a.frames;
+        if (a.pack_lanes || item >= per_rb * a.n_rblocks) return;
+        const int rb = item / per_rb, r = item - rb * per_rb;
+        quantize_stream_wave<CH, STAGE, PTRS>(a, r % a.n_strips, rb, r / a.n_strips, 0);
+        return;
+    }
     // Order: row block slowest, then frame, then strip.  All work items are resident at once (one round) and the
     // dispatcher deals workgroups to the 256 CUs round-robin, so a CU's three workgroups are 256 and 512 workgroups
     // apart: with the frame slowest those were the SAME region of three different frames -- on a frame that is part
@@ -813,6 +832,14 @@ __global__ __launch_bounds__(256) void k_quantize_stream(const QSArgs a)
     // (row counters, stage gating, row base addresses) lives in SGPRs and branches are scalar
     const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     quantize_stream_item<CH, STAGE>(a, item);
+}
+
+// the table form: a.img (and a.mask, if not null) is a device array of a.frames addresses; launched with a.pack_lanes == 0
+template <int CH, int STAGE = QS_WHOLE>
+__global__ __launch_bounds__(256) void k_quantize_stream_ptrs(const QSArgs a)
+{
+    const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    quantize_stream_item<CH, STAGE, true>(a, item);
 }
 #endif
 

@@ -169,7 +169,10 @@ __device__ __forceinline__ uint32_t vote_word(uint32_t v)
     return v ? w : 1u;
 }
 
-template <int CH, bool WITH_FLOAT, int QN>
+// PTRS (the table form of the batched match): img is a device array of gridDim.z frame addresses and mask, if not null, one of
+// mask addresses (an entry may not be null); frame blockIdx.z's pointers are read from them when the kernel runs, and img_fs and
+// mask_fs are not read at all.
+template <int CH, bool WITH_FLOAT, int QN, bool PTRS = false>
 __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img, int rows, int cols,
                                                   int stride, const uint8_t* __restrict__ mask,
                                                   float thr_sq, uint8_t* __restrict__ out,
@@ -179,8 +182,13 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
 {
     // a batch of frames of one geometry: frame = blockIdx.z, *_fs = bytes from one frame to the next (mask_fs = 0: the
     // frames share one mask)
-    if (mask) mask += (int64_t)blockIdx.z * mask_fs;
-    img += (size_t)blockIdx.z * img_fs;
+    if (PTRS) {
+        if (mask) mask = reinterpret_cast<const uint8_t* const*>(mask)[blockIdx.z];
+        img = reinterpret_cast<const uint8_t* const*>(img)[blockIdx.z];
+    } else {
+        if (mask) mask += (int64_t)blockIdx.z * mask_fs;
+        img += (size_t)blockIdx.z * img_fs;
+    }
     out += (size_t)blockIdx.z * out_fs;
     if (pyr_out) pyr_out += (size_t)blockIdx.z * pyr_fs;
     __shared__ uint32_t s_src[CH][QS_R][QS_W / 4]; // u8 x4
@@ -699,6 +707,24 @@ __global__ __launch_bounds__(256) void k_resize_mask(const uint8_t* __restrict__
 {
     top_wave_priority(); // a small kernel between two gradient launches of its batch
     src += (int64_t)blockIdx.y * src_fs;
+    dst += (int64_t)blockIdx.y * dst_fs;
+    const double fx = (double)cols / dcols, fy = (double)rows / drows;
+    const int n = drows * dcols;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+        int x = idx % dcols, y = idx / dcols;
+        int sx = (int)floor(x * fx), sy = (int)floor(y * fy);
+        sx = sx > cols - 1 ? cols - 1 : sx;
+        sy = sy > rows - 1 ? rows - 1 : sy;
+        dst[idx] = src[(size_t)sy * cols + sx];
+    }
+}
+
+// ... the level-0 masks named by a device array of gridDim.y addresses (the table form of the batched match)
+__global__ __launch_bounds__(256) void k_resize_mask_ptrs(const uint8_t* const* __restrict__ masks, int rows, int cols,
+                                                          uint8_t* __restrict__ dst, int drows, int dcols, int64_t dst_fs)
+{
+    top_wave_priority();
+    const uint8_t* src = masks[blockIdx.y];
     dst += (int64_t)blockIdx.y * dst_fs;
     const double fx = (double)cols / dcols, fy = (double)rows / drows;
     const int n = drows * dcols;

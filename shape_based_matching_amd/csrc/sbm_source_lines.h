@@ -67,7 +67,8 @@ namespace sbm {
 constexpr int SL_PREFETCH = 4; // source rows in flight ahead of the one being consumed (the ring holds 6)
 
 // One work item: strip `strip` (256 columns), rows sl_rows(rb, ...) of frame `frame`.
-template <int CH>
+// PTRS: the table form (sbm_quantize_stream.h) -- a.img is a device array of frame addresses, each a multiple of 4 by the caller's promise.
+template <int CH, bool PTRS = false>
 __device__ __forceinline__ void source_lines_wave(const QSArgs& a, int strip, int rb, int frame)
 {
     using namespace wv;
@@ -83,7 +84,8 @@ __device__ __forceinline__ void source_lines_wave(const QSArgs& a, int strip, in
     const V c0 = splat((uint32_t)(strip * SL_STRIP)) + (lane << 2); // first column of this lane
     const P in_img = lt_i(c0, splat((uint32_t)cols));               // not a lane of the cut
     const V row_off = select(in_img, CH == 3 ? c0 + (c0 << 1) : c0, BUF_DROP); // the lane's bytes in a source row and in a row of the copy
-    const Buf src_buf = make_buf(const_cast<uint8_t*>(a.img) + (int64_t)frame * a.img_fs, sl_frame_bytes(rows, cols, CH, a.stride));
+    const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
+    const Buf src_buf = make_buf(const_cast<uint8_t*>(img), sl_frame_bytes(rows, cols, CH, a.stride));
     const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, (uint32_t)rows * (uint32_t)cols * CH);
     const Buf pyr_buf = make_buf(a.pyr + (int64_t)frame * a.pyr_fs, (uint32_t)drows * (uint32_t)dcols * CH);
     const V pyr_off = select(p_and(in_img, eq(lane & 1u, splat(0u))), CH == 3 ? (c0 >> 1) + ((c0 >> 1) << 1) : (c0 >> 1), BUF_DROP);
@@ -193,13 +195,13 @@ __device__ __forceinline__ void source_lines_wave(const QSArgs& a, int strip, in
     }
 }
 
-template <int CH>
+template <int CH, bool PTRS = false>
 __device__ __forceinline__ void source_lines_item(const QSArgs& a, int item)
 {
     const int n_strips = sl_strips(a.cols);
     if (item >= n_strips * a.n_rblocks * a.frames) return;
     const SlItem it = sl_item(item, n_strips, a.frames);
-    source_lines_wave<CH>(a, it.strip, it.rb, it.frame);
+    source_lines_wave<CH, PTRS>(a, it.strip, it.rb, it.frame);
 }
 
 #ifndef SBM_WAVE_EMU
@@ -209,6 +211,14 @@ __global__ __launch_bounds__(256) void k_source_lines(const QSArgs a)
 {
     const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     source_lines_item<CH>(a, item);
+}
+
+// the table form
+template <int CH>
+__global__ __launch_bounds__(256) void k_source_lines_ptrs(const QSArgs a)
+{
+    const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    source_lines_item<CH, true>(a, item);
 }
 #endif
 
