@@ -215,6 +215,28 @@ int sbm_match_batch_device_ptrs(sbm_ctx* ctx, const void* d_frame_ptrs, int32_t 
                                 int32_t stride, int32_t channels, const void* d_mask_ptrs, int32_t flags,
                                 float threshold, void* d_out, int64_t cap, void* d_counts, void* stream);
 
+/* sbm_match_batch_device_ptrs for PLANAR frames of three channels: a [B, 3, H, W] image batch, the [3, H, W] output of a GPU
+ * JPEG decoder, the three planes of a decoder or ISP surface -- matched where they lie, without an interleaving copy.
+ * d_plane_ptrs is a DEVICE array of 3 * n_frames 64-bit addresses; entry 3 f + c is the first byte of channel c of frame f, and
+ * channel c is what the reference sees as interleaved channel c (B, G, R for a cv::imread frame).  The order is the caller's:
+ * listing the planes of an RGB tensor as (2, 1, 0) IS the BGR frame.  `stride` is the bytes per row of a plane, shared by all
+ * planes of all frames, >= cols (a window of a larger [3, H, W] canvas: the canvas's W).  Planes need no alignment; they may
+ * overlap, repeat (the three entries of a frame may be equal) and lie in different allocations more than 4 GiB apart.  Always
+ * three channels: a gray planar frame is a frame of sbm_match_batch_device_ptrs with channels = 1.
+ * d_mask_ptrs, the tables' lifetime, the graph key (the two table addresses, not their contents; a _ptrs call at the same table
+ * address is another graph), d_out, cap, d_counts, the result mirror and the state the context is left in are those of
+ * sbm_match_batch_device_ptrs.  Inside the context everything stays interleaved: level 1's image, and the retained copy of level
+ * 0 that the sparse path and the accessors read (sbm_get_quantized_frame, sbm_match_templates) -- the source pass re-interleaves
+ * the planes as it copies them.  That pass is always the strided form (sbm_get_source_form reports 1).
+ * flags is reserved and must be 0.
+ * SBM_ERR_INVALID: NULL d_plane_ptrs, n_frames < 1, flags != 0, stride < cols, and every geometry sbm_match_batch_device refuses
+ * (a stride above 16 with more than one frame).
+ * Not offered: the C++ facade (cv::Mat has no planar three-channel form), the sharded, banded and host-batch entry points, a
+ * line-shaped source pass, four-channel surfaces. */
+int sbm_match_batch_device_planes(sbm_ctx* ctx, const void* d_plane_ptrs, int32_t n_frames, int32_t rows, int32_t cols,
+                                  int32_t stride, const void* d_mask_ptrs, int32_t flags, float threshold, void* d_out,
+                                  int64_t cap, void* d_counts, void* stream);
+
 /* hipGraph replay of an entry point's launches: the kernel sequence of a call is recorded once per distinct argument
  * tuple (stream capture) and replayed with one hipGraphLaunch.
  *   enabled = -1 (default, "auto"): sbm_match_batch_device and sbm_match_templates_device replay once the caller keeps

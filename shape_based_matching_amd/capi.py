@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "sbm_get_refine_form",
     "sbm_get_sparse_items",
     "sbm_match_batch_device_ptrs",
+    "sbm_match_batch_device_planes",
 ]
 
 # sbm_match_batch_device_ptrs flags: the caller promises that every frame pointer is a multiple of 4
@@ -180,6 +181,7 @@ def lib() -> C.CDLL:
     L.sbm_match_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp]
     L.sbm_match_batch_device_masked.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, f32, vp, i64, vp, vp]
     L.sbm_match_batch_device_ptrs.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, i64, vp, vp]
+    L.sbm_match_batch_device_planes.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, f32, vp, i64, vp, vp]
     L.sbm_match_batch_host_begin_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, i64, i32]
     L.sbm_match_batch_host_masked.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, i32]
     L.sbm_get_quantized_frame.argtypes = [vp, i32, i32, vp]
@@ -365,6 +367,17 @@ class Context:
                                                  stride, channels, C.c_void_p(d_mask_ptrs) if d_mask_ptrs else None, flags,
                                                  C.c_float(threshold), C.c_void_p(d_out), cap, C.c_void_p(d_counts),
                                                  C.c_void_p(stream) if stream else None))
+
+    def match_batch_device_planes(self, d_plane_ptrs: int, n_frames: int, rows: int, cols: int, stride: int, threshold: float,
+                                  d_out: int, cap: int, d_counts: int, d_mask_ptrs: int = 0, flags: int = 0, stream: int = 0):
+        """match_batch_device_ptrs for planar frames of three channels: d_plane_ptrs is a DEVICE array of 3 * n_frames 64-bit
+        addresses (entry 3 f + c: channel c of frame f, in the reference's order B, G, R -- the caller's to choose), stride the bytes
+        per row of a plane, d_mask_ptrs as for match_batch_device_ptrs; flags is reserved (0).  torch_frames.plane_table writes
+        the table for [B, 3, H, W] tensors."""
+        _check(lib().sbm_match_batch_device_planes(self._h, C.c_void_p(d_plane_ptrs) if d_plane_ptrs else None, n_frames, rows, cols,
+                                                   stride, C.c_void_p(d_mask_ptrs) if d_mask_ptrs else None, flags,
+                                                   C.c_float(threshold), C.c_void_p(d_out), cap, C.c_void_p(d_counts),
+                                                   C.c_void_p(stream) if stream else None))
 
     def nms_batch_device(self, d_recs: int, d_counts: int, cap: int, n_frames: int, d_out: int, out_cap: int, d_out_counts: int,
                          score_threshold: float, nms_threshold: float, eta: float = 1.0, top_k: int = 0, n_parts: int = 1,

@@ -554,7 +554,8 @@ static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs,
 {
     // frames named by a device table (sbm_frame_ptrs_plan.h) lie anywhere: no 32-bit offset reaches from one to the next.  The
     // table form is launched unpacked (DESIGN.md section 5 has the measurement behind that choice)
-    if (fs_is_table(img_fs)) return 0;
+    // (a table of planes, sbm_frame_planes_plan.h, likewise)
+    if (fs_names_table(img_fs)) return 0;
     const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, ch, frames, mask_fs) : 0;
     if (!lanes) return 0;
     // the frames of a group are addressed by 32-bit per-lane offsets from the group's first frame: the caller's frame
@@ -638,9 +639,13 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     const bool band = row_lo > 0 || row_hi < rows;
     // The table form (sbm_match_batch_device_ptrs): img_fs says so and holds the call's flags, d_img is the device array of frame
     // addresses and d_mask, if not null, the array of mask addresses.  The caller's level-0 launch only -- whole, without float outputs.
-    const bool table = fs_is_table(img_fs);
+    // The plane form (sbm_match_batch_device_planes) is a table form too: img_fs is its own mark, d_img the device array of three
+    // plane addresses per frame, d_mask as above; three channels, and `stride` is a plane's row.
+    const bool planes = fs_is_planes(img_fs);
+    const bool table = fs_is_table(img_fs) || planes;
     if (table && (band || tile_band || d_mag || d_ori || (d_mask && !fs_is_table(mask_fs)) || (form && form->stage != QS_SOURCE)))
         return fail(SBM_ERR_STATE, "a table of frame pointers names the frames of a whole level-0 launch only");
+    if (planes && ch != FPL_CHANNELS) return fail(SBM_ERR_STATE, "a table of plane pointers names frames of three channels");
     if (!table && fs_is_table(mask_fs)) return fail(SBM_ERR_STATE, "a table of mask pointers needs a table of frame pointers");
     // tile_band: rows [row_lo, row_hi) as a band of whole rows of 16 x 64 TILES (row_lo a multiple of 16, row_hi too or the
     // last row): the latency path of sbm_match, whose level-0 launches follow the frame's upload band by band
@@ -655,7 +660,9 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     // The source pass as whole lines (sbm_source_lines.h) wherever the caller's layout admits it; every other layout -- a row pad
     // of 13 bytes, an odd frame stride -- stays with the strided form below.
     // Behind a table the host cannot see the frames' addresses: the caller's promise (SBM_PTRS_ALIGNED4) stands in for them.
-    const bool lines = table ? frame_ptrs_source_lines(fs_table_flags(img_fs), stride, rows, cols, ch, tuning().source_lines != 0)
+    // Planes have no line form.
+    const bool lines = planes ? frame_planes_source_lines(fs_planes_flags(img_fs), stride, rows, cols, tuning().source_lines != 0)
+                       : table ? frame_ptrs_source_lines(fs_table_flags(img_fs), stride, rows, cols, ch, tuning().source_lines != 0)
                              : tuning().source_lines && source_lines_ok((uint64_t)(uintptr_t)d_img, stride, img_fs, frames, rows, cols, ch);
     if (form && form->stage == QS_SOURCE && lines) {
         QSArgs a;
@@ -743,7 +750,9 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
             if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_SOURCE>), g, dim3(256), 0, s, a); \
             else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                \
         } while (0)
-        if (table && ch == 1) SBM_QS_PTRS(1);
+        if (planes && stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_SOURCE>), g, dim3(256), 0, s, a);
+        else if (planes) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_WHOLE>), g, dim3(256), 0, s, a);
+        else if (table && ch == 1) SBM_QS_PTRS(1);
         else if (table) SBM_QS_PTRS(3);
         else if (ch == 1) SBM_QS(1);
         else SBM_QS(3);
@@ -768,7 +777,13 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
             SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY, PTRS_>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
                        d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);         \
     } while (0)
-    if (table && ch == 1) SBM_QUANTIZE(1, false, true);
+    if (planes && many)
+        SBM_LAUNCH(c, "k_quantize", (k_quantize<3, false, QN_THROUGHPUT, true, true>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, stride, d_mask,
+                   thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);
+    else if (planes)
+        SBM_LAUNCH(c, "k_quantize", (k_quantize<3, false, QN_LATENCY, true, true>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, d_mask,
+                   thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);
+    else if (table && ch == 1) SBM_QUANTIZE(1, false, true);
     else if (table) SBM_QUANTIZE(3, false, true);
     else if (ch == 1 && !wf) SBM_QUANTIZE(1, false, false);
     else if (ch == 1) SBM_QUANTIZE(1, true, false);
@@ -1288,7 +1303,8 @@ int check_match_call(const sbm_ctx* c, const MatchCall& m)
     if (int e = check_stride(m.stride, m.cols, m.ch)) return e;
     if (m.frames > 1 && m.frame_stride < (int64_t)m.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
     // (one frame: the stride is not read -- but it must not be the mark of the table form, sbm_frame_ptrs_plan.h)
-    if (fs_is_table(m.frame_stride)) return fail(SBM_ERR_INVALID, "frame_stride out of range");
+    // (... nor that of the plane form, sbm_frame_planes_plan.h)
+    if (fs_names_table(m.frame_stride)) return fail(SBM_ERR_INVALID, "frame_stride out of range");
     if (m.mask_stride && (!m.mask || m.mask_stride < (int64_t)m.rows * m.cols)) return fail(SBM_ERR_INVALID, "mask_stride smaller than one mask");
     return 0;
 }

@@ -313,6 +313,23 @@ int sbm_match_batch_device_ptrs(sbm_ctx* c, const void* d_frame_ptrs, int32_t n_
     return match_or_replay(c, s, m, n_frames);
 }
 
+// Planar frames: the table holds three plane addresses per frame and only the level-0 gradient launch reads it (launch_quantize: the
+// plane forms of its kernels).  The call travels as a table call does, with the plane form's own mark in the place of the frame
+// stride (sbm_frame_planes_plan.h) -- part of the key of its captured graph, so a _ptrs graph at the same table address is another
+// graph -- and three channels; the masks, if any, are a table of the _ptrs kind.
+int sbm_match_batch_device_planes(sbm_ctx* c, const void* d_plane_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                  const void* d_mask_ptrs, int32_t flags, float threshold, void* d_out, int64_t cap, void* d_counts,
+                                  void* stream)
+{
+    if (!c || !d_out || !d_counts) return fail(SBM_ERR_INVALID, "null argument");
+    if (const int e = frame_planes_check(d_plane_ptrs != nullptr, n_frames, cols, stride, flags)) return fail(SBM_ERR_INVALID, "%s", frame_planes_error(e));
+    const MatchCall m{(const uint8_t*)d_plane_ptrs, rows, cols, stride, FPL_CHANNELS, (const uint8_t*)d_mask_ptrs, threshold, (sbm_match_rec*)d_out, cap,
+                      (int32_t*)d_counts, n_frames, frame_planes_fs(flags), d_mask_ptrs ? FP_TABLE_FS : 0};
+    hipStream_t s;
+    if (int e = begin_match(c, stream, m, &s)) return e;
+    return match_or_replay(c, s, m, n_frames);
+}
+
 int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
 {
     if (!c || !d_out || !d_count) return fail(SBM_ERR_INVALID, "null argument");

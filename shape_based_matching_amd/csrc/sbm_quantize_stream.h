@@ -42,6 +42,12 @@
 // reads its frame's entry once, with a scalar load (the frame is wave-uniform), and is otherwise the item of the contiguous form.
 // The last strip is never packed in this form: a packed wave addresses its frames by 32-bit lane offsets from the first.
 //
+// Plane form (PLANES beside PTRS, k_quantize_stream_planes; three channels): the table holds three addresses per frame, entry
+// 3 f + c the first byte of channel c of frame f, each plane rows x `stride` bytes.  A lane loads one dword (its 4 pixels) per plane
+// where the interleaved form loads three consecutive ones, replicates the border and widens per plane as the gray form does, and
+// from the window on is the interleaved form: the planes ARE the de-interleaved channels.  The source pass re-interleaves the three
+// dwords for the retained copy, which stays rows x cols x 3 packed for every reader it has.
+//
 // Requires cols % 4 == 0 and cols >= 4 (every pyramid level of a match() frame with T in {4, 8, ...} satisfies
 // it); other geometries and the float outputs (magnitude / angle of the stage API and of training) stay with
 // k_quantize.
@@ -56,6 +62,8 @@
 // the streamed stores of the source pass in terms of the emulation's plain ones (the cache hint has no meaning on the CPU)
 namespace wv {
 inline void buf_store_u32_nt(const Buf& b, const V& voff, uint32_t soff, const V& v) { buf_store_u32(b, voff, soff, v); }
+// (nor has the address space of a load)
+inline V load_u32_global(const uint8_t* base, const V& off) { return load_u32(base, off); }
 inline void buf_store_u32x3_nt(const Buf& b, const V& voff, uint32_t soff, const V& v0, const V& v1, const V& v2)
 {
     buf_store_u32(b, voff, soff, v0);
@@ -175,17 +183,21 @@ __device__ __forceinline__ wv::V qs_vote_word(wv::V v, wv::P keep)
 // row).  No constant-row shortcut: there is no arithmetic worth skipping.  The window holds 6 rows (pyrDown reads 5), two rows per
 // pyrDown row, so a group of 6 iterations has static register indices and a static row parity: the item's first loaded row
 // R0 - 2 is even (hs and row_lo are), and pyrDown row oy is due when source row 2 oy + 2 has entered the window.
-template <int CH, bool PTRS = false>
+template <int CH, bool PTRS = false, bool PLANES = false>
 __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip, int rb, int frame, int nseg)
 {
     using namespace wv;
+    static_assert(!PLANES || (PTRS && CH == 3), "the plane form is a table form of three channels");
     constexpr int ND = CH == 3 ? 3 : 1;
+    constexpr bool IL3 = CH == 3 && !PLANES; // three interleaved channels: 12 consecutive bytes per lane
     const int rows = a.rows, cols = a.cols;
     int R0 = a.row_lo + rb * a.hs;
     if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
     const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
     const int cb = strip * QS_USEFUL - QS_HALO_LANES * QS_LANE_PX;
-    const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img = PLANES ? qs_table_entry(a.img, 3 * frame) : PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img1 = PLANES ? qs_table_entry(a.img, 3 * frame + 1) : img; // plane form: channels 1 and 2
+    const uint8_t* img2 = PLANES ? qs_table_entry(a.img, 3 * frame + 2) : img;
     const int drows = rows >> 1, dcols = cols >> 1;
 
     const V lane = lane_id();
@@ -199,7 +211,7 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
     const V segc = select(seg_ok, segv, 0u);
     const V c0 = splat((uint32_t)cb) + (lseg << 2);
     const V lcol = clamp_i(c0, 0, cols - 4);
-    const V ld_off = (CH == 3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs;
+    const V ld_off = (IL3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs;
     const P left_out = lt_i(c0, splat(0u)), right_out = ge_i(c0, splat((uint32_t)cols));
     const P outside = p_or(left_out, right_out);
     const bool border_strip = nseg || cb < 0 || cb + 256 > cols;
@@ -213,7 +225,7 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
     const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, nseg ? nfr * (uint32_t)a.keep_fs : (uint32_t)rows * (uint32_t)cols * CH);
     const V keep_off = select(store_ok, (CH == 3 ? c0 + (c0 << 1) : c0) + segc * (uint32_t)a.keep_fs, BUF_DROP);
     V selA = splat(0x03020100u), selB = splat(0x03020100u), selC = splat(0x07060504u);
-    if (CH == 3) {
+    if (IL3) {
         selA = select(left_out, 0x00020100u, select(right_out, 0x05070605u, 0x03020100u));
         selB = select(left_out, 0x01000201u, 0x06050706u);
         selC = select(left_out, 0x02010002u, select(right_out, 0x07060507u, 0x07060504u));
@@ -233,6 +245,12 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
         int y = R0 - 2 + i;
         y = y < 0 ? 0 : (y > rows - 1 ? rows - 1 : y);
         const uint8_t* rowp = img + (int64_t)y * a.stride;
+        if (PLANES) { // one dword per plane
+            d[0] = load_u32_global(rowp, ld_off);
+            d[1 % ND] = load_u32_global(img1 + (int64_t)y * a.stride, ld_off);
+            d[2 % ND] = load_u32_global(img2 + (int64_t)y * a.stride, ld_off);
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < ND; ++q) d[q] = load_u32(rowp + 4 * q, ld_off);
     };
@@ -250,10 +268,18 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
 #pragma unroll
             for (int q = 0; q < ND; ++q) d[q] = dq[k][q];
             const V koff = y >= R0 && y < R1 ? keep_off : splat(BUF_DROP);
-            if (CH == 3) buf_store_u32x3_nt(keep_buf, koff, (uint32_t)(y * cols * CH), d[0], d[1 % ND], d[2 % ND]);
+            if (PLANES) {
+                // the copy is interleaved: (c0 c1 c2 c3) of the three planes -> bytes 0 .. 11 of the lane's four pixels
+                const V t0 = perm(d[1 % ND], d[0], 0x010c0400u), t1 = perm(d[1 % ND], d[0], 0x06020c05u), t2 = perm(d[1 % ND], d[0], 0x0c07030cu);
+                buf_store_u32x3_nt(keep_buf, koff, (uint32_t)(y * cols * CH), perm(d[2 % ND], t0, 0x03040100u), perm(d[2 % ND], t1, 0x03020500u),
+                                   perm(d[2 % ND], t2, 0x07020106u));
+            } else if (CH == 3) buf_store_u32x3_nt(keep_buf, koff, (uint32_t)(y * cols * CH), d[0], d[1 % ND], d[2 % ND]);
             else buf_store_u32_nt(keep_buf, koff, (uint32_t)(y * cols * CH), d[0]);
             if (border_strip) {
-                if (CH == 3) {
+                if (PLANES) {
+#pragma unroll
+                    for (int q = 0; q < ND; ++q) d[q] = perm(d[q], d[q], selA);
+                } else if (CH == 3) {
                     const V n0 = perm(d[2 % ND], d[0], selA), n2 = perm(d[2 % ND], d[0], selC);
                     const V n1 = select(outside, perm(d[2 % ND], d[0], selB), d[1 % ND]);
                     d[0] = n0;
@@ -263,7 +289,13 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
                     d[0] = perm(d[0], d[0], selA);
                 }
             }
-            if (CH == 3) {
+            if (PLANES) {
+#pragma unroll
+                for (int c = 0; c < CH; ++c) {
+                    win[k][c][0] = perm(d[c % ND], d[c % ND], 0x0c020c00u);
+                    win[k][c][1] = perm(d[c % ND], d[c % ND], 0x0c030c01u);
+                }
+            } else if (CH == 3) {
                 win[k][0][0] = perm(d[1 % ND], d[0], 0x0c060c00u);
                 win[k][1 % CH][0] = perm(d[1 % ND], d[0], 0x0c070c01u);
                 win[k][2 % CH][0] = perm(d[2 % ND], d[0], 0x0c040c02u);
@@ -322,13 +354,15 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
 
 // One work item: strip `strip`, output rows [rb*hs, min(rb*hs+hs, rows)), frame `frame`.
 // nseg == 0: the whole wave is strip `strip` of frame `frame`; nseg > 0: packed last strip of frames frame .. frame+nseg-1
-template <int CH, int STAGE = QS_WHOLE, bool PTRS = false>
+template <int CH, int STAGE = QS_WHOLE, bool PTRS = false, bool PLANES = false>
 __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0)
 {
     using namespace wv;
+    static_assert(!PLANES || (PTRS && CH == 3 && STAGE != QS_SPARSE), "the plane form is a table form of three channels");
     constexpr int ND = CH == 3 ? 3 : 1; // source dwords per lane and row
+    constexpr bool IL3 = CH == 3 && !PLANES; // three interleaved channels: 12 consecutive bytes per lane
     if (STAGE == QS_SOURCE) { // a loop of its own
-        quantize_source_wave<CH, PTRS>(a, strip, rb, frame, nseg);
+        quantize_source_wave<CH, PTRS, PLANES>(a, strip, rb, frame, nseg);
         return;
     }
     int x_first = strip * QS_USEFUL; // first useful column of the item's strip
@@ -364,7 +398,9 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
     const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
     const int cb = x_first - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
-    const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img = PLANES ? qs_table_entry(a.img, 3 * frame) : PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
+    const uint8_t* img1 = PLANES ? qs_table_entry(a.img, 3 * frame + 1) : img; // plane form: channels 1 and 2
+    const uint8_t* img2 = PLANES ? qs_table_entry(a.img, 3 * frame + 2) : img;
     uint8_t* out = a.out + (int64_t)frame * a.out_fs;
     uint8_t* pyr = STAGE != QS_SPARSE && a.pyr ? a.pyr + (int64_t)frame * a.pyr_fs : nullptr;
     // the frame's own mask (quantize(): one mask per match() call).  No select on a.mask: without a mask mask_fs is 0, so the
@@ -385,7 +421,7 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     const V segc = select(seg_ok, segv, 0u);
     const V c0 = splat((uint32_t)cb) + (lseg << 2);       // first column of this lane (may be negative / >= cols)
     const V lcol = clamp_i(c0, 0, cols - 4);              // column actually loaded (BORDER_REPLICATE)
-    const V ld_off = (CH == 3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs; // byte offset from the frame's source row
+    const V ld_off = (IL3 ? lcol + (lcol << 1) : lcol) + segc * (uint32_t)a.img_fs; // byte offset from the frame's source row
     // ... from the mask row of the group's first frame: segment g reads frame f0 + g's own mask; idle segments (segc = 0)
     // re-read the first frame's, never a mask past the last frame.  Once per work item, not per row.
     const V mk_off = lcol + segc * (uint32_t)a.mask_fs;
@@ -414,7 +450,7 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
                              BUF_DROP);                                                           // (c0 / 2) * CH
     // border lanes: byte selectors that turn the loaded (clamped) group into 4 copies of its first / last pixel
     V selA = splat(0x03020100u), selB = splat(0x03020100u), selC = splat(0x07060504u);
-    if (CH == 3) {
+    if (IL3) {
         selA = select(left_out, 0x00020100u, select(right_out, 0x05070605u, 0x03020100u));
         selB = select(left_out, 0x01000201u, 0x06050706u); // only used by outside lanes
         selC = select(left_out, 0x02010002u, select(right_out, 0x07060507u, 0x07060504u));
@@ -434,6 +470,12 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
         int y = R0 - 5 + i;
         y = y < 0 ? 0 : (y > rows - 1 ? rows - 1 : y);
         const uint8_t* rowp = img + (int64_t)y * a.stride;
+        if (PLANES) { // one dword per plane
+            d[0] = load_u32_global(rowp, ld_off);
+            d[1 % ND] = load_u32_global(img1 + (int64_t)y * a.stride, ld_off);
+            d[2 % ND] = load_u32_global(img2 + (int64_t)y * a.stride, ld_off);
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < ND; ++q) d[q] = load_u32(rowp + 4 * q, ld_off);
     };
@@ -475,7 +517,13 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
             bool row_flat = false;
             uint32_t key = flat_key;
             if (flat_cnt > 0 || (i & 3) == 0) {
-                if (CH == 3) {
+                if (PLANES) {
+                    // the same key as the interleaved form's, (b, g, r) of the strip's first pixel, and flat only if all three planes are
+                    const uint32_t b = read_first(d[0]) & 0xffu, g = read_first(d[1 % ND]) & 0xffu, r = read_first(d[2 % ND]) & 0xffu;
+                    key = b | (g << 8) | (r << 16);
+                    row_flat = all(p_and(p_and(eq(d[0], splat(b * 0x01010101u)), eq(d[1 % ND], splat(g * 0x01010101u))),
+                                         eq(d[2 % ND], splat(r * 0x01010101u))));
+                } else if (CH == 3) {
                     key = read_first(d[0]) & 0xffffffu; // (b, g, r) of the strip's first pixel
                     const uint32_t b = key & 0xff, g = (key >> 8) & 0xff, r = key >> 16;
                     const uint32_t p0 = key | (b << 24), p1 = g | (r << 8) | (b << 16) | (g << 24), p2 = r | (b << 8) | (g << 16) | (r << 24);
@@ -498,7 +546,10 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
             //      to fill the window) ----
             if (!long_run) {
                 if (border_strip) {
-                    if (CH == 3) {
+                    if (PLANES) {
+#pragma unroll
+                        for (int q = 0; q < ND; ++q) d[q] = perm(d[q], d[q], selA);
+                    } else if (CH == 3) {
                         const V n0 = perm(d[2 % ND], d[0], selA), n2 = perm(d[2 % ND], d[0], selC);
                         const V n1 = select(outside, perm(d[2 % ND], d[0], selB), d[1 % ND]);
                         d[0] = n0;
@@ -508,7 +559,13 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
                         d[0] = perm(d[0], d[0], selA);
                     }
                 }
-                if (CH == 3) {
+                if (PLANES) {
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) {
+                        st.win[k][c][0] = perm(d[c % ND], d[c % ND], 0x0c020c00u);
+                        st.win[k][c][1] = perm(d[c % ND], d[c % ND], 0x0c030c01u);
+                    }
+                } else if (CH == 3) {
                     st.win[k][0][0] = perm(d[1 % ND], d[0], 0x0c060c00u);
                     st.win[k][1 % CH][0] = perm(d[1 % ND], d[0], 0x0c070c01u);
                     st.win[k][2 % CH][0] = perm(d[2 % ND], d[0], 0x0c040c02u);
@@ -780,14 +837,14 @@ __host__ __device__ inline int quantize_stream_items(const QSArgs& a)
     return n_full * a.n_rblocks * a.frames + (a.pack_lanes ? a.n_rblocks * a.pack_groups : 0);
 }
 
-template <int CH, int STAGE = QS_WHOLE, bool PTRS = false>
+template <int CH, int STAGE = QS_WHOLE, bool PTRS = false, bool PLANES = false>
 __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
 {
     if (PTRS) { // never packed: (strip, row block, frame) in the order below and nothing else
         const int per_rb = a.n_strips * a.frames;
         if (a.pack_lanes || item >= per_rb * a.n_rblocks) return;
         const int rb = item / per_rb, r = item - rb * per_rb;
-        quantize_stream_wave<CH, STAGE, PTRS>(a, r % a.n_strips, rb, r / a.n_strips, 0);
+        quantize_stream_wave<CH, STAGE, PTRS, PLANES>(a, r % a.n_strips, rb, r / a.n_strips, 0);
         return;
     }
     // Order: row block slowest, then frame, then strip.  All work items are resident at once (one round) and the
@@ -840,6 +897,14 @@ __global__ __launch_bounds__(256) void k_quantize_stream_ptrs(const QSArgs a)
 {
     const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     quantize_stream_item<CH, STAGE, true>(a, item);
+}
+
+// the plane form: a.img is a device array of 3 * a.frames plane addresses (a.mask as in the table form); three channels
+template <int STAGE = QS_WHOLE>
+__global__ __launch_bounds__(256) void k_quantize_stream_planes(const QSArgs a)
+{
+    const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    quantize_stream_item<3, STAGE, true, true>(a, item);
 }
 #endif
 

@@ -172,7 +172,9 @@ __device__ __forceinline__ uint32_t vote_word(uint32_t v)
 // PTRS (the table form of the batched match): img is a device array of gridDim.z frame addresses and mask, if not null, one of
 // mask addresses (an entry may not be null); frame blockIdx.z's pointers are read from them when the kernel runs, and img_fs and
 // mask_fs are not read at all.
-template <int CH, bool WITH_FLOAT, int QN, bool PTRS = false>
+// PLANES (beside PTRS, three channels): img is a device array of 3 * gridDim.z PLANE addresses, entry 3 f + c the first byte of
+// channel c of frame f, rows x `stride` bytes each.  Phase A's LDS tile is planar already: s_src[c] is filled from plane c.
+template <int CH, bool WITH_FLOAT, int QN, bool PTRS = false, bool PLANES = false>
 __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img, int rows, int cols,
                                                   int stride, const uint8_t* __restrict__ mask,
                                                   float thr_sq, uint8_t* __restrict__ out,
@@ -182,7 +184,13 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
 {
     // a batch of frames of one geometry: frame = blockIdx.z, *_fs = bytes from one frame to the next (mask_fs = 0: the
     // frames share one mask)
-    if (PTRS) {
+    static_assert(!PLANES || (PTRS && CH == 3 && !WITH_FLOAT), "the plane form is a table form of three channels");
+    const uint8_t* pl[3] = {nullptr, nullptr, nullptr}; // PLANES: the frame's three planes
+    if (PLANES) {
+        if (mask) mask = reinterpret_cast<const uint8_t* const*>(mask)[blockIdx.z];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pl[k] = reinterpret_cast<const uint8_t* const*>(img)[3 * blockIdx.z + k];
+    } else if (PTRS) {
         if (mask) mask = reinterpret_cast<const uint8_t* const*>(mask)[blockIdx.z];
         img = reinterpret_cast<const uint8_t* const*>(img)[blockIdx.z];
     } else {
@@ -215,7 +223,11 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
     const bool flat_check = !WITH_FLOAT && thr_sq >= 0.f;
     uint32_t ref[CH];
     bool nonflat = false;
-    if (flat_check) {
+    if (flat_check && PLANES) { // the tile's first pixel, a byte of each plane
+        const size_t o0 = (size_t)clampi(R0 - 5, 0, rows - 1) * stride + (size_t)clampi(C0 - 8, 0, cols - 1);
+#pragma unroll
+        for (int k = 0; k < CH; ++k) ref[k] = (uint32_t)pl[k % 3][o0] * 0x01010101u;
+    } else if (flat_check) {
         const uint8_t* p0 = img + (size_t)clampi(R0 - 5, 0, rows - 1) * stride + (size_t)clampi(C0 - 8, 0, cols - 1) * CH;
 #pragma unroll
         for (int k = 0; k < CH; ++k) ref[k] = (uint32_t)p0[k] * 0x01010101u;
@@ -231,6 +243,12 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
             const int it = tid + rd * QN;
             if (it < A_ITEMS) {
                 const int r = it / (QS_W / 4), g = it - r * (QS_W / 4);
+                if (PLANES) { // the group's four bytes of each plane
+                    const size_t o = (size_t)clampi(R0 - 5 + r, 0, rows - 1) * stride + (size_t)clampi(C0 - 8 + 4 * g, 0, cols - 4);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) d[rd][k % (CH == 1 ? 1 : 3)] = ld_u32_any(pl[k] + o);
+                    continue;
+                }
                 const uint8_t* p = img + (size_t)clampi(R0 - 5 + r, 0, rows - 1) * stride + (size_t)clampi(C0 - 8 + 4 * g, 0, cols - 4) * CH;
                 d[rd][0] = ld_u32_any(p);
                 if (CH > 1) {
@@ -248,6 +266,9 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
                 uint32_t w[CH];
                 if (CH == 1) {
                     w[0] = d[rd][0];
+                } else if (PLANES) {
+#pragma unroll
+                    for (int k = 0; k < CH; ++k) w[k] = d[rd][k % (CH == 1 ? 1 : 3)];
                 } else {
                     const uint32_t d0 = d[rd][0], d1 = d[rd][1 % (CH == 1 ? 1 : 3)], d2 = d[rd][2 % (CH == 1 ? 1 : 3)];
                     // 12 interleaved bytes b0..b11 -> channel k = {b[k], b[k+3], b[k+6], b[k+9]}
@@ -273,7 +294,10 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
             for (int k = 0; k < CH; ++k) {
                 uint32_t w = 0;
 #pragma unroll
-                for (int m = 0; m < 4; ++m) w |= (uint32_t)rowp[clampi(c + m, 0, cols - 1) * CH + k] << (8 * m);
+                for (int m = 0; m < 4; ++m) {
+                    if (PLANES) w |= (uint32_t)pl[k % 3][(size_t)clampi(R0 - 5 + r, 0, rows - 1) * stride + clampi(c + m, 0, cols - 1)] << (8 * m);
+                    else w |= (uint32_t)rowp[clampi(c + m, 0, cols - 1) * CH + k] << (8 * m);
+                }
                 s_src[k][r][g] = w;
                 if (flat_check) nonflat = nonflat || w != ref[k];
             }

@@ -129,6 +129,14 @@ __device__ __forceinline__ uint32_t read_first(V a) { return __builtin_amdgcn_re
 
 // memory: wave-uniform base pointer + per-lane byte offset
 __device__ __forceinline__ V load_u32(const uint8_t* base, V off) { return *(const wv_u32_unaligned*)(base + off); }
+// ... where the base is known to be device memory although the compiler cannot see it (an address read from a table is a generic
+// pointer to it: flat_load, a 64-bit VGPR address per load): global_load with the base in SGPRs and the lane's offset in one VGPR.
+// The plane form of the row-streaming kernel loads from three bases per row.
+typedef __attribute__((address_space(1))) const uint8_t* wv_global_u8;
+__device__ __forceinline__ V load_u32_global(const uint8_t* base, V off)
+{
+    return *(__attribute__((address_space(1))) const wv_u32_unaligned*)((wv_global_u8)base + off);
+}
 
 // Stores go through a buffer resource: a lane whose offset is >= the buffer size (BUF_DROP) is discarded by the
 // hardware range check, so predicated stores need no branch and the kernel keeps wave-uniform control flow.
