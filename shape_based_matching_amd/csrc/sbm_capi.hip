@@ -23,6 +23,7 @@
 #include "sbm_source_lines.h"
 #include "sbm_frame_ptrs_plan.h"
 #include "sbm_frame_planes_plan.h"
+#include "sbm_frame_source.h"
 #include "sbm_train_kernels.h"
 #include "sbm_nms_kernels.h"
 

@@ -269,23 +269,10 @@ struct sbm_ctx {
 
     // hipGraph cache for sbm_match_device (one captured graph per distinct argument tuple)
     struct GraphEntry {
-        const void* img;
-        int rows, cols, stride, ch;
-        const void* mask;
-        uint32_t thr_bits;
-        void* out;
-        int64_t cap;
-        void* count;
-        void* mo;
-        void* mc;
-        int frames;       // 0: single-frame graph (sbm_match_device), else the batch size
-        int64_t frame_stride;
-        int64_t mask_stride; // bytes between the frames' masks; 0: one shared mask (a different launch for the same pointer)
-        hipGraph_t graph;
-        hipGraphExec_t exec;
-        uint64_t last_use;
-        bool sparse_grad = false; // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
-        bool sparse_rects = false; // ... with its work items taken from the record of need rectangles (other kernel arguments)
+        GraphKey key; // sbm_frame_source.h
+        hipGraph_t graph = nullptr;
+        hipGraphExec_t exec = nullptr;
+        uint64_t last_use = 0;
         int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
         int32_t source_form = 0;               // ... and the captured source pass
         int32_t refine_form[SBM_MAX_LEVELS][6] = {}; // ... and what the captured enqueue_local launched per level
@@ -316,7 +303,7 @@ struct sbm_ctx {
     int graph_pref = -1;
     bool auto_graph_off = false;      // auto: the caller's argument tuples never repeat (captures without hits): stop capturing
     int graph_captures_since_hit = 0;
-    std::vector<GraphEntry> graph_seen; // auto: tuples seen once (a tuple is captured at its second sighting)
+    std::vector<GraphKey> graph_seen; // auto: tuples seen once (a tuple is captured at its second sighting)
     hipStream_t side = nullptr;
     hipEvent_t ev_fork[SBM_MAX_LEVELS] = {};
     hipEvent_t ev_join = nullptr;
@@ -550,26 +537,24 @@ int upload_geo(sbm_ctx* c, hipStream_t s)
 // per Mpixel) and the only one with the float outputs and arbitrary widths.  SBM_QUANTIZE=tile|stream forces one for
 // A/B runs, SBM_QS_HS sets the rows per wave.
 // segment lanes of the packed last strip (0: none); SBM_QS_PACK=0 is the A/B knob
-static int qs_pack_lanes(int rows, int cols, int ch, int frames, int64_t img_fs, int stride, int64_t mask_fs)
+static int qs_pack_lanes(int rows, int cols, const FrameSource& src, const MaskSource& mask)
 {
-    // frames named by a device table (sbm_frame_ptrs_plan.h) lie anywhere: no 32-bit offset reaches from one to the next.  The
-    // table form is launched unpacked (DESIGN.md section 5 has the measurement behind that choice)
-    // (a table of planes, sbm_frame_planes_plan.h, likewise)
-    if (fs_names_table(img_fs)) return 0;
-    const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, ch, frames, mask_fs) : 0;
+    if (!source_may_pack(src)) return 0;
+    const int lanes = tuning().qs_pack ? quantize_stream_pack_lanes(rows, cols, src.ch, src.frames, kernel_mask_stride(mask)) : 0;
     if (!lanes) return 0;
     // the frames of a group are addressed by 32-bit per-lane offsets from the group's first frame: the caller's frame
     // stride (any value, also negative or zero) must keep them within 2 GiB
-    const int64_t span = (int64_t)(64 / lanes - 1) * img_fs;
-    if (img_fs < 0 || span + (int64_t)rows * stride >= (int64_t)0x7ff00000) return 0;
+    const int64_t span = (int64_t)(64 / lanes - 1) * src.frame_stride;
+    if (src.frame_stride < 0 || span + (int64_t)rows * src.stride >= (int64_t)0x7ff00000) return 0;
     return lanes;
 }
 
 // rows = the image's rows; band_rows = the output rows of this launch (rows for a whole level; a row band of a
 // build-sharded step otherwise, which always takes the streaming kernel: the tile kernel has no row-range form)
-int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frames, bool wf, int64_t img_fs, int stride, int band_rows = 0,
-                         int64_t mask_fs = 0)
+// wf: the launch has float outputs
+int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, const FrameSource& src, const MaskSource& mask, bool wf, int band_rows = 0)
 {
+    const int ch = src.ch, frames = src.frames;
     const bool band = band_rows > 0 && band_rows < rows;
     const int out_rows = band ? band_rows : rows;
     const int mode = c->quantize_mode ? c->quantize_mode : tuning().quantize;
@@ -583,7 +568,7 @@ int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, int ch, int frame
     // takes about  ceil(waves / resident slots) x (hs + 10 halo rows).  Choose the rows per wave that minimise it.
     const int64_t slots = (int64_t)c->n_simd * (ch == 3 ? 3 : 6); // resident waves: 3 per SIMD at the BGR kernel's registers, 6 gray
     // waves per row block: one per strip and frame, except that a narrow last strip is shared by several frames
-    const int pack = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride, mask_fs);
+    const int pack = qs_pack_lanes(rows, cols, src, mask);
     const int64_t per_rb = pack ? (strips - 1) * frames + (frames + 64 / pack - 1) / (64 / pack) : strips * frames;
     int hs = 0;
     int64_t best = INT64_MAX;
@@ -629,47 +614,64 @@ struct QSForm {
 // rows per work item of the source pass: its items run hs + 3 row iterations, in whole groups of 6
 int source_pass_rows() { return tuning().src_hs > 0 ? (tuning().src_hs + 1) & ~1 : 32; }
 
-int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, int cols, int stride, int ch,
-                    const uint8_t* d_mask, float weak, uint8_t* d_out, float* d_mag, float* d_ori, uint8_t* d_pyr,
-                    int frames = 1, int64_t img_fs = 0, int row_lo = 0, int row_hi = -1, bool tile_band = false, int64_t mask_fs = 0,
-                    const QSForm* form = nullptr)
+// One launch of the gradient stage: where its frames and masks lie, the level's geometry, the outputs, the rows
+struct QuantizeLaunch {
+    FrameSource src;
+    MaskSource mask;            // none: every pixel counts
+    int rows = 0, cols = 0;
+    float weak = 0.f;
+    uint8_t* out = nullptr;     // the orientation map, rows x cols per frame (packed)
+    float* mag = nullptr;       // float outputs (the stage entry points, training): the tile kernel
+    float* ori = nullptr;
+    uint8_t* pyr = nullptr;     // the fused cv::pyrDown output, (rows / 2) x (cols / 2) x ch per frame (packed), or null
+    int row_lo = 0, row_hi = -1; // output rows [row_lo, row_hi); -1: to the last
+    bool tile_band = false;
+    const QSForm* form = nullptr;
+};
+
+int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
 {
-    if (!d_mask) mask_fs = 0; // mask_fs: bytes between the frames' masks, 0 = one mask for all frames
-    if (row_hi < 0) row_hi = rows;
+    const FrameSource& src = q.src;
+    const int rows = q.rows, cols = q.cols, ch = src.ch, frames = src.frames, row_lo = q.row_lo, row_hi = q.row_hi < 0 ? rows : q.row_hi;
+    const QSForm* const form = q.form;
+    const bool tile_band = q.tile_band;
     const bool band = row_lo > 0 || row_hi < rows;
-    // The table form (sbm_match_batch_device_ptrs): img_fs says so and holds the call's flags, d_img is the device array of frame
-    // addresses and d_mask, if not null, the array of mask addresses.  The caller's level-0 launch only -- whole, without float outputs.
-    // The plane form (sbm_match_batch_device_planes) is a table form too: img_fs is its own mark, d_img the device array of three
-    // plane addresses per frame, d_mask as above; three channels, and `stride` is a plane's row.
-    const bool planes = fs_is_planes(img_fs);
-    const bool table = fs_is_table(img_fs) || planes;
-    if (table && (band || tile_band || d_mag || d_ori || (d_mask && !fs_is_table(mask_fs)) || (form && form->stage != QS_SOURCE)))
+    // The table forms (sbm_match_batch_device_ptrs: a device array of frame addresses; sbm_match_batch_device_planes: of three plane
+    // addresses per frame, three channels, `stride` a plane's row), with the masks, if any, in a device array of mask addresses.
+    // The caller's level-0 launch only -- whole, without float outputs.
+    const bool planes = src.kind == FRAMES_PLANES;
+    const bool table = frames_in_table(src);
+    if (table && (band || tile_band || q.mag || q.ori || (q.mask.kind != MASK_NONE && q.mask.kind != MASK_TABLE) || (form && form->stage != QS_SOURCE)))
         return fail(SBM_ERR_STATE, "a table of frame pointers names the frames of a whole level-0 launch only");
     if (planes && ch != FPL_CHANNELS) return fail(SBM_ERR_STATE, "a table of plane pointers names frames of three channels");
-    if (!table && fs_is_table(mask_fs)) return fail(SBM_ERR_STATE, "a table of mask pointers needs a table of frame pointers");
+    if (!table && q.mask.kind == MASK_TABLE) return fail(SBM_ERR_STATE, "a table of mask pointers needs a table of frame pointers");
+    // what the kernels get: the frames or their table, the strides a table form does not read as 0
+    const uint8_t* const d_img = (const uint8_t*)src.base;
+    const uint8_t* const d_mask = (const uint8_t*)q.mask.base;
+    const int stride = src.stride;
+    const int64_t img_fs = kernel_frame_stride(src), mask_fs = kernel_mask_stride(q.mask);
+    uint8_t* const d_out = q.out;
+    float* const d_mag = q.mag;
+    float* const d_ori = q.ori;
+    uint8_t* const d_pyr = q.pyr;
     // tile_band: rows [row_lo, row_hi) as a band of whole rows of 16 x 64 TILES (row_lo a multiple of 16, row_hi too or the
     // last row): the latency path of sbm_match, whose level-0 launches follow the frame's upload band by band
     const int tile_row0 = tile_band ? row_lo / QT_R : 0;
     dim3 grid((cols + QT_C - 1) / QT_C, tile_band ? (row_hi - row_lo + QT_R - 1) / QT_R : (rows + QT_R - 1) / QT_R, frames);
-    const float thr_sq = weak * weak;
+    const float thr_sq = q.weak * q.weak;
     const bool wf = d_mag || d_ori;
     const int64_t out_fs = (int64_t)rows * cols, pyr_fs = (int64_t)(rows / 2) * (cols / 2) * ch; // the context's own per-frame buffers
-    int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, ch, frames, wf, img_fs, stride, band ? row_hi - row_lo : 0, mask_fs);
+    int hs = tile_band ? 0 : quantize_stream_rows(c, rows, cols, src, q.mask, wf, band ? row_hi - row_lo : 0);
     if (form && (!hs || band || d_mask)) return fail(SBM_ERR_STATE, "a reduced gradient form needs a whole, unmasked launch of the streaming kernel");
     if (form && form->stage == QS_SOURCE) hs = source_pass_rows();
     // The source pass as whole lines (sbm_source_lines.h) wherever the caller's layout admits it; every other layout -- a row pad
     // of 13 bytes, an odd frame stride -- stays with the strided form below.
-    // Behind a table the host cannot see the frames' addresses: the caller's promise (SBM_PTRS_ALIGNED4) stands in for them.
-    // Planes have no line form.
-    const bool lines = planes ? frame_planes_source_lines(fs_planes_flags(img_fs), stride, rows, cols, tuning().source_lines != 0)
-                       : table ? frame_ptrs_source_lines(fs_table_flags(img_fs), stride, rows, cols, ch, tuning().source_lines != 0)
-                             : tuning().source_lines && source_lines_ok((uint64_t)(uintptr_t)d_img, stride, img_fs, frames, rows, cols, ch);
-    if (form && form->stage == QS_SOURCE && lines) {
+    if (form && form->stage == QS_SOURCE && source_takes_lines(src, rows, cols, tuning().source_lines)) {
         QSArgs a;
         memset(&a, 0, sizeof a);
         a.img = d_img;
         a.pyr = d_pyr;
-        a.img_fs = table ? 0 : img_fs;
+        a.img_fs = img_fs;
         a.pyr_fs = pyr_fs;
         a.rows = rows;
         a.cols = cols;
@@ -698,10 +700,10 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.mask = d_mask;
         a.out = d_out;
         a.pyr = d_pyr;
-        a.img_fs = table ? 0 : img_fs;
+        a.img_fs = img_fs;
         a.out_fs = out_fs;
         a.pyr_fs = pyr_fs;
-        a.mask_fs = table ? 0 : mask_fs;
+        a.mask_fs = mask_fs;
         a.rows = rows;
         a.cols = cols;
         a.stride = stride;
@@ -712,7 +714,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
         a.n_strips = (cols + QS_USEFUL - 1) / QS_USEFUL;
         a.n_rblocks = (row_hi - row_lo + hs - 1) / hs;
         a.frames = frames;
-        a.pack_lanes = qs_pack_lanes(rows, cols, ch, frames, img_fs, stride, mask_fs);
+        a.pack_lanes = qs_pack_lanes(rows, cols, src, q.mask);
         a.pack_groups = a.pack_lanes ? (frames + 64 / a.pack_lanes - 1) / (64 / a.pack_lanes) : 0;
         const int stage = form ? form->stage : (int)QS_WHOLE;
         if (stage == QS_SOURCE) {
@@ -744,18 +746,26 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
             else if (stage == QS_SPARSE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SPARSE>), g, dim3(256), 0, s, a); \
             else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                     \
         } while (0)
-        // (the table form has the whole row loop and the source pass; the sparse launch reads the retained copy)
+        // (the table forms have the whole row loop and the source pass; the sparse launch reads the retained copy)
 #define SBM_QS_PTRS(CH_)                                                                                                    \
         do {                                                                                                                \
             if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_SOURCE>), g, dim3(256), 0, s, a); \
             else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_ptrs<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                \
         } while (0)
-        if (planes && stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_SOURCE>), g, dim3(256), 0, s, a);
-        else if (planes) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_WHOLE>), g, dim3(256), 0, s, a);
-        else if (table && ch == 1) SBM_QS_PTRS(1);
-        else if (table) SBM_QS_PTRS(3);
-        else if (ch == 1) SBM_QS(1);
-        else SBM_QS(3);
+        switch (src.kind) {
+        case FRAMES_PLANES:
+            if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_SOURCE>), g, dim3(256), 0, s, a);
+            else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_planes<QS_WHOLE>), g, dim3(256), 0, s, a);
+            break;
+        case FRAMES_TABLE:
+            if (ch == 1) SBM_QS_PTRS(1);
+            else SBM_QS_PTRS(3);
+            break;
+        case FRAMES_STRIDED:
+            if (ch == 1) SBM_QS(1);
+            else SBM_QS(3);
+            break;
+        }
 #undef SBM_QS_PTRS
 #undef SBM_QS
         HIP_TRY(hipGetLastError());
@@ -766,29 +776,29 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const uint8_t* d_img, int rows, i
     if (tile_band && (row_lo % QT_R || (row_hi % QT_R && row_hi != rows))) return fail(SBM_ERR_INVALID, "a band of tiles must start and end on tile rows");
     // many tiles per CU (a batch of frames): 512-thread blocks, four of them per CU; else 1024-thread blocks (tile latency)
     const bool many = (int64_t)grid.x * grid.y * grid.z >= 2048;
-    // (the table form: d_img / d_mask are the tables, the two strides are not read)
-    const int64_t k_img_fs = table ? 0 : img_fs, k_mask_fs = table ? 0 : mask_fs;
-#define SBM_QUANTIZE(CH_, WF_, PTRS_)                                                                                       \
+    // (the table forms: d_img / d_mask are the tables)
+#define SBM_QUANTIZE(CH_, WF_, PTRS_, PLANES_)                                                                              \
     do {                                                                                                                    \
         if (many)                                                                                                           \
-            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_THROUGHPUT, PTRS_>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, \
-                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs); \
+            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_THROUGHPUT, PTRS_, PLANES_>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, \
+                       stride, d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);     \
         else                                                                                                                \
-            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY, PTRS_>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
-                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);         \
+            SBM_LAUNCH(c, "k_quantize", (k_quantize<CH_, WF_, QN_LATENCY, PTRS_, PLANES_>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, \
+                       d_mask, thr_sq, d_out, d_mag, d_ori, d_pyr, img_fs, out_fs, pyr_fs, tile_row0, mask_fs);             \
     } while (0)
-    if (planes && many)
-        SBM_LAUNCH(c, "k_quantize", (k_quantize<3, false, QN_THROUGHPUT, true, true>), grid, dim3(QN_THROUGHPUT), 0, s, d_img, rows, cols, stride, d_mask,
-                   thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);
-    else if (planes)
-        SBM_LAUNCH(c, "k_quantize", (k_quantize<3, false, QN_LATENCY, true, true>), grid, dim3(QN_LATENCY), 0, s, d_img, rows, cols, stride, d_mask,
-                   thr_sq, d_out, d_mag, d_ori, d_pyr, k_img_fs, out_fs, pyr_fs, tile_row0, k_mask_fs);
-    else if (table && ch == 1) SBM_QUANTIZE(1, false, true);
-    else if (table) SBM_QUANTIZE(3, false, true);
-    else if (ch == 1 && !wf) SBM_QUANTIZE(1, false, false);
-    else if (ch == 1) SBM_QUANTIZE(1, true, false);
-    else if (!wf) SBM_QUANTIZE(3, false, false);
-    else SBM_QUANTIZE(3, true, false);
+    switch (src.kind) {
+    case FRAMES_PLANES: SBM_QUANTIZE(3, false, true, true); break;
+    case FRAMES_TABLE:
+        if (ch == 1) SBM_QUANTIZE(1, false, true, false);
+        else SBM_QUANTIZE(3, false, true, false);
+        break;
+    case FRAMES_STRIDED:
+        if (ch == 1 && !wf) SBM_QUANTIZE(1, false, false, false);
+        else if (ch == 1) SBM_QUANTIZE(1, true, false, false);
+        else if (!wf) SBM_QUANTIZE(3, false, false, false);
+        else SBM_QUANTIZE(3, true, false, false);
+        break;
+    }
 #undef SBM_QUANTIZE
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1031,60 +1041,74 @@ int check_bands(const sbm_ctx* c, int n_bands)
     return 0;
 }
 
-// Rows [row_lo, row_hi) of level l's gradient stage, the one place it is launched from for a pyramid.  img / stride / mask
-// are the caller's cursor down the pyramid: level 0's at first, and the first launch of a level l > 0 (first: the caller
-// says so; further bands of the level find the cursor moved) moves them down -- the mask resized from level l-1's, the
-// image the one level l-1's launch produced (fused cv::pyrDown).  img_fs: bytes between the frames of this level's image.
-// mask_fs: bytes between the frames' masks at the cursor's level, 0 = one mask for all frames; a mask per frame stays a mask
-// per frame down the pyramid (pyrDown(), line2Dup.cpp:439: level l's from level l-1's, frame by frame).
-int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, const uint8_t*& img, int& stride, const uint8_t*& mask, int64_t& mask_fs,
-                           int frames, int64_t img_fs, int row_lo, int row_hi)
+// the context's own frames: level l's image (l >= 1: what level l-1's launch produced, fused cv::pyrDown), the retained level-0 source
+FrameSource level_frames(const sbm_ctx* c, int l, int frames) { return packed_frames(c->d_img[l].p, c->rows[l], c->cols[l], c->channels, frames); }
+FrameSource retained_frames(const sbm_ctx* c, int ch, int frames) { return packed_frames(c->d_src0.p, c->rows[0], c->cols[0], ch, frames); }
+
+// A call's cursor down the pyramid: the caller's frames and masks at level 0, the context's own from level 1 on
+struct PyramidCursor {
+    FrameSource src;
+    MaskSource mask;
+};
+
+// Rows [row_lo, row_hi) of level l's gradient stage, the one place it is launched from for a pyramid.  The first launch of a
+// level l > 0 (first: the caller says so; further bands of the level find the cursor moved) moves the cursor down -- the mask
+// resized from level l-1's, the image the one level l-1's launch produced.  A mask per frame stays a mask per frame down the
+// pyramid (pyrDown(), line2Dup.cpp:439: level l's from level l-1's, frame by frame).
+int enqueue_gradient_level(sbm_ctx* c, hipStream_t s, int l, bool first, PyramidCursor& cur, int row_lo, int row_hi)
 {
-    const int ch = c->channels;
+    const int frames = cur.src.frames;
     if (l > 0 && first) {
-        if (mask) {
+        if (cur.mask.kind != MASK_NONE) {
             const int n = c->rows[l] * c->cols[l];
-            const int64_t dst_fs = mask_fs ? (int64_t)n : 0;
-            if (mask_fs && frames > c->mask_frames) return fail(SBM_ERR_STATE, "level %d holds %d masks, the batch has %d frames", l, c->mask_frames, frames);
-            if (fs_is_table(mask_fs)) // level 0's masks are named by the caller's table; from here on they are the context's own
+            const bool per_frame = masks_per_frame(cur.mask);
+            if (per_frame && frames > c->mask_frames) return fail(SBM_ERR_STATE, "level %d holds %d masks, the batch has %d frames", l, c->mask_frames, frames);
+            const int64_t dst_fs = per_frame ? (int64_t)n : 0;
+            if (cur.mask.kind == MASK_TABLE) // level 0's masks are named by the caller's table; from here on they are the context's own
                 SBM_LAUNCH(c, "k_resize_mask", k_resize_mask_ptrs, dim3(std::min((n + 255) / 256, 4096), frames), dim3(256), 0, s,
-                           reinterpret_cast<const uint8_t* const*>(mask), c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l],
+                           reinterpret_cast<const uint8_t* const*>(cur.mask.base), c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l],
                            c->cols[l], dst_fs);
             else
-                SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096), mask_fs ? frames : 1), dim3(256), 0, s, mask,
-                           c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l], mask_fs, dst_fs);
+                SBM_LAUNCH(c, "k_resize_mask", k_resize_mask, dim3(std::min((n + 255) / 256, 4096), per_frame ? frames : 1), dim3(256), 0, s,
+                           (const uint8_t*)cur.mask.base, c->rows[l - 1], c->cols[l - 1], c->d_mask[l].as<uint8_t>(), c->rows[l], c->cols[l],
+                           kernel_mask_stride(cur.mask), dst_fs);
             HIP_TRY(hipGetLastError());
-            mask = c->d_mask[l].as<uint8_t>();
-            mask_fs = dst_fs;
+            cur.mask = strided_masks(c->d_mask[l].p, dst_fs);
         }
-        img = c->d_img[l].as<uint8_t>();
-        stride = c->cols[l] * ch;
+        cur.src = level_frames(c, l, frames);
     }
-    return launch_quantize(c, s, img, c->rows[l], c->cols[l], stride, ch, mask, c->cfg.weak_threshold, c->d_quant[l].as<uint8_t>(), nullptr,
-                           nullptr, l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr, frames, img_fs, row_lo, row_hi, false, mask_fs);
+    QuantizeLaunch q;
+    q.src = cur.src;
+    q.mask = cur.mask;
+    q.rows = c->rows[l], q.cols = c->cols[l];
+    q.weak = c->cfg.weak_threshold;
+    q.out = c->d_quant[l].as<uint8_t>();
+    q.pyr = l + 1 < c->L ? c->d_img[l + 1].as<uint8_t>() : nullptr;
+    q.row_lo = row_lo, q.row_hi = row_hi;
+    return launch_quantize(c, s, q);
 }
 
 // What one call adds to the plan's inputs for a sparse level-0 gradient (PlanInputs::sparse_gradient ...): the knob and the
 // retained buffer, whether both launches -- the source pass on the caller's frames, the later ones on the retained copy --
 // take the streaming kernel, the mask, the bands (a one-band exchange reads the map too; level 0 launched already counts)
-PlanInputs call_plan_inputs(const sbm_ctx* c, const uint8_t* mask, int stride0, int frames, int64_t img0_fs, const Bands* bands, bool level0_done)
+PlanInputs call_plan_inputs(const sbm_ctx* c, const FrameSource& src, const MaskSource& mask, const Bands* bands, bool level0_done)
 {
     PlanInputs pin = plan_inputs(c);
-    const int rows = c->rows[0], cols = c->cols[0], ch = c->channels;
-    const int64_t fs = (int64_t)rows * cols * ch;
+    const int rows = c->rows[0], cols = c->cols[0], frames = src.frames;
+    const int64_t fs = (int64_t)rows * cols * c->channels;
     pin.sparse_gradient = tuning().sparse_gradient && c->d_src0.p && fs < (int64_t)0x7ff00000 && (size_t)frames * (size_t)fs <= c->d_src0.cap;
-    pin.l0_stream = pin.sparse_gradient && quantize_stream_rows(c, rows, cols, ch, frames, false, img0_fs, stride0) != 0 &&
-                    quantize_stream_rows(c, rows, cols, ch, frames, false, fs, cols * ch) != 0;
-    pin.l0_mask = mask != nullptr;
+    pin.l0_stream = pin.sparse_gradient && quantize_stream_rows(c, rows, cols, src, MaskSource{}, false) != 0 &&
+                    quantize_stream_rows(c, rows, cols, retained_frames(c, c->channels, frames), MaskSource{}, false) != 0;
+    pin.l0_mask = mask.kind != MASK_NONE;
     pin.banded = bands != nullptr || level0_done;
     pin.any_batch = frames > 1 && any_batch_ok(c);
     return pin;
 }
 
 // ... the plan of a match entry point then makes level 0's map sparsely
-bool plans_sparse_gradient(const sbm_ctx* c, const uint8_t* mask, int stride0, int frames, int64_t img0_fs, const Bands* bands, bool level0_done)
+bool plans_sparse_gradient(const sbm_ctx* c, const FrameSource& src, const MaskSource& mask, const Bands* bands, bool level0_done)
 {
-    return plan_build(call_plan_inputs(c, mask, stride0, frames, img0_fs, bands, level0_done), all_rows_ok(c), true).sparse_gradient;
+    return plan_build(call_plan_inputs(c, src, mask, bands, level0_done), all_rows_ok(c), true).sparse_gradient;
 }
 
 // Every level of every frame of a batch in the forms of `plan` (LM_SPREAD or LM_PLANES8 per level), in one launch of
@@ -1121,14 +1145,12 @@ int launch_lm_any(sbm_ctx* c, hipStream_t s, const BuildPlan& plan, int frames, 
     return 0;
 }
 
-int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride0, const uint8_t* d_mask0,
-                    int32_t* reset_count = nullptr, int frames = 1, int64_t img0_fs = 0, const Bands* bands = nullptr,
-                    bool level0_gradient_done = false, int64_t mask0_fs = 0)
+// src0 / mask0: level 0's frames and masks, the caller's or the context's own
+int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const MaskSource& mask0, int32_t* reset_count = nullptr,
+                    const Bands* bands = nullptr, bool level0_gradient_done = false)
 {
-    const uint8_t* img = d_img0;
-    int stride = stride0;
-    const uint8_t* mask = d_mask0;
-    int64_t mask_fs = d_mask0 ? mask0_fs : 0;
+    PyramidCursor cur{src0, mask0};
+    const int frames = src0.frames;
     c->last_frames = frames;
     c->source_form = 0;
     c->sparse_items[0] = 0, c->sparse_items[1] = -1, c->sparse_items[2] = 0;
@@ -1138,7 +1160,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
     // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch, and its T = 4 strip levels as bit strips.
     // The stage entry points keep the 8 response planes there (the bit planes are then packed from them on demand).
-    const PlanInputs pin = call_plan_inputs(c, d_mask0, stride0, frames, img0_fs, bands, level0_gradient_done);
+    const PlanInputs pin = call_plan_inputs(c, src0, mask0, bands, level0_gradient_done);
     const BuildPlan plan = plan_build(pin, all_rows, reset_count != nullptr);
     // off the one-launch builder's grid a batch takes k_build_lm_any, which is sized for strides up to LMA_MAX_T
     if (!all_rows && frames > 1 && !pin.any_batch) {
@@ -1159,16 +1181,20 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const uint8_t* d_img0, int stride
                 lo = std::max(0, (bands->first + b) * br - e);
                 hi = std::min(c->rows[l], (bands->first + b + 1) * br + e);
             }
-            const int64_t img_fs = l == 0 ? img0_fs : (int64_t)c->rows[l] * c->cols[l] * c->channels;
             if (l == 0 && plan.sparse_gradient) {
                 // the source pass: level 1's image and the retained copy; the map waits for the coarse candidates (enqueue_sparse_strips)
                 const QSForm form{QS_SOURCE, c->d_src0.as<uint8_t>(), (int64_t)c->rows[0] * c->cols[0] * c->channels, nullptr, 0, 0, 0, 0};
-                if (int e = launch_quantize(c, s, img, c->rows[0], c->cols[0], stride, c->channels, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(),
-                                            nullptr, nullptr, c->d_img[1].as<uint8_t>(), frames, img_fs, 0, c->rows[0], false, 0, &form))
-                    return e;
+                QuantizeLaunch q;
+                q.src = src0;
+                q.rows = c->rows[0], q.cols = c->cols[0];
+                q.weak = c->cfg.weak_threshold;
+                q.out = c->d_quant[0].as<uint8_t>();
+                q.pyr = c->d_img[1].as<uint8_t>();
+                q.form = &form;
+                if (int e = launch_quantize(c, s, q)) return e;
                 continue;
             }
-            if (int e = enqueue_gradient_level(c, s, l, b == 0, img, stride, mask, mask_fs, frames, img_fs, lo, hi)) return e;
+            if (int e = enqueue_gradient_level(c, s, l, b == 0, cur, lo, hi)) return e;
         }
         if (!all_rows && !pin.any_batch)
             if (int e = launch_build_lm(c, s, l)) return e;
@@ -1226,9 +1252,12 @@ int ensure_level0_map(sbm_ctx* c, hipStream_t s)
     if (c->map0_whole || c->levels_valid < 1) return 0;
     const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
     if (!c->d_src0.p || (size_t)c->last_frames * rows * cols * ch > c->d_src0.cap) return fail(SBM_ERR_STATE, "level 0's source is not retained");
-    if (int e = launch_quantize(c, s, c->d_src0.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(), nullptr,
-                                nullptr, nullptr, c->last_frames, (int64_t)rows * cols * ch))
-        return e;
+    QuantizeLaunch q;
+    q.src = retained_frames(c, ch, c->last_frames);
+    q.rows = rows, q.cols = cols;
+    q.weak = c->cfg.weak_threshold;
+    q.out = c->d_quant[0].as<uint8_t>();
+    if (int e = launch_quantize(c, s, q)) return e;
     c->map0_whole = true;
     return 0;
 }
@@ -1279,16 +1308,13 @@ int prepare_templates(sbm_ctx* c, float threshold, int64_t cap)
 // One match call as every entry point describes it: frames of rows x cols x ch pixels, frame_stride bytes apart, against the
 // active templates; per frame up to cap records into out and a {n_matches, overflow} pair into counts (device memory)
 struct MatchCall {
-    const uint8_t* img;
-    int rows, cols, stride, ch;
-    const uint8_t* mask;
+    FrameSource src;
+    MaskSource mask;
+    int rows, cols;
     float thr;
     sbm_match_rec* out;
     int64_t cap;
     int32_t* counts;
-    int frames;
-    int64_t frame_stride;
-    int64_t mask_stride = 0; // bytes from frame f's mask to frame f + 1's; 0: the mask, if any, is shared by the frames
 };
 
 int check_stride(int stride, int cols, int ch)
@@ -1298,14 +1324,12 @@ int check_stride(int stride, int cols, int ch)
 
 int check_match_call(const sbm_ctx* c, const MatchCall& m)
 {
-    if (!c || !m.img || !m.out || !m.counts) return fail(SBM_ERR_INVALID, "null argument");
-    if (m.frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
-    if (int e = check_stride(m.stride, m.cols, m.ch)) return e;
-    if (m.frames > 1 && m.frame_stride < (int64_t)m.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
-    // (one frame: the stride is not read -- but it must not be the mark of the table form, sbm_frame_ptrs_plan.h)
-    // (... nor that of the plane form, sbm_frame_planes_plan.h)
-    if (fs_names_table(m.frame_stride)) return fail(SBM_ERR_INVALID, "frame_stride out of range");
-    if (m.mask_stride && (!m.mask || m.mask_stride < (int64_t)m.rows * m.cols)) return fail(SBM_ERR_INVALID, "mask_stride smaller than one mask");
+    if (!c || !m.src.base || !m.out || !m.counts) return fail(SBM_ERR_INVALID, "null argument");
+    if (m.src.frames < 1) return fail(SBM_ERR_INVALID, "n_frames must be >= 1");
+    if (int e = check_stride(m.src.stride, m.cols, m.src.ch)) return e;
+    // (one frame: the frame stride is not read)
+    if (m.src.frames > 1 && m.src.frame_stride < (int64_t)m.src.stride * m.rows) return fail(SBM_ERR_INVALID, "frame_stride smaller than one frame");
+    if (m.mask.kind == MASK_STRIDED && m.mask.stride < (int64_t)m.rows * m.cols) return fail(SBM_ERR_INVALID, "mask_stride smaller than one mask");
     return 0;
 }
 
@@ -1315,9 +1339,9 @@ int check_match_call(const sbm_ctx* c, const MatchCall& m)
 // of the call happens here too (it may synchronise), so that the launches can be replayed as a graph.
 int settle_match_state(sbm_ctx* c, const MatchCall& m, const Bands* bands, bool also_dirty)
 {
-    const bool frame_masks = m.mask_stride != 0;
-    if (match_dirty(c, m.rows, m.cols, m.ch, m.frames, m.thr) || also_dirty || (frame_masks && m.frames > c->mask_frames)) HIP_TRY(hipDeviceSynchronize());
-    if (int e = ensure_geometry(c, m.rows, m.cols, m.ch, m.frames, frame_masks)) return e;
+    const bool frame_masks = masks_per_frame(m.mask);
+    if (match_dirty(c, m.rows, m.cols, m.src.ch, m.src.frames, m.thr) || also_dirty || (frame_masks && m.src.frames > c->mask_frames)) HIP_TRY(hipDeviceSynchronize());
+    if (int e = ensure_geometry(c, m.rows, m.cols, m.src.ch, m.src.frames, frame_masks)) return e;
     if (bands)
         if (int e = check_bands(c, bands->n)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
@@ -1597,7 +1621,6 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     if (!c->map0_whole) {
         // the call ran the source pass only (BuildPlan::sparse_gradient): level 0's gradient stage now, from the retained
         // source, in the work items whose output the flagged tiles' builders load.  The map stays in pieces (map0_whole).
-        const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
         QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
         form.need_rects = rects;
         form.n_bands = n_bands;
@@ -1605,9 +1628,13 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
             HIP_TRY(hipMemsetAsync(c->d_sparse_items.p, 0, sizeof(int32_t), s));
             form.item_count = c->d_sparse_items.as<int32_t>();
         }
-        if (int e = launch_quantize(c, s, c->d_src0.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(),
-                                    nullptr, nullptr, nullptr, frames, (int64_t)rows * cols * ch, 0, rows, false, 0, &form))
-            return e;
+        QuantizeLaunch q;
+        q.src = retained_frames(c, c->src0_ch, frames);
+        q.rows = c->rows[0], q.cols = c->cols[0];
+        q.weak = c->cfg.weak_threshold;
+        q.out = c->d_quant[0].as<uint8_t>();
+        q.form = &form;
+        if (int e = launch_quantize(c, s, q)) return e;
     }
     LmArgs a;
     memset(&a, 0, sizeof a);
@@ -1692,14 +1719,6 @@ bool graph_wanted(const sbm_ctx* c, int kind)
     return kind != 0 && c->pipeline_depth >= 2 && !c->auto_graph_off;
 }
 
-bool graph_key_equal(const sbm_ctx::GraphEntry& g, const sbm_ctx::GraphEntry& k)
-{
-    return g.img == k.img && g.rows == k.rows && g.cols == k.cols && g.stride == k.stride && g.ch == k.ch && g.mask == k.mask &&
-           g.thr_bits == k.thr_bits && g.out == k.out && g.cap == k.cap && g.count == k.count && g.mo == k.mo && g.mc == k.mc &&
-           g.frames == k.frames && g.frame_stride == k.frame_stride && g.mask_stride == k.mask_stride && g.sparse_grad == k.sparse_grad &&
-           g.sparse_rects == k.sparse_rects;
-}
-
 constexpr size_t GRAPH_CACHE = 16;
 
 // Replay the graph captured for this argument tuple on stream s, capturing it first if need be (capture(&graph) records
@@ -1707,16 +1726,16 @@ constexpr size_t GRAPH_CACHE = 16;
 // itself -- auto mode, a tuple seen for the first time (callers whose buffers never repeat must not pay a capture per
 // call) or a caller whose tuples keep changing.
 template <class Capture>
-int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool* launched, Capture capture)
+int graph_replay(sbm_ctx* c, const GraphKey& key, hipStream_t s, bool* launched, Capture capture)
 {
     *launched = false;
     sbm_ctx::GraphEntry* hit = nullptr;
     for (auto& g : c->graphs)
-        if (graph_key_equal(g, key)) hit = &g;
+        if (g.key == key) hit = &g;
     if (!hit) {
         if (c->graph_pref < 0) {
             bool seen = false;
-            for (auto& g : c->graph_seen) seen = seen || graph_key_equal(g, key);
+            for (auto& k : c->graph_seen) seen = seen || k == key;
             if (!seen) {
                 if (c->graph_seen.size() >= 64) c->graph_seen.erase(c->graph_seen.begin());
                 c->graph_seen.push_back(key);
@@ -1736,7 +1755,8 @@ int graph_replay(sbm_ctx* c, const sbm_ctx::GraphEntry& key, hipStream_t s, bool
             (void)hipGraphDestroy(c->graphs[lru].graph);
             c->graphs.erase(c->graphs.begin() + lru);
         }
-        sbm_ctx::GraphEntry ge = key;
+        sbm_ctx::GraphEntry ge;
+        ge.key = key;
         if (int e = capture(&ge.graph)) return e;
         hipError_t he = hipGraphInstantiate(&ge.exec, ge.graph, nullptr, nullptr, 0);
         if (he != hipSuccess) {
@@ -1794,8 +1814,8 @@ void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch,
 // every launch of a match call, in order
 int enqueue_match(sbm_ctx* c, hipStream_t s, const MatchCall& m, const Bands* bands = nullptr, bool level0_gradient_done = false)
 {
-    if (int e = enqueue_pyramid(c, s, m.img, m.stride, m.mask, m.counts, m.frames, m.frame_stride, bands, level0_gradient_done, m.mask_stride)) return e;
-    return enqueue_loop(c, s, m.out, m.cap, m.counts, m.frames, false);
+    if (int e = enqueue_pyramid(c, s, m.src, m.mask, m.counts, bands, level0_gradient_done)) return e;
+    return enqueue_loop(c, s, m.out, m.cap, m.counts, m.src.frames, false);
 }
 
 // The whole match() of one frame as a DAG, recorded by stream capture on the context's two private streams:
@@ -1807,13 +1827,10 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
 {
     const int L = c->L;
     hipStream_t st = c->stream, sd = c->side;
-    const uint8_t* img = m.img;
-    int stride = m.stride;
-    const uint8_t* mask = m.mask;
-    int64_t mask_fs = 0; // one frame
+    PyramidCursor cur{m.src, m.mask}; // one frame
     bool forked = false;
     for (int l = 0; l < L; ++l) {
-        if (int e = enqueue_gradient_level(c, st, l, true, img, stride, mask, mask_fs, 1, 0, 0, c->rows[l])) return e; // one frame: no frame stride
+        if (int e = enqueue_gradient_level(c, st, l, true, cur, 0, c->rows[l])) return e;
         const bool fork = l < L - 1 && tuning().graph_fork;
         if (fork && (hipEventRecord(c->ev_fork[l], st) != hipSuccess || hipStreamWaitEvent(sd, c->ev_fork[l], 0) != hipSuccess))
             return fail(SBM_ERR_HIP, "graph fork failed");
@@ -1829,16 +1846,21 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
 }
 
 // kind: 0 single frame, > 0 frames of a batch, -1 the template loop alone (graph_wanted).  The key of the call's captured graph:
-sbm_ctx::GraphEntry graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
+GraphKey graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
 {
-    uint32_t thr_bits;
-    memcpy(&thr_bits, &m.thr, 4);
-    // (the template loop has no frame stride: what its launches depend on instead is the form every level is held in)
+    GraphKey key;
+    key.src = m.src;
+    key.mask = m.mask;
+    key.rows = m.rows, key.cols = m.cols;
+    memcpy(&key.thr_bits, &m.thr, 4);
+    key.out = m.out, key.cap = m.cap, key.count = m.counts;
+    key.mirror_out = c->mirror_out, key.mirror_count = c->mirror_count;
+    key.kind = kind;
+    // (the template loop has no frames: what its launches depend on instead is the form every level is held in)
+    if (kind < 0) key.forms_signature = forms_signature(c->forms, c->L);
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
-    const bool sparse_grad = kind > 0 && plans_sparse_gradient(c, m.mask, m.stride, m.frames, m.frame_stride, nullptr, false);
-    sbm_ctx::GraphEntry key{m.img, m.rows, m.cols, m.stride, m.ch, m.mask, thr_bits, m.out, m.cap, m.counts, (void*)c->mirror_out, (void*)c->mirror_count,
-                            kind, kind < 0 ? forms_signature(c->forms, c->L) : m.frame_stride, m.mask ? m.mask_stride : 0, nullptr, nullptr, 0, sparse_grad};
-    key.sparse_rects = sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
+    key.sparse_grad = kind > 0 && plans_sparse_gradient(c, m.src, m.mask, nullptr, false);
+    key.sparse_rects = key.sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
     return key;
 }
 
@@ -1859,7 +1881,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             if (int e = ensure_local_forms(c, s)) return e;
         }
         bool launched = false;
-        const sbm_ctx::GraphEntry key = graph_key(c, m, kind);
+        const GraphKey key = graph_key(c, m, kind);
         if (int e = graph_replay(c, key, s, &launched, [&](hipGraph_t* g) {
                 hipStream_t st = c->stream;
                 HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
@@ -1874,7 +1896,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             // builder's where that takes every level, else the batched any-stride builder's; the template loop builds nothing
             if (kind >= 0) {
                 record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects);
-                c->last_frames = m.frames;
+                c->last_frames = m.src.frames;
             }
             return 0;
         }

@@ -266,7 +266,7 @@ int sbm_partition_templates(sbm_ctx* c, int32_t rows, int32_t cols, const int32_
 int sbm_match_device(sbm_ctx* c, const void* d_img, int32_t rows, int32_t cols, int32_t stride, int32_t channels,
                      const void* d_mask, float threshold, void* d_out, int64_t cap, void* d_count, void* stream)
 {
-    const MatchCall m{(const uint8_t*)d_img, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, 0};
+    const MatchCall m{strided_frames(d_img, stride, channels, 1, 0), strided_masks(d_mask, 0), rows, cols, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count};
     if (int e = check_match_call(c, m)) return e;
     hipStream_t s;
     if (int e = begin_match(c, stream, m, &s)) return e;
@@ -277,7 +277,8 @@ int sbm_match_batch_device(sbm_ctx* c, const void* d_imgs, int64_t frame_stride,
                            int32_t stride, int32_t channels, const void* d_mask, float threshold, void* d_out, int64_t cap,
                            void* d_counts, void* stream)
 {
-    const MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames, frame_stride};
+    const MatchCall m{strided_frames(d_imgs, stride, channels, n_frames, frame_stride), strided_masks(d_mask, 0), rows, cols, threshold,
+                      (sbm_match_rec*)d_out, cap, (int32_t*)d_counts};
     if (int e = check_match_call(c, m)) return e;
     hipStream_t s;
     if (int e = begin_match(c, stream, m, &s)) return e;
@@ -289,7 +290,8 @@ int sbm_match_batch_device_masked(sbm_ctx* c, const void* d_imgs, int64_t frame_
                                   int64_t cap, void* d_counts, void* stream)
 {
     if (!d_masks) return fail(SBM_ERR_INVALID, "null masks (sbm_match_batch_device matches without one)");
-    const MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_masks, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_counts, n_frames, frame_stride, mask_stride};
+    const MatchCall m{strided_frames(d_imgs, stride, channels, n_frames, frame_stride), strided_masks(d_masks, mask_stride), rows, cols, threshold,
+                      (sbm_match_rec*)d_out, cap, (int32_t*)d_counts};
     if (int e = check_match_call(c, m)) return e;
     hipStream_t s;
     if (int e = begin_match(c, stream, m, &s)) return e;
@@ -297,34 +299,34 @@ int sbm_match_batch_device_masked(sbm_ctx* c, const void* d_imgs, int64_t frame_
 }
 
 // The frames (and masks) are named by device arrays of addresses that only the level-0 gradient launch reads, on the stream
-// (launch_quantize: the table forms of its kernels).  The call travels as every batch call does, with the tables' addresses in the
-// place of the image and mask pointers and the table form's mark -- which holds the flags -- in the place of the two strides
-// (sbm_frame_ptrs_plan.h): that tuple is also the key of its captured graph, and the tables' contents are no part of it.
+// (launch_quantize: the table forms of its kernels).  The call travels as every batch call does, its frames a FrameSource of kind
+// FRAMES_TABLE that holds the table's address and the flags, its masks a MaskSource of kind MASK_TABLE (sbm_frame_source.h): those
+// records are also part of the key of its captured graph, and the tables' contents are no part of it.
 int sbm_match_batch_device_ptrs(sbm_ctx* c, const void* d_frame_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
                                 int32_t channels, const void* d_mask_ptrs, int32_t flags, float threshold, void* d_out, int64_t cap,
                                 void* d_counts, void* stream)
 {
     if (!c || !d_out || !d_counts) return fail(SBM_ERR_INVALID, "null argument");
     if (const int e = frame_ptrs_check(d_frame_ptrs != nullptr, n_frames, cols, stride, channels, flags)) return fail(SBM_ERR_INVALID, "%s", frame_ptrs_error(e));
-    const MatchCall m{(const uint8_t*)d_frame_ptrs, rows, cols, stride, channels, (const uint8_t*)d_mask_ptrs, threshold, (sbm_match_rec*)d_out, cap,
-                      (int32_t*)d_counts, n_frames, frame_ptrs_fs(flags), d_mask_ptrs ? FP_TABLE_FS : 0};
+    const MatchCall m{table_frames(FRAMES_TABLE, d_frame_ptrs, stride, channels, n_frames, flags), table_masks(d_mask_ptrs), rows, cols, threshold,
+                      (sbm_match_rec*)d_out, cap, (int32_t*)d_counts};
     hipStream_t s;
     if (int e = begin_match(c, stream, m, &s)) return e;
     return match_or_replay(c, s, m, n_frames);
 }
 
 // Planar frames: the table holds three plane addresses per frame and only the level-0 gradient launch reads it (launch_quantize: the
-// plane forms of its kernels).  The call travels as a table call does, with the plane form's own mark in the place of the frame
-// stride (sbm_frame_planes_plan.h) -- part of the key of its captured graph, so a _ptrs graph at the same table address is another
-// graph -- and three channels; the masks, if any, are a table of the _ptrs kind.
+// plane forms of its kernels).  The call travels as a table call does, its frames a FrameSource of kind FRAMES_PLANES with three
+// channels (sbm_frame_source.h) -- the kind is part of the key of its captured graph, so a _ptrs graph at the same table address is
+// another graph; the masks, if any, are a table of mask addresses as a _ptrs call's are.
 int sbm_match_batch_device_planes(sbm_ctx* c, const void* d_plane_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
                                   const void* d_mask_ptrs, int32_t flags, float threshold, void* d_out, int64_t cap, void* d_counts,
                                   void* stream)
 {
     if (!c || !d_out || !d_counts) return fail(SBM_ERR_INVALID, "null argument");
     if (const int e = frame_planes_check(d_plane_ptrs != nullptr, n_frames, cols, stride, flags)) return fail(SBM_ERR_INVALID, "%s", frame_planes_error(e));
-    const MatchCall m{(const uint8_t*)d_plane_ptrs, rows, cols, stride, FPL_CHANNELS, (const uint8_t*)d_mask_ptrs, threshold, (sbm_match_rec*)d_out, cap,
-                      (int32_t*)d_counts, n_frames, frame_planes_fs(flags), d_mask_ptrs ? FP_TABLE_FS : 0};
+    const MatchCall m{table_frames(FRAMES_PLANES, d_plane_ptrs, stride, FPL_CHANNELS, n_frames, flags), table_masks(d_mask_ptrs), rows, cols, threshold,
+                      (sbm_match_rec*)d_out, cap, (int32_t*)d_counts};
     hipStream_t s;
     if (int e = begin_match(c, stream, m, &s)) return e;
     return match_or_replay(c, s, m, n_frames);
@@ -338,7 +340,7 @@ int sbm_match_templates_device(sbm_ctx* c, float threshold, void* d_out, int64_t
     if (templates_dirty(c, threshold)) HIP_TRY(hipDeviceSynchronize());
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     // no image: the pyramid is the resident one
-    const MatchCall m{nullptr, c->rows[0], c->cols[0], 0, 0, nullptr, threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count, 1, 0};
+    const MatchCall m{FrameSource{}, MaskSource{}, c->rows[0], c->cols[0], threshold, (sbm_match_rec*)d_out, cap, (int32_t*)d_count};
     return match_or_replay(c, s, m, -1);
 }
 
@@ -457,8 +459,8 @@ static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_
     const size_t frame_bytes = (size_t)rows * cols * channels, mask_bytes = (size_t)rows * cols;
     // one sub-batch: frames from an input buffer of the pipeline, packed; image, results and frame count follow per sub-batch
     // (and its masks, one per frame, from the mask buffer beside that input buffer)
-    MatchCall m{nullptr, rows, cols, cols * channels, channels, nullptr, threshold, nullptr, cap, nullptr, sub, (int64_t)frame_bytes,
-                masks ? (int64_t)mask_bytes : 0};
+    MatchCall m{packed_frames(nullptr, rows, cols, channels, sub), MaskSource{}, rows, cols, threshold, nullptr, cap, nullptr};
+    if (masks) m.mask.kind = MASK_STRIDED, m.mask.stride = (int64_t)mask_bytes; // (base: the sub-batch's, below)
     if (int e = begin_host_match(c, m, c->citems_dirty)) return e;
     // geometries the one-launch linear-memory builder does not take (level widths that are not multiples of 16, other
     // strides) batch through the any-stride builder (k_build_lm_any) up to T = 16; a pyramid with a larger stride goes one
@@ -483,7 +485,7 @@ static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_
     for (int f = 0; f < n_frames; ++f) h_counts[2 * f] = -1, h_counts[2 * f + 1] = 0;
     if (mask) {
         HIP_TRY(hipMemcpyAsync(c->d_mask[0].p, mask, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
-        m.mask = c->d_mask[0].as<uint8_t>();
+        m.mask = strided_masks(c->d_mask[0].p, 0);
     }
     MirrorScope mirror(c);
     int rc = 0;
@@ -518,11 +520,11 @@ static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_
             rc = fail(SBM_ERR_HIP, "event record / wait failed");
             break;
         }
-        m.img = c->d_in[buf].as<uint8_t>();
-        if (masks) m.mask = c->d_min[buf].as<uint8_t>();
+        m.src.base = c->d_in[buf].p;
+        if (masks) m.mask.base = c->d_min[buf].p;
         m.out = c->d_bout.as<sbm_match_rec>() + (size_t)f0 * cap;
         m.counts = (int32_t*)((char*)c->d_bout.p + rec_bytes) + 2 * f0;
-        m.frames = nf;
+        m.src.frames = nf;
         mirror.to((sbm_match_rec*)c->h_bout + (size_t)f0 * cap, h_counts + 2 * f0);
         rc = enqueue_match(c, c->stream, m);
         if (!rc && hipEventRecord(c->ev_free[buf], c->stream) != hipSuccess) rc = fail(SBM_ERR_HIP, "event record failed");
@@ -643,7 +645,7 @@ static int upload_image_banded(sbm_ctx* c, const uint8_t* img, int rows, int col
     *done = false;
     const int NB = tuning().match_bands;
     const int n_tile_rows = (rows + QT_R - 1) / QT_R;
-    if (NB < 2 || n_tile_rows < 4 * NB || quantize_stream_rows(c, rows, cols, ch, 1, false, 0, cols * ch) != 0) return 0;
+    if (NB < 2 || n_tile_rows < 4 * NB || quantize_stream_rows(c, rows, cols, packed_frames(nullptr, rows, cols, ch, 1), MaskSource{}, false) != 0) return 0;
     if (!img) return fail(SBM_ERR_INVALID, "null image");
     if (int e = check_stride(stride, cols, ch)) return e;
     if (int e = ensure_geometry(c, rows, cols, ch)) return e;
@@ -662,10 +664,16 @@ static int upload_image_banded(sbm_ctx* c, const uint8_t* img, int rows, int col
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_band[j], 0));
         const int t_hi = j + 1 == NB ? n_tile_rows : r1 / QT_R - 1; // the band's last tile row needs the next band's first rows
         if (t_hi > t_lo) {
-            if (int e = launch_quantize(c, c->stream, d, rows, cols, (int)row_bytes, ch, mask ? c->d_mask[0].as<uint8_t>() : nullptr,
-                                        c->cfg.weak_threshold, c->d_quant[0].as<uint8_t>(), nullptr, nullptr,
-                                        c->L > 1 ? c->d_img[1].as<uint8_t>() : nullptr, 1, 0, t_lo * QT_R, std::min(rows, t_hi * QT_R), true))
-                return e;
+            QuantizeLaunch q;
+            q.src = level_frames(c, 0, 1);
+            q.mask = strided_masks(mask ? c->d_mask[0].p : nullptr, 0);
+            q.rows = rows, q.cols = cols;
+            q.weak = c->cfg.weak_threshold;
+            q.out = c->d_quant[0].as<uint8_t>();
+            q.pyr = c->L > 1 ? c->d_img[1].as<uint8_t>() : nullptr;
+            q.row_lo = t_lo * QT_R, q.row_hi = std::min(rows, t_hi * QT_R);
+            q.tile_band = true;
+            if (int e = launch_quantize(c, c->stream, q)) return e;
             t_lo = t_hi;
         }
     }
@@ -703,8 +711,8 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
     }
     // with the pinned mirror the emitting kernel's record capacity is the pinned buffer's (it bounds both copies)
     const int64_t dev_cap = own_mirror ? std::min<int64_t>(c->cand_cap, c->h_res_cap) : c->cand_cap;
-    const MatchCall m{c->d_img[0].as<uint8_t>(), rows, cols, cols * channels, channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr, threshold,
-                      c->d_out.as<sbm_match_rec>(), dev_cap, c->d_outcount.as<int32_t>(), 1, 0};
+    const MatchCall m{level_frames(c, 0, 1), strided_masks(mask ? c->d_mask[0].p : nullptr, 0), rows, cols, threshold,
+                      c->d_out.as<sbm_match_rec>(), dev_cap, c->d_outcount.as<int32_t>()};
     {
         MirrorScope mirror(c);
         if (own_mirror) {
@@ -761,7 +769,7 @@ int sbm_build_pyramid(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols
     if (int e = order_after_caller_work(c)) return e;
     if (c->profiling && !c->profiling_keep) c->clear_timings();
     if (int e = upload_image(c, img, rows, cols, stride, channels, mask)) return e;
-    if (int e = enqueue_pyramid(c, c->stream, c->d_img[0].as<uint8_t>(), cols * channels, mask ? c->d_mask[0].as<uint8_t>() : nullptr)) return e;
+    if (int e = enqueue_pyramid(c, c->stream, level_frames(c, 0, 1), strided_masks(mask ? c->d_mask[0].p : nullptr, 0))) return e;
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->profiling) collect_timings(c);
     return 0;

@@ -182,7 +182,8 @@ extern "C" int sbm_match_batch_device_banded(sbm_ctx* c, const void* d_imgs, int
                                              void* stream)
 {
     if (!c || !d_local) return fail(SBM_ERR_INVALID, "null argument");
-    MatchCall m{(const uint8_t*)d_imgs, rows, cols, stride, channels, (const uint8_t*)d_mask, threshold, (sbm_match_rec*)d_local, cap, (int32_t*)d_local, n_frames, frame_stride};
+    MatchCall m{strided_frames(d_imgs, stride, channels, n_frames, frame_stride), strided_masks(d_mask, 0), rows, cols, threshold,
+                (sbm_match_rec*)d_local, cap, (int32_t*)d_local};
     if (int e = check_match_call(c, m)) return e;
     // this rank's shard, as sbm_match_batch_device_sharded lays it out: the records follow the header of counts
     const size_t header = ((size_t)n_frames * 8 + 15) / 16 * 16;

@@ -15,9 +15,14 @@ int sbm_quantized_orientations(sbm_ctx* c, const uint8_t* img, int32_t rows, int
         return rc;
     if (hipMemcpy2D(d_in.p, (size_t)cols * ch, img, stride, (size_t)cols * ch, rows, hipMemcpyHostToDevice) != hipSuccess)
         return fail(SBM_ERR_HIP, "image upload failed");
-    if ((rc = launch_quantize(c, c->stream, d_in.as<uint8_t>(), rows, cols, cols * ch, ch, nullptr, weak, d_q.as<uint8_t>(),
-                              magnitude ? d_mag.as<float>() : nullptr, angle_ori ? d_ori.as<float>() : nullptr, nullptr)))
-        return rc;
+    QuantizeLaunch q;
+    q.src = packed_frames(d_in.p, rows, cols, ch, 1);
+    q.rows = rows, q.cols = cols;
+    q.weak = weak;
+    q.out = d_q.as<uint8_t>();
+    q.mag = magnitude ? d_mag.as<float>() : nullptr;
+    q.ori = angle_ori ? d_ori.as<float>() : nullptr;
+    if ((rc = launch_quantize(c, c->stream, q))) return rc;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(angle, d_q.p, npx, hipMemcpyDeviceToHost) != hipSuccess ||
         (magnitude && hipMemcpy(magnitude, d_mag.p, npx * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
         (angle_ori && hipMemcpy(angle_ori, d_ori.p, npx * 4, hipMemcpyDeviceToHost) != hipSuccess))

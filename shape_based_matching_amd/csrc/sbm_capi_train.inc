@@ -94,9 +94,14 @@ int train_enqueue(sbm_ctx* c, hipStream_t s, const uint8_t* d_imgs, int64_t img_
             const uint8_t* img = l == 0 ? d_imgs + (int64_t)i * img_stride : base + img_off[l] + img_fs[l] * i;
             const size_t px = (size_t)i * p.pix_stride + v.pix_off;
             // the training side quantises without the mask (ColorGradientPyramid::update); the mask enters with the erosion
-            if (int e = launch_quantize(c, s, img, lr[l], lc[l], l == 0 ? stride : lc[l] * ch, ch, nullptr, c->cfg.weak_threshold,
-                                        (uint8_t*)p.quant + px, (float*)p.mag + px, (float*)p.ori + px, nullptr))
-                return e;
+            QuantizeLaunch q;
+            q.src = l == 0 ? strided_frames(img, stride, ch, 1, 0) : packed_frames(img, lr[l], lc[l], ch, 1);
+            q.rows = lr[l], q.cols = lc[l];
+            q.weak = c->cfg.weak_threshold;
+            q.out = (uint8_t*)p.quant + px;
+            q.mag = (float*)p.mag + px;
+            q.ori = (float*)p.ori + px;
+            if (int e = launch_quantize(c, s, q)) return e;
         }
     }
     const int gx0 = (int)std::min<size_t>(((size_t)rows * cols + 255) / 256, 4096);

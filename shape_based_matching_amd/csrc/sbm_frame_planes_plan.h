@@ -1,8 +1,9 @@
 // sbm_frame_planes_plan.h — the host rules of the batched match on planar frames (sbm_match_batch_device_planes: the loop of
 // Detector::match, line2Dup.cpp:1078, over frames whose three channels are three planes anywhere in device memory, named by a device
 // table of 3 * n_frames addresses).  As with the table of frame pointers (sbm_frame_ptrs_plan.h) the host never reads the table: what
-// it decides it decides from the call's integers.  Plain integer code, no HIP types: launch_quantize and the entry point call it,
-// tests/test_frame_planes_plan.py compiles it for the CPU suite.
+// it decides it decides from the call's integers.  The call travels as a FrameSource of kind FRAMES_PLANES (sbm_frame_source.h); its
+// masks, if any, are a table of mask addresses as a _ptrs call's are.  Plain integer code, no HIP types: the entry point and
+// sbm_frame_source.h call it, tests/test_frame_planes_plan.py compiles it for the CPU suite.
 #pragma once
 #include <stdint.h>
 #include "sbm_frame_ptrs_plan.h"
@@ -42,16 +43,5 @@ inline bool frame_planes_source_lines(int flags, int64_t stride, int rows, int c
     (void)flags, (void)stride, (void)rows, (void)cols, (void)knob;
     return false;
 }
-
-// How a plane call travels through the host code that carries "bytes from one frame to the next": like a table call, by a frame
-// stride no layout can have -- one of its own, above every value sbm_frame_ptrs_plan.h reads as ITS mark (that range and its known
-// flags are not widened), so that a captured graph keyed on it never aliases a _ptrs graph at the same table address.  The image
-// pointer beside it is the address of the plane table; the masks of a plane call are a table of sbm_frame_ptrs_plan.h's kind.
-constexpr int64_t FPL_TABLE_FS = INT64_MIN + 16;
-inline int64_t frame_planes_fs(int flags) { return FPL_TABLE_FS + (flags & FPL_KNOWN_FLAGS); }
-inline bool fs_is_planes(int64_t fs) { return fs >= FPL_TABLE_FS && fs <= FPL_TABLE_FS + FPL_KNOWN_FLAGS; }
-inline int fs_planes_flags(int64_t fs) { return fs_is_planes(fs) ? (int)(fs - FPL_TABLE_FS) : 0; }
-// either kind of device table in the place of the frames
-inline bool fs_names_table(int64_t fs) { return fs_is_table(fs) || fs_is_planes(fs); }
 
 } // namespace sbm

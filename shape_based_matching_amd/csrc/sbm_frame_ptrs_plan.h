@@ -1,8 +1,9 @@
 // sbm_frame_ptrs_plan.h — the host rules of the batched match from a device table of frame pointers
 // (sbm_match_batch_device_ptrs: the loop of Detector::match, line2Dup.cpp:1078, over frames that lie anywhere in device memory).
 // The host never reads the table, so everything it decides it decides from the call's integers: whether the arguments are
-// acceptable, and which form of the sparse path's source pass the call takes.  Plain integer code, no HIP types: launch_quantize
-// and the entry point call it, tests/test_frame_ptrs_plan.py compiles it for the CPU suite.
+// acceptable, and which form of the sparse path's source pass the call takes.  How the call travels through the host code is
+// sbm_frame_source.h's business (a FrameSource of kind FRAMES_TABLE, which holds the flags).  Plain integer code, no HIP types: the
+// entry point and sbm_frame_source.h call it, tests/test_frame_ptrs_plan.py compiles it for the CPU suite.
 #pragma once
 #include <stdint.h>
 #include "sbm_source_lines_plan.h"
@@ -43,13 +44,5 @@ inline bool frame_ptrs_source_lines(int flags, int64_t stride, int rows, int col
 {
     return knob && (flags & FP_ALIGNED4) != 0 && source_lines_ok(0, stride, 0, 1, rows, cols, ch);
 }
-
-// How a table call travels through the host code that carries "bytes from one frame to the next": a frame stride no layout can
-// have names the table form and holds the call's flags (so a captured graph is keyed on them, where a contiguous call's is keyed
-// on its stride); the masks' stride likewise.  The image / mask pointer beside it is then the table's address.
-constexpr int64_t FP_TABLE_FS = INT64_MIN;
-inline int64_t frame_ptrs_fs(int flags) { return FP_TABLE_FS + (flags & FP_KNOWN_FLAGS); }
-inline bool fs_is_table(int64_t fs) { return fs <= FP_TABLE_FS + FP_KNOWN_FLAGS; }
-inline int fs_table_flags(int64_t fs) { return fs_is_table(fs) ? (int)(fs - FP_TABLE_FS) : 0; }
 
 } // namespace sbm

@@ -1,6 +1,6 @@
-// TEST INFRASTRUCTURE: shape_based_matching_amd/csrc/sbm_frame_planes_plan.h -- the argument check, the source-pass form rule and the
-// mark of sbm_match_batch_device_planes -- behind a C interface, beside the mark of the table of frame pointers it must not alias
-// (sbm_frame_ptrs_plan.h).  Compiled by tests/test_frame_planes_plan.py into its temporary directory; never loaded by the product.
+// TEST INFRASTRUCTURE: shape_based_matching_amd/csrc/sbm_frame_planes_plan.h -- the argument check and the source-pass form rule of
+// sbm_match_batch_device_planes -- behind a C interface.  Compiled by tests/test_frame_planes_plan.py into its temporary directory;
+// never loaded by the product.
 #include "sbm_frame_planes_plan.h"
 
 using namespace sbm;
@@ -18,12 +18,3 @@ extern "C" int sbm_emu_frame_planes_lines(int flags, int64_t stride, int rows, i
 }
 
 extern "C" int sbm_emu_frame_planes_channels() { return FPL_CHANNELS; }
-
-// the mark a plane call carries in the place of a frame stride
-extern "C" int64_t sbm_emu_frame_planes_fs(int flags) { return frame_planes_fs(flags); }
-extern "C" int sbm_emu_fs_is_planes(int64_t fs) { return fs_is_planes(fs) ? 1 : 0; }
-extern "C" int sbm_emu_fs_planes_flags(int64_t fs) { return fs_planes_flags(fs); }
-extern "C" int sbm_emu_fs_names_table(int64_t fs) { return fs_names_table(fs) ? 1 : 0; }
-// ... and the _ptrs mark beside it
-extern "C" int64_t sbm_emu_frame_ptrs_fs(int flags) { return frame_ptrs_fs(flags); }
-extern "C" int sbm_emu_fs_is_table(int64_t fs) { return fs_is_table(fs) ? 1 : 0; }

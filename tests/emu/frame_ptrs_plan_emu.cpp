@@ -21,7 +21,3 @@ extern "C" int sbm_emu_source_lines_ok(uint64_t base, int64_t stride, int64_t fr
 {
     return source_lines_ok(base, stride, frame_stride, frames, rows, cols, ch) ? 1 : 0;
 }
-
-// the mark a table call carries in the place of a frame stride: round trip of the flags, and no stride a layout can have
-extern "C" int sbm_emu_frame_ptrs_fs_roundtrip(int flags) { return fs_is_table(frame_ptrs_fs(flags)) ? fs_table_flags(frame_ptrs_fs(flags)) : -1; }
-extern "C" int sbm_emu_fs_is_table(int64_t fs) { return fs_is_table(fs) ? 1 : 0; }

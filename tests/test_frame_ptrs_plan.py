@@ -33,8 +33,6 @@ def emu(tmp_path_factory):
     L.sbm_emu_frame_ptrs_error.restype = C.c_char_p
     L.sbm_emu_frame_ptrs_lines.argtypes = [i, i64, i, i, i, i]
     L.sbm_emu_source_lines_ok.argtypes = [C.c_uint64, i64, i64, i, i, i, i]
-    L.sbm_emu_frame_ptrs_fs_roundtrip.argtypes = [i]
-    L.sbm_emu_fs_is_table.argtypes = [i64]
     return L
 
 
@@ -96,10 +94,3 @@ def test_rule_agrees_with_the_contiguous_rule(emu):
             assert emu.sbm_emu_frame_ptrs_lines(ALIGNED4, stride, rows, cols, ch, 1) == want, (rows, cols, ch, pad, frames, base)
             n += want
     assert n > 20  # the grid holds layouts of both kinds
-
-
-def test_table_mark_is_no_frame_stride(emu):
-    for flags in (0, ALIGNED4):
-        assert emu.sbm_emu_frame_ptrs_fs_roundtrip(flags) == flags
-    for fs in (0, 1, -1, 4096, -4096, 2 ** 62, -(2 ** 62), 2 ** 63 - 1, -(2 ** 63) + 2):
-        assert emu.sbm_emu_fs_is_table(fs) == 0, fs
