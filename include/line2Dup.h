@@ -195,11 +195,24 @@ public:
      * call of a loop of addTemplate(sources[k], class_id, object_masks[k], sscales[k], orientations[k], ...) returns (a
      * failed template returns -1 and takes no id) and the detector afterwards is identical to the loop's.  object_masks:
      * empty, or one per source (an empty Mat = no mask); sscales / orientations: empty (addTemplate's defaults) or one per
-     * source.  Sources of one size and type are trained together on the device (sbm_train_batch). */
+     * source.  num_features_each: empty (num_features for all) or one count per source, the loop's last argument.
+     * Sources of one size and type without counts of their own are trained together by sbm_train_batch, as before; any
+     * other list goes through sbm_train_ragged, all sizes and counts in one call. */
     std::vector<int> addTemplates(const std::vector<cv::Mat>& sources, const std::string& class_id,
                                   const std::vector<cv::Mat>& object_masks, const std::vector<float>& sscales = {},
                                   const std::vector<float>& orientations = {}, int tagFieldID = 0,
-                                  std::string fiducial_src = "none", int num_features = 0);
+                                  std::string fiducial_src = "none", int num_features = 0,
+                                  const std::vector<int>& num_features_each = {});
+
+    /* The scale sweep of one source: the loop of addTemplate(resize(source, scales[k]), class_id,
+     * resize(object_mask, scales[k]) > 0, sscales[k], orientations[k], tagFieldID, fiducial_src, num_features_each[k])
+     * with cv::resize(src, dst, Size(), s, s) as shapeInfo_producer::transform calls it (reference line2Dup.h:379-405,
+     * 455-457).  The source and the mask are uploaded once and resized on the device (sbm_train_sweep).  object_mask:
+     * empty = none; sscales / orientations / num_features_each: empty (addTemplate's defaults) or one per scale. */
+    std::vector<int> addTemplatesScaled(const cv::Mat& source, const std::string& class_id, const cv::Mat& object_mask,
+                                        const std::vector<float>& scales, const std::vector<float>& sscales = {},
+                                        const std::vector<float>& orientations = {}, int tagFieldID = 0,
+                                        std::string fiducial_src = "none", const std::vector<int>& num_features_each = {});
 
     int addTemplate_rotate(const std::string& class_id, int zero_id, float theta, cv::Point2f center);
 
@@ -333,6 +346,14 @@ public:
     void produce_infos();
     cv::Mat src_of(const Info& info) { return transform(src, info.angle, info.scale); }
     cv::Mat mask_of(const Info& info);
+
+    /* MI355X extension: the loop of detector.addTemplate(src_of(info), class_id, mask_of(info), sscales[k],
+     * orientations[k], tagFieldID, fiducial_src, num_features_each[k]) over `infos` (test.cpp:181-192), element k what the
+     * k-th call returns.  Maximal runs of consecutive infos in one rotation class (none, 90, 180, 270 by ANGLE_TOLERANCE)
+     * go through one Detector::addTemplatesScaled each; the rotation is done on the host once per run. */
+    std::vector<int> addTemplates(line2Dup::Detector& detector, const std::string& class_id, const std::vector<Info>& infos,
+                                  const std::vector<float>& sscales = {}, const std::vector<float>& orientations = {}, int tagFieldID = 0,
+                                  std::string fiducial_src = "none", const std::vector<int>& num_features_each = {});
 
     static void save_infos(std::vector<Info>& infos, std::string path = "infos.yaml");
     static std::vector<Info> load_infos(std::string path = "info.yaml");

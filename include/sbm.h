@@ -565,6 +565,62 @@ int sbm_train_batch(sbm_ctx* ctx, const uint8_t* const* imgs, int32_t n_images, 
                     int32_t num_features, sbm_template_level* levels, sbm_train_feature* feats, int64_t feat_cap,
                     int32_t* status);
 
+/* ---- ragged batched training -------------------------------------------------
+ * The same, for images of different sizes and feature counts in one call: the training loop of the reference's
+ * test.cpp:scale_test("train") (:162-200) calls addTemplate on shapes.src_of(info) over scale_range {0.1, 1} in steps of
+ * 0.01, 91 sources of 91 sizes, which as one-geometry batches are 91 batches of one image.  Here every kernel after the
+ * per-image gradient launches runs once for the batch, the image (and the pyramid level) a grid dimension; each
+ * (image, level) reads its own record of a device table, so a batch costs about its largest image, not the sum.
+ * Image i is exactly what sbm_train_batch makes of it alone; one image's failure or overflow touches nothing of another.
+ *   levels[i * n_levels + l], status[2 * i], status[2 * i + 1]   as sbm_train_batch
+ *   feats[images[i].feat_first ...]   the image's block of images[i].feat_cap records; feature_offset counts from it
+ * An image too small for the pyramid is no error of the call: levels are built while both sides are >= 5 (the 5 x 5
+ * scan of extractTemplate, :452-539, has no pixel in a smaller one), and the image ends with status {1, first failing
+ * level} as addTemplate returns -1 for it (:1343) and the loop goes on.  SBM_ERR_INVALID, with nothing enqueued:
+ * n_images outside 1 .. 65535, channels not 1 or 3, rows or cols outside 1 .. 32767, stride < cols * channels,
+ * num_features < 1 or halved to fewer than 2 at the last level, a negative feat_cap or feat_first, feature blocks that
+ * overlap, a null image.  Fewer than 2, not 1 as in sbm_train_batch: asked for ONE feature, selectScatteredFeatures
+ * (:163-212) never returns once the level has a candidate (its first candidate is always enough, so it clears and
+ * widens the distance for ever), and a kernel that follows it would not end; these calls refuse the count instead. */
+typedef struct sbm_train_image { /* 48 bytes */
+    const void* img;             /* first pixel; a device address in the _device form, a host address in the host form */
+    const void* mask;            /* rows x cols bytes, rows packed; NULL: none */
+    int32_t rows, cols, stride, num_features;
+    int64_t feat_first, feat_cap; /* this image's block of the feature array, in records */
+} sbm_train_image;
+
+/* Device form.  `images` is a HOST array, read during the call only; img and mask are device addresses.  d_levels:
+ * n_images * n_levels sbm_template_level; d_feats: the feature array the blocks lie in; d_status: n_images * 2 int32.
+ * Stream-ordered on `stream` (NULL: the context's): the table of records travels on the stream from a pinned slot, so
+ * calls enqueued back to back need no synchronisation between them -- a call waits on the host only for the PREVIOUS
+ * call's table copy to have left the slot, and for the device when the scratch has to grow.  The
+ * one-training-scratch-per-context rule of sbm_train_batch_device stands.  Not capturable into a hipGraph (the host
+ * wait, and the table's contents are the call's). */
+int sbm_train_ragged_device(sbm_ctx* ctx, const sbm_train_image* images, int32_t n_images, int32_t channels,
+                            float strong_threshold, void* d_levels, void* d_feats, void* d_status, void* stream);
+/* Host form: img and mask are host addresses, feats a host array that holds every block.  Uploads, runs the device form
+ * on the context's stream, downloads and synchronises. */
+int sbm_train_ragged(sbm_ctx* ctx, const sbm_train_image* images, int32_t n_images, int32_t channels,
+                     float strong_threshold, sbm_template_level* levels, sbm_train_feature* feats, int32_t* status);
+
+/* The scale sweep of shapeInfo_producer (line2Dup.h:379-405, 451-457: transform resizes the source, mask_of the mask and
+ * thresholds it `> 0`): scale k trains cv::resize(img, Size(), fx, fy) under the equally resized mask, non-zero staying
+ * non-zero.  One source, uploaded once; one resize launch for all scales (sizes as sbm_resize_linear(out = NULL)
+ * reports them); the scaled images live in the context's scratch, and from there on the call is the ragged one, scale k
+ * its image k.  A scale that resizes to an empty image: SBM_ERR_INVALID for the call.  Not capturable either. */
+typedef struct sbm_train_scale {
+    double fx, fy;
+    int32_t num_features, reserved;
+    int64_t feat_first, feat_cap;
+} sbm_train_scale;
+
+int sbm_train_sweep_device(sbm_ctx* ctx, const void* d_img, int32_t rows, int32_t cols, int32_t stride, int32_t channels,
+                           const void* d_mask, const sbm_train_scale* scales, int32_t n_scales, float strong_threshold,
+                           void* d_levels, void* d_feats, void* d_status, void* stream);
+int sbm_train_sweep(sbm_ctx* ctx, const uint8_t* img_host, int32_t rows, int32_t cols, int32_t stride, int32_t channels,
+                    const uint8_t* mask_host, const sbm_train_scale* scales, int32_t n_scales, float strong_threshold,
+                    sbm_template_level* levels, sbm_train_feature* feats, int32_t* status);
+
 /* ---- measurement ---------------------------------------------------------
  * Per-kernel HIP-event timings of the last sbm_match/sbm_build_pyramid/
  * sbm_match_templates call when profiling was enabled (adds synchronisation;

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "sbm_select_templates", "sbm_partition_templates", "sbm_match_sharded",
     "sbm_match_batch_host", "sbm_match_batch_host_begin", "sbm_match_batch_host_end", "sbm_extract_local_maxima",
     "sbm_train_batch", "sbm_train_batch_device",
+    "sbm_train_ragged", "sbm_train_ragged_device", "sbm_train_sweep", "sbm_train_sweep_device",
     "sbm_set_pipeline_depth", "sbm_set_coarse_mode", "sbm_set_refine_order", "sbm_set_refine_bits", "sbm_get_coarse_bitplanes",
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
@@ -68,6 +69,32 @@ class SbmNmsParams(C.Structure):
         ("nms_threshold", C.c_float),
         ("eta", C.c_float),
         ("top_k", C.c_int32),
+    ]
+
+
+class SbmTrainImage(C.Structure):
+    """sbm_train_image: one image of a ragged training call (48 bytes)"""
+    _fields_ = [
+        ("img", C.c_void_p),
+        ("mask", C.c_void_p),
+        ("rows", C.c_int32),
+        ("cols", C.c_int32),
+        ("stride", C.c_int32),
+        ("num_features", C.c_int32),
+        ("feat_first", C.c_int64),
+        ("feat_cap", C.c_int64),
+    ]
+
+
+class SbmTrainScale(C.Structure):
+    """sbm_train_scale: one scale of a training sweep (40 bytes)"""
+    _fields_ = [
+        ("fx", C.c_double),
+        ("fy", C.c_double),
+        ("num_features", C.c_int32),
+        ("reserved", C.c_int32),
+        ("feat_first", C.c_int64),
+        ("feat_cap", C.c_int64),
     ]
 
 
@@ -226,6 +253,10 @@ def lib() -> C.CDLL:
     L.sbm_extract_local_maxima.argtypes = [vp, vp, vp, i32, i32, f32, vp, i64, C.POINTER(i64)]
     L.sbm_train_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, i64, f32, i32, vp, vp, i64, vp, vp]
     L.sbm_train_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, f32, i32, vp, vp, i64, vp]
+    L.sbm_train_ragged_device.argtypes = [vp, vp, i32, i32, f32, vp, vp, vp, vp]
+    L.sbm_train_ragged.argtypes = [vp, vp, i32, i32, f32, vp, vp, vp]
+    L.sbm_train_sweep_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, vp, vp]
+    L.sbm_train_sweep.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, vp]
     L.sbm_set_pipeline_depth.argtypes = [vp, i32]
     L.sbm_set_coarse_mode.argtypes = [vp, i32]
     L.sbm_set_refine_order.argtypes = [vp, i32]
@@ -524,6 +555,112 @@ class Context:
                 raise SbmError(-3, f"image {i}: {status[i, 1]} features exceed the capacity {cap}")
             out.append((levels[i].copy(), feats[i, : status[i, 1]].copy()))
         return out
+
+    # ---- ragged batched training: images of different sizes and feature counts in one call --------------------------
+    def _feature_cap(self, rows: int, cols: int) -> int:
+        """no more accepted maxima than 3 x 3 cells, level by level: the most features an image can have"""
+        return sum(((rows >> l) + 2) // 3 * (((cols >> l) + 2) // 3) for l in range(self.n_levels))
+
+    def train_ragged_device(self, images: Sequence["SbmTrainImage"], channels: int, strong_threshold: float, d_levels: int, d_feats: int,
+                            d_status: int, stream: int = 0):
+        """sbm_train_ragged_device: `images` are descriptors of device images (read during the call only); image i's
+        n_levels level records at d_levels, its features in its own block of d_feats, {status, count} at d_status + 2*i."""
+        arr = (SbmTrainImage * max(len(images), 1))(*images)
+        _check(lib().sbm_train_ragged_device(self._h, arr, len(images), channels, C.c_float(strong_threshold), C.c_void_p(d_levels),
+                                             C.c_void_p(d_feats) if d_feats else None, C.c_void_p(d_status),
+                                             C.c_void_p(stream) if stream else None))
+
+    def train_ragged_raw(self, imgs: Sequence[np.ndarray], masks: Optional[Sequence[Optional[np.ndarray]]], strong_threshold: float,
+                         num_features_each: Sequence[int], feat_caps: Sequence[int], feat_firsts: Optional[Sequence[int]] = None,
+                         feats: Optional[np.ndarray] = None):
+        """sbm_train_ragged as it is: (levels[n, n_levels], feats[total], status[n, 2], firsts[n]).  Image i's block of
+        feat_caps[i] records starts at feat_firsts[i] (None: the blocks behind each other); `feats`, if given, is the
+        feature array the call writes into (a caller's fill stays where no block lies)."""
+        arrs = [_img(im) for im in imgs]
+        n = len(arrs)
+        ch = arrs[0][3] if arrs else 3
+        if any(a[3] != ch for a in arrs):
+            raise ValueError("the images of a call share the number of channels")
+        ms = [None] * n if masks is None else [None if m is None else np.ascontiguousarray(m, np.uint8) for m in masks]
+        if len(ms) != n or any(m is not None and m.shape != (a[1], a[2]) for m, a in zip(ms, arrs)):
+            raise ValueError("masks: None, or one (rows, cols) array or None per image")
+        if len(num_features_each) != n or len(feat_caps) != n:
+            raise ValueError("one feature count and one capacity per image")
+        firsts = list(np.cumsum([0] + [max(int(c), 0) for c in feat_caps])[:-1]) if feat_firsts is None else list(feat_firsts)
+        desc = (SbmTrainImage * max(n, 1))()
+        for i, (a, r, c, _) in enumerate(arrs):
+            desc[i] = SbmTrainImage(a.ctypes.data, None if ms[i] is None else ms[i].ctypes.data, r, c, c * ch, int(num_features_each[i]),
+                                    int(firsts[i]), int(feat_caps[i]))
+        end = max([int(f) + max(int(c), 0) for f, c in zip(firsts, feat_caps)] + [0])
+        if feats is None:
+            feats = np.zeros(max(end, 1), TRAIN_FEATURE_DTYPE)
+        levels = np.zeros((n, self.n_levels), LEVEL_DTYPE)
+        status = np.zeros((n, 2), np.int32)
+        _check(lib().sbm_train_ragged(self._h, desc, n, ch, C.c_float(strong_threshold), _p(levels), _p(feats), _p(status)))
+        return levels, feats, status, firsts
+
+    @staticmethod
+    def _train_results(levels, feats, status, firsts, caps):
+        out = []
+        for i in range(len(levels)):
+            if status[i, 0] == 1:
+                out.append(None)
+                continue
+            if status[i, 0] != 0:
+                raise SbmError(-3, f"image {i}: {status[i, 1]} features exceed the capacity {caps[i]}")
+            out.append((levels[i].copy(), feats[firsts[i]: firsts[i] + status[i, 1]].copy()))
+        return out
+
+    def train_ragged_status(self, imgs: Sequence[np.ndarray], masks: Optional[Sequence[Optional[np.ndarray]]], strong: float,
+                            num_features_each: Sequence[int]):
+        """train_ragged and the status array [n, 2]: {0, features} | {1, first failing level}"""
+        caps = [self._feature_cap(*_img(im)[1:3]) for im in imgs]
+        levels, feats, status, firsts = self.train_ragged_raw(imgs, masks, strong, num_features_each, caps)
+        return self._train_results(levels, feats, status, firsts, caps), status
+
+    def train_ragged(self, imgs: Sequence[np.ndarray], masks: Optional[Sequence[Optional[np.ndarray]]], strong: float,
+                     num_features_each: Sequence[int]):
+        """Detector::addTemplate(imgs[i], masks[i], num_features_each[i]) for images of any sizes in one call: a list of
+        (levels, feats), None where addTemplate returns -1 (an image too small for the pyramid included)."""
+        return self.train_ragged_status(imgs, masks, strong, num_features_each)[0]
+
+    def sweep_dims(self, rows: int, cols: int, fx: float, fy: float):
+        """the size cv::resize(img, Size(), fx, fy) gives a rows x cols image (sbm_resize_linear's size query)"""
+        dr, dc = C.c_int32(0), C.c_int32(0)
+        probe = np.zeros(1, np.uint8)
+        _check(lib().sbm_resize_linear(self._h, _p(probe), rows, cols, cols, 1, fx, fy, None, 0, C.byref(dr), C.byref(dc)))
+        return dr.value, dc.value
+
+    def train_sweep_status(self, img: np.ndarray, mask: Optional[np.ndarray], scales: Sequence[float], strong: float,
+                           num_features_each: Sequence[int]):
+        """train_sweep and the status array [n, 2].  A scale is a number (fx = fy) or a pair (fx, fy)."""
+        a, r, c, ch = _img(img)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (r, c):
+            raise ValueError("mask: a (rows, cols) array")
+        n = len(scales)
+        if len(num_features_each) != n:
+            raise ValueError("one feature count per scale")
+        fxy = [(float(s[0]), float(s[1])) if isinstance(s, (tuple, list)) else (float(s), float(s)) for s in scales]
+        desc = (SbmTrainScale * max(n, 1))()
+        caps, firsts, first = [], [], 0
+        for k, (fx, fy) in enumerate(fxy):
+            dr, dc = self.sweep_dims(r, c, fx, fy)
+            caps.append(self._feature_cap(max(dr, 0), max(dc, 0)))
+            firsts.append(first)
+            desc[k] = SbmTrainScale(fx, fy, int(num_features_each[k]), 0, first, caps[k])
+            first += caps[k]
+        levels = np.zeros((n, self.n_levels), LEVEL_DTYPE)
+        feats = np.zeros(max(first, 1), TRAIN_FEATURE_DTYPE)
+        status = np.zeros((n, 2), np.int32)
+        _check(lib().sbm_train_sweep(self._h, _p(a), r, c, c * ch, ch, _p(m), desc, n, C.c_float(strong), _p(levels), _p(feats), _p(status)))
+        return self._train_results(levels, feats, status, firsts, caps), status
+
+    def train_sweep(self, img: np.ndarray, mask: Optional[np.ndarray], scales: Sequence[float], strong: float, num_features_each: Sequence[int]):
+        """The scale sweep of shapeInfo_producer: Detector::addTemplate(resize(img, s), resize(mask, s) > 0,
+        num_features_each[k]) for every scale s, the source uploaded once and resized on the device: a list of
+        (levels, feats), None where addTemplate returns -1."""
+        return self.train_sweep_status(img, mask, scales, strong, num_features_each)[0]
 
     def select_templates(self, idx: Sequence[int]):
         a = np.ascontiguousarray(idx, np.int32)

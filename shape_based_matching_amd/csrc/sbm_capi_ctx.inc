@@ -266,6 +266,14 @@ struct sbm_ctx {
     int h_nms_counts_frames = 0;
     // batched training (sbm_capi_train.inc): the scratch of a batch, grown by the rule of d_nms_scratch; the host form's images, masks and results
     DevBuf d_train, d_train_in, d_train_mask, d_train_out;
+    // ragged training: the pinned slot the table of records (and a sweep's scale and coefficient tables) is copied from,
+    // the event behind its last copy, and the sweep's scaled images, masks and tables
+    void* h_train_table = nullptr;
+    size_t h_train_table_cap = 0;
+    hipEvent_t ev_train_table = nullptr;
+    bool train_table_busy = false, train_table_recorded = false;
+    hipStream_t train_table_stream = nullptr;
+    DevBuf d_train_sweep;
 
     // hipGraph cache for sbm_match_device (one captured graph per distinct argument tuple)
     struct GraphEntry {

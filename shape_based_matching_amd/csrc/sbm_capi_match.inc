@@ -70,6 +70,8 @@ void sbm_destroy(sbm_ctx* c)
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_res_count) (void)hipHostFree(c->h_res_count);
     if (c->h_nms_counts) (void)hipHostFree(c->h_nms_counts);
+    if (c->h_train_table) (void)hipHostFree(c->h_train_table);
+    if (c->ev_train_table) (void)hipEventDestroy(c->ev_train_table);
     c->drop_graphs();
     for (int l = 0; l < SBM_MAX_LEVELS; ++l)
         if (c->ev_fork[l]) (void)hipEventDestroy(c->ev_fork[l]);

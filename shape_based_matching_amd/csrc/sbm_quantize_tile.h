@@ -647,61 +647,66 @@ __global__ __launch_bounds__(QN) void k_quantize(const uint8_t* __restrict__ img
 // cv::pyrDown: [1 4 6 4 1]^2, (sum + 128) >> 8, REFLECT_101; dst = (rows/2, cols/2).
 // One lane per output pixel (all channels).  Interior pixels of 1- and 3-channel
 // images read each of the 5 source rows as unaligned dwords; the border ring
-// takes the reflect path.
+// takes the reflect path.  pyrdown_pixel is output pixel idx of a destination dc wide: the sample function k_pyrdown
+// and the table form of batched training (k_train_pyrdown, sbm_train_kernels.h) share.
+__device__ __forceinline__ void pyrdown_pixel(const uint8_t* __restrict__ src, int rows, int cols, int ch, int stride,
+                                              uint8_t* __restrict__ dst, int idx, int dc)
+{
+    const int K[5] = {1, 4, 6, 4, 1};
+    const int x = idx % dc, y = idx / dc;
+    const bool interior = x >= 1 && y >= 1 && 2 * x + 2 < cols && 2 * y + 2 < rows &&
+                          (2 * x - 2) * ch + 16 <= stride; // the 16-byte row read stays inside the row
+    if (interior && ch == 3) {
+        int acc[3] = {0, 0, 0};
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const uint8_t* s = src + (size_t)(2 * y + j - 2) * stride + (2 * x - 2) * 3;
+            uint32_t w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) w[q] = ld_u32_any(s + 4 * q);
+            int h[3] = {0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int b = i * 3 + k;
+                    h[k] += K[i] * (int)((w[b >> 2] >> (8 * (b & 3))) & 0xff);
+                }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc[k] += K[j] * h[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dst[(size_t)idx * 3 + k] = (uint8_t)((acc[k] + 128) >> 8);
+    } else if (interior && ch == 1) {
+        int acc = 0;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            const uint8_t* s = src + (size_t)(2 * y + j - 2) * stride + (2 * x - 2);
+            uint32_t w0 = ld_u32_any(s);
+            int h = (int)(w0 & 0xff) + 4 * (int)((w0 >> 8) & 0xff) + 6 * (int)((w0 >> 16) & 0xff) + 4 * (int)(w0 >> 24) + (int)s[4];
+            acc += K[j] * h;
+        }
+        dst[idx] = (uint8_t)((acc + 128) >> 8);
+    } else {
+        for (int k = 0; k < ch; ++k) {
+            int acc = 0;
+            for (int j = 0; j < 5; ++j) {
+                const uint8_t* s = src + (size_t)reflect101(2 * y + j - 2, rows) * stride;
+                int h = 0;
+                for (int i = 0; i < 5; ++i) h += K[i] * s[reflect101(2 * x + i - 2, cols) * ch + k];
+                acc += K[j] * h;
+            }
+            dst[(size_t)idx * ch + k] = (uint8_t)((acc + 128) >> 8);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_pyrdown(const uint8_t* __restrict__ src, int rows, int cols, int ch,
                                                  int stride, uint8_t* __restrict__ dst)
 {
     const int dr = rows / 2, dc = cols / 2;
     const int n = dr * dc;
-    const int K[5] = {1, 4, 6, 4, 1};
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-        const int x = idx % dc, y = idx / dc;
-        const bool interior = x >= 1 && y >= 1 && 2 * x + 2 < cols && 2 * y + 2 < rows &&
-                              (2 * x - 2) * ch + 16 <= stride; // the 16-byte row read stays inside the row
-        if (interior && ch == 3) {
-            int acc[3] = {0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const uint8_t* s = src + (size_t)(2 * y + j - 2) * stride + (2 * x - 2) * 3;
-                uint32_t w[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) w[q] = ld_u32_any(s + 4 * q);
-                int h[3] = {0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const int b = i * 3 + k;
-                        h[k] += K[i] * (int)((w[b >> 2] >> (8 * (b & 3))) & 0xff);
-                    }
-#pragma unroll
-                for (int k = 0; k < 3; ++k) acc[k] += K[j] * h[k];
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) dst[(size_t)idx * 3 + k] = (uint8_t)((acc[k] + 128) >> 8);
-        } else if (interior && ch == 1) {
-            int acc = 0;
-#pragma unroll
-            for (int j = 0; j < 5; ++j) {
-                const uint8_t* s = src + (size_t)(2 * y + j - 2) * stride + (2 * x - 2);
-                uint32_t w0 = ld_u32_any(s);
-                int h = (int)(w0 & 0xff) + 4 * (int)((w0 >> 8) & 0xff) + 6 * (int)((w0 >> 16) & 0xff) + 4 * (int)(w0 >> 24) + (int)s[4];
-                acc += K[j] * h;
-            }
-            dst[idx] = (uint8_t)((acc + 128) >> 8);
-        } else {
-            for (int k = 0; k < ch; ++k) {
-                int acc = 0;
-                for (int j = 0; j < 5; ++j) {
-                    const uint8_t* s = src + (size_t)reflect101(2 * y + j - 2, rows) * stride;
-                    int h = 0;
-                    for (int i = 0; i < 5; ++i) h += K[i] * s[reflect101(2 * x + i - 2, cols) * ch + k];
-                    acc += K[j] * h;
-                }
-                dst[(size_t)idx * ch + k] = (uint8_t)((acc + 128) >> 8);
-            }
-        }
-    }
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) pyrdown_pixel(src, rows, cols, ch, stride, dst, idx, dc);
 }
 
 // cv::resize(INTER_LINEAR) of an 8-bit image with the host-computed coefficient tables (sbm_resize_table.h):
@@ -725,6 +730,17 @@ __global__ __launch_bounds__(256) void k_resize_linear_u8(const uint8_t* __restr
     }
 }
 
+// destination sample idx of resize(mask, INTER_NEAREST) to a plane dcols wide, fx = cols / dcols, fy = rows / drows:
+// the sample function k_resize_mask and the table form of batched training (k_train_resize_mask) share
+__device__ __forceinline__ uint8_t resize_mask_sample(const uint8_t* __restrict__ src, int rows, int cols, double fx, double fy, int idx, int dcols)
+{
+    int x = idx % dcols, y = idx / dcols;
+    int sx = (int)floor(x * fx), sy = (int)floor(y * fy);
+    sx = sx > cols - 1 ? cols - 1 : sx;
+    sy = sy > rows - 1 ? rows - 1 : sy;
+    return src[(size_t)sy * cols + sx];
+}
+
 // frame = blockIdx.y: one mask per frame, src_fs / dst_fs bytes apart (a shared mask is a grid of one frame)
 __global__ __launch_bounds__(256) void k_resize_mask(const uint8_t* __restrict__ src, int rows, int cols,
                                                      uint8_t* __restrict__ dst, int drows, int dcols, int64_t src_fs, int64_t dst_fs)
@@ -734,13 +750,7 @@ __global__ __launch_bounds__(256) void k_resize_mask(const uint8_t* __restrict__
     dst += (int64_t)blockIdx.y * dst_fs;
     const double fx = (double)cols / dcols, fy = (double)rows / drows;
     const int n = drows * dcols;
-    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
-        int x = idx % dcols, y = idx / dcols;
-        int sx = (int)floor(x * fx), sy = (int)floor(y * fy);
-        sx = sx > cols - 1 ? cols - 1 : sx;
-        sy = sy > rows - 1 ? rows - 1 : sy;
-        dst[idx] = src[(size_t)sy * cols + sx];
-    }
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) dst[idx] = resize_mask_sample(src, rows, cols, fx, fy, idx, dcols);
 }
 
 // ... the level-0 masks named by a device array of gridDim.y addresses (the table form of the batched match)

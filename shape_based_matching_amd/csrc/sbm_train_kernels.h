@@ -17,7 +17,9 @@
 #include <stdint.h>
 
 #include "../../include/sbm.h"
+#include "sbm_resize_table.h"
 #include "sbm_train_math.h"
+#include "sbm_train_plan.h"
 
 namespace sbm {
 
@@ -56,24 +58,7 @@ __global__ __launch_bounds__(256) void k_local_maxima5(const float* __restrict__
 // selection of scattered features (k_train_select); per image, cropTemplates and the caller's layout (k_train_crop).
 // The scalar rules are those of sbm_train_math.h.  The level is a grid dimension beside the image; the levels of an
 // image lie behind each other in one per-image "pixel space" (planes) and "candidate space" (lists).
-struct TrainCand {
-    int32_t xy;    // x | y << 16
-    int32_t label; // bit index of the one-hot orientation
-    float score;   // squared magnitude
-    float theta;   // angle_ori
-};
-
-struct TrainLevel {
-    int32_t rows, cols;
-    int32_t cand_cap;    // train_cand_bound(rows, cols)
-    uint32_t nf;         // features asked of this level
-    int64_t pix_off;     // of this level in an image's pixel space
-    int64_t cand_off;    // ... candidate space
-    int64_t sort_off;    // ... key space (a power of two >= cand_cap keys per level)
-    const uint8_t* mask; // level's masks (nullptr: none), mask_fs bytes apart (0: one for all images)
-    int64_t mask_fs;
-};
-
+// TrainCand, TrainLevel and the ragged form's TrainRecord: sbm_train_plan.h, which a CPU compiler takes.
 struct TrainPlan {
     int32_t L, n_images;
     float thr_sq;
@@ -88,13 +73,25 @@ struct TrainPlan {
     uint32_t* kept_xy;    // [n_images][cand_stride]: their positions beyond what LDS holds
     int32_t* counts;      // [n_images][L][2]: candidates; selected features, -1 = the level failed
     TrainLevel lv[8];
+    const TrainRecord* table; // the ragged form: [n_images][L] records of the images' own geometry (lv unused, strides 0)
 };
+
+// The record of (image, level).  RAGGED = false: the call's one geometry, p.lv[l], and offsets img * stride + off.
+// RAGGED = true: the image's own record of the device table -- absolute offsets under strides of 0, its own mask and
+// feature count; indexed by blockIdx only, so the record is wave-uniform and its fields are scalar loads.
+template <bool RAGGED>
+__device__ __forceinline__ const TrainLevel& train_level(const TrainPlan& p, int img, int l)
+{
+    if constexpr (RAGGED) return p.table[(int64_t)img * p.L + l];
+    else return p.lv[l];
+}
 
 enum { TRAIN_KEPT_LDS = 4096 };
 
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_train_maxima(const TrainPlan p)
 {
-    const TrainLevel& v = p.lv[blockIdx.y];
+    const TrainLevel& v = train_level<RAGGED>(p, blockIdx.z, blockIdx.y);
     const int64_t base = (int64_t)blockIdx.z * p.pix_stride + v.pix_off;
     const float* __restrict__ mag = p.mag + base;
     uint8_t* __restrict__ flags = p.flags + base;
@@ -123,10 +120,12 @@ __global__ __launch_bounds__(256) void k_train_maxima(const TrainPlan p)
 // One wave per (image, level) walks the rows.  Lane i owns the columns [i * K, (i + 1) * K): it composes the column
 // maps of its segment, the wave composes the segments' maps by a prefix scan, and the lane replays its segment from its
 // incoming state.  Kept pixels are marked in the flag plane, where the next two rows find them.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void k_train_resolve(const TrainPlan p)
 {
     const int l = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
-    const TrainLevel& v = p.lv[l];
+    const TrainLevel& v = train_level<RAGGED>(p, img, l);
+    const int cand_cap = v.cand_cap; // read before the first store: the record stays in scalar registers
     const int64_t base = (int64_t)img * p.pix_stride + v.pix_off;
     uint8_t* flags = p.flags + base;
     const uint8_t* __restrict__ quant = p.quant + base;
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(64) void k_train_resolve(const TrainPlan p)
             for (int c = c0; c < c1; ++c) {
                 const uint32_t a = quant[(size_t)r * cols + c];
                 if ((f0[c] & 2) && a) {
-                    if (pos < v.cand_cap) {
+                    if (pos < cand_cap) {
                         TrainCand k;
                         k.xy = c | (r << 16);
                         k.label = __ffs(a) - 1;
@@ -190,18 +189,20 @@ __global__ __launch_bounds__(64) void k_train_resolve(const TrainPlan p)
         }
         __syncthreads(); // the marks of this row, before the next row reads them
     }
-    if (lane == 0) p.counts[((int64_t)img * p.L + l) * 2] = min(total, v.cand_cap);
+    if (lane == 0) p.counts[((int64_t)img * p.L + l) * 2] = min(total, cand_cap);
 }
 
 // bitonic sort of the level's keys (train_key), descending, in global scratch by one workgroup
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_train_sort(const TrainPlan p)
 {
     const int l = blockIdx.x, img = blockIdx.y, tid = threadIdx.x;
-    const TrainLevel& v = p.lv[l];
+    const TrainLevel& v = train_level<RAGGED>(p, img, l);
+    const uint32_t nf = v.nf;
     const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + v.cand_off;
     uint64_t* keys = p.keys + (int64_t)img * p.sort_stride + v.sort_off;
     const int n = p.counts[((int64_t)img * p.L + l) * 2];
-    if (train_level_fails((size_t)n, v.nf)) return;
+    if (train_level_fails((size_t)n, nf)) return;
     int P = 1;
     while (P < n) P <<= 1;
     for (int i = tid; i < P; i += 256) keys[i] = i < n ? train_key(__float_as_uint(cand[i].score), (uint32_t)i) : 0ull;
@@ -225,22 +226,25 @@ __global__ __launch_bounds__(256) void k_train_sort(const TrainPlan p)
 // tests its candidate against the features kept before the chunk, then the chunk's survivors are taken in order, each
 // one striking out the later survivors too close to it.  That is the sequential sweep: a candidate is taken iff it is far
 // from every feature taken before it.
+template <bool RAGGED>
 __global__ __launch_bounds__(64) void k_train_select(const TrainPlan p)
 {
     __shared__ uint32_t s_kept[TRAIN_KEPT_LDS];
     const int l = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
-    const TrainLevel& v = p.lv[l];
+    const TrainLevel& v = train_level<RAGGED>(p, img, l);
+    const int cand_cap = v.cand_cap; // read before the first store: the record stays in scalar registers
+    const uint32_t nf = v.nf;
     const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + v.cand_off;
     const uint64_t* __restrict__ keys = p.keys + (int64_t)img * p.sort_stride + v.sort_off;
     int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + v.cand_off;
     uint32_t* kept_g = p.kept_xy + (int64_t)img * p.cand_stride + v.cand_off;
     int32_t* counts = p.counts + ((int64_t)img * p.L + l) * 2;
     const int n = counts[0];
-    if (train_level_fails((size_t)n, v.nf)) {
+    if (train_level_fails((size_t)n, nf)) {
         if (lane == 0) counts[1] = -1;
         return;
     }
-    TrainSelect st = train_select_begin((size_t)n, v.nf);
+    TrainSelect st = train_select_begin((size_t)n, nf);
     int cnt = 0;
     for (;;) {
         const float d2 = st.distance * st.distance;
@@ -263,7 +267,7 @@ __global__ __launch_bounds__(64) void k_train_select(const TrainPlan p)
                 const int k = __ffsll((unsigned long long)m) - 1;
                 const int kxy = __shfl(xy, k);
                 if (lane == k) {
-                    if (cnt < v.cand_cap) {
+                    if (cnt < cand_cap) {
                         if (cnt < TRAIN_KEPT_LDS) s_kept[cnt] = (uint32_t)xy;
                         else kept_g[cnt] = (uint32_t)xy;
                         sel[cnt] = idx;
@@ -276,15 +280,17 @@ __global__ __launch_bounds__(64) void k_train_select(const TrainPlan p)
             }
             __syncthreads(); // the chunk's features, before the next chunk reads them
         }
-        const int next = train_select_next(st, (size_t)cnt, v.nf);
+        const int next = train_select_next(st, (size_t)cnt, nf);
         if (next == TRAIN_PASS_STOP) break;
         if (next == TRAIN_PASS_RESTART) cnt = 0;
     }
-    if (lane == 0) counts[1] = min(cnt, v.cand_cap);
+    if (lane == 0) counts[1] = min(cnt, cand_cap);
 }
 
 // cropTemplates and the caller's layout, one workgroup per image.  status: {0, features} | {1, first failing level} |
-// {2, features needed} when they exceed feat_cap; the level records of an image that is not ok are zeroed.
+// {2, features needed} when they exceed feat_cap; the level records of an image that is not ok are zeroed.  The
+// ragged form takes the image's feature block from its record (feat_first, feat_cap) instead of img * feat_cap.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_template_level* __restrict__ levels, sbm_train_feature* __restrict__ feats,
                                                     int64_t feat_cap, int32_t* __restrict__ status)
 {
@@ -292,7 +298,13 @@ __global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_templ
     const int img = blockIdx.x, tid = threadIdx.x;
     const int32_t* counts = p.counts + (int64_t)img * p.L * 2;
     levels += (int64_t)img * p.L;
-    feats += (int64_t)img * feat_cap;
+    if constexpr (RAGGED) {
+        const TrainRecord& rec = p.table[(int64_t)img * p.L];
+        feats += rec.feat_first;
+        feat_cap = rec.feat_cap;
+    } else {
+        feats += (int64_t)img * feat_cap;
+    }
     int failed = -1;
     int64_t total = 0;
     for (int l = p.L - 1; l >= 0; --l) {
@@ -319,8 +331,8 @@ __global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_templ
     __syncthreads();
     int mn_x = INT32_MAX, mn_y = INT32_MAX, mx_x = INT32_MIN, mx_y = INT32_MIN;
     for (int l = 0; l < p.L; ++l) {
-        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
-        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + train_level<RAGGED>(p, img, l).cand_off;
+        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + train_level<RAGGED>(p, img, l).cand_off;
         for (int k = tid; k < counts[2 * l + 1]; k += 256) {
             const int xy = cand[sel[k]].xy;
             const int x = (xy & 0xffff) << l, y = (xy >> 16) << l;
@@ -335,8 +347,8 @@ __global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_templ
     const int min_x = train_crop_even(s_mm[0]), min_y = train_crop_even(s_mm[1]);
     int64_t off = 0;
     for (int l = 0; l < p.L; ++l) {
-        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
-        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + p.lv[l].cand_off;
+        const TrainCand* __restrict__ cand = p.cand + (int64_t)img * p.cand_stride + train_level<RAGGED>(p, img, l).cand_off;
+        const int32_t* __restrict__ sel = p.sel + (int64_t)img * p.cand_stride + train_level<RAGGED>(p, img, l).cand_off;
         const int nl = counts[2 * l + 1];
         const TrainBox b = train_crop_level(min_x, min_y, s_mm[2], s_mm[3], l);
         if (tid == 0) {
@@ -364,6 +376,69 @@ __global__ __launch_bounds__(256) void k_train_crop(const TrainPlan p, sbm_templ
     if (tid == 0) {
         status[2 * img] = 0;
         status[2 * img + 1] = (int32_t)total;
+    }
+}
+
+// ---- the level steps of the ragged form: one launch per level, image = blockIdx.y --------------------------------------
+// Level l's image from level l-1's (cv::pyrDown, line2Dup.cpp:431-433) and level l's mask from level l-1's (nearest
+// neighbour, :439), both geometries and all four addresses from the image's records; the samples are k_pyrdown's and
+// k_resize_mask's.  The grid's x is sized for the batch's largest level l; a level that is not built has no pixel.
+__global__ __launch_bounds__(256) void k_train_pyrdown(const TrainRecord* __restrict__ table, int L, int l, int ch)
+{
+    const TrainRecord& s = table[(int64_t)blockIdx.y * L + l - 1];
+    const TrainRecord& d = table[(int64_t)blockIdx.y * L + l];
+    const uint8_t* __restrict__ src = s.img;
+    uint8_t* __restrict__ dst = const_cast<uint8_t*>(d.img);
+    const int rows = s.rows, cols = s.cols, stride = s.stride, dc = d.cols;
+    const int n = d.rows * dc;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) pyrdown_pixel(src, rows, cols, ch, stride, dst, idx, dc);
+}
+
+__global__ __launch_bounds__(256) void k_train_resize_mask(const TrainRecord* __restrict__ table, int L, int l)
+{
+    const TrainRecord& s = table[(int64_t)blockIdx.y * L + l - 1];
+    const TrainRecord& d = table[(int64_t)blockIdx.y * L + l];
+    const uint8_t* __restrict__ src = s.mask;
+    uint8_t* __restrict__ dst = const_cast<uint8_t*>(d.mask);
+    const int rows = s.rows, cols = s.cols, drows = d.rows, dcols = d.cols;
+    const int n = dst ? drows * dcols : 0; // an image without a mask, or a level that is not built
+    if (n == 0) return;
+    const double fx = (double)cols / dcols, fy = (double)rows / drows;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) dst[idx] = resize_mask_sample(src, rows, cols, fx, fy, idx, dcols);
+}
+
+// ---- the scale sweep (sbm_train_sweep_device): every scaled image and mask of one source in one launch -----------------
+// cv::resize(src, dst, Size(), fx, fy) of shapeInfo_producer::transform (line2Dup.h:379-405), scale = blockIdx.y.  The
+// coefficient tables of sbm_resize_table.h, one pair per scale, lie behind each other in one index and one coefficient
+// array; one thread makes one destination sample (resize_linear_sample).  The samples behind the image's are the mask's,
+// resized with the same tables as a one-channel plane and thresholded as mask_of does (`> 0`, :455-457).
+__global__ __launch_bounds__(256) void k_resize_sweep_u8(const uint8_t* __restrict__ src, int rows, int cols, int ch, int stride,
+                                                         const uint8_t* __restrict__ mask, const TrainSweepScale* __restrict__ scales,
+                                                         const int32_t* __restrict__ tab_idx, const int16_t* __restrict__ tab_coef)
+{
+    const TrainSweepScale& sc = scales[blockIdx.y];
+    const int drows = sc.rows, dcols = sc.cols;
+    const int32_t* __restrict__ xi = tab_idx + sc.x_off;
+    const int32_t* __restrict__ yi = tab_idx + sc.y_off;
+    const int16_t* __restrict__ xa = tab_coef + 2 * sc.x_off;
+    const int16_t* __restrict__ ya = tab_coef + 2 * sc.y_off;
+    uint8_t* __restrict__ dst = sc.img;
+    uint8_t* __restrict__ dmask = sc.mask;
+    const int64_t npx = (int64_t)drows * dcols, n_img = npx * ch, n = n_img + (mask ? npx : 0);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const bool m = i >= n_img;
+        const int64_t j = m ? i - n_img : i;
+        const int c = m ? 1 : ch, k = (int)(j % c);
+        const int64_t px = j / c;
+        const int x = (int)(px % dcols), y = (int)(px / dcols);
+        const int x0 = xi[x], x1 = x0 + 1 < cols ? x0 + 1 : cols - 1;
+        const int y0 = yi[y], y1 = y0 + 1 < rows ? y0 + 1 : rows - 1;
+        const int64_t st = m ? cols : stride;
+        const uint8_t* r0 = (m ? mask : src) + y0 * st;
+        const uint8_t* r1 = (m ? mask : src) + y1 * st;
+        const uint8_t v = resize_linear_sample(r0[x0 * c + k], r0[x1 * c + k], r1[x0 * c + k], r1[x1 * c + k], xa[2 * x], xa[2 * x + 1], ya[2 * y], ya[2 * y + 1]);
+        if (m) dmask[j] = v > 0 ? 255 : 0;
+        else dst[j] = v;
     }
 }
 

@@ -7,6 +7,7 @@
 //   demo convert <in_fmt> <class_id> <out_fmt>
 //       readClasses + writeClasses (no GPU needed)
 //   demo scale_train <image.ppm> <num_features> <scale_lo> <scale_hi> <scale_step> <templ_fmt> <class_id> <info.yaml>
+//                    [<angle_lo> <angle_hi> <angle_step>]
 //       test.cpp:scale_test("train") (test.cpp:170-203): shapeInfo_producer::src_of / mask_of (cv::resize) + addTemplate
 //   demo nms <templ_fmt> <class_id> <image> <threshold> <num_features> [pad]
 //       test.cpp:noise_test (test.cpp:455-491): match, boxes from templ[0].width/height, NMSBoxes(boxes, scores, 0, 0.5f)
@@ -23,7 +24,9 @@
 //       one mask per frame: matchBatch / matchAsync+wait / matchBatchNMS / setDevices + matchBatch with a vector of masks
 //       against per-frame match(frame_f, threshold, ids, mask_f); the frames of `batch`, masks that contain the object, cut it,
 //       are absent (empty Mat) or are a non-continuous view, in turn
-//   demo trainbatch <num_features> <loop_fmt> <batch_fmt> <class_id> <image> <mask.pgm|-> [<image> <mask.pgm|-> ...]
+//   demo scale_train_batch ...  the arguments and the output of scale_train, through shapeInfo_producer::addTemplates:
+//       every scale of the sweep resized and trained on the device in one call (Detector::addTemplatesScaled)
+//   demo trainbatch <num_features> <loop_fmt> <batch_fmt> <class_id> [counts=a,b,...] <image> <mask.pgm|-> [<image> <mask.pgm|-> ...]
 //       the same list of sources trained twice: a loop of addTemplate into one detector, one addTemplates into another;
 //       prints both lists of ids and writes both detectors with writeClasses (`-` = no mask)
 //   demo instance <config.yaml> <image> <threshold>
@@ -154,7 +157,7 @@ int main(int argc, char** argv)
             printf("trained %d templates\n", detector.numTemplates());
             return 0;
         }
-        if (mode == "scale_train") {
+        if (mode == "scale_train" || mode == "scale_train_batch") {
             if (argc < 10) return usage();
             Mat img = imread(argv[2], IMREAD_UNCHANGED);
             if (img.empty()) { fprintf(stderr, "cannot read %s\n", argv[2]); return 1; }
@@ -164,12 +167,24 @@ int main(int argc, char** argv)
             shape_based_matching::shapeInfo_producer shapes(img);
             shapes.scale_range = {(float)atof(argv[4]), (float)atof(argv[5])};
             shapes.scale_step = (float)atof(argv[6]);
+            if (argc > 12) { // the angles of every scale: 90, 180 and 270 rotate (line2Dup.h:379-405), any other angle only resizes
+                shapes.angle_range = {(float)atof(argv[10]), (float)atof(argv[11])};
+                shapes.angle_step = (float)atof(argv[12]);
+            }
             shapes.produce_infos();
             std::vector<shape_based_matching::shapeInfo_producer::Info> infos_have_templ;
-            for (auto& info : shapes.infos) {
-                // the call of test.cpp:185-186, argument for argument (in this fork the 4th parameter is `sscale`)
-                int templ_id = detector.addTemplate(shapes.src_of(info), class_id, shapes.mask_of(info), int(num_feature * info.scale));
-                if (templ_id != -1) infos_have_templ.push_back(info);
+            if (mode == "scale_train_batch") { // the same loop as one call: every scale resized and trained on the device
+                std::vector<float> sscales;
+                for (auto& info : shapes.infos) sscales.push_back((float)int(num_feature * info.scale));
+                const std::vector<int> ids = shapes.addTemplates(detector, class_id, shapes.infos, sscales);
+                for (size_t k = 0; k < ids.size(); ++k)
+                    if (ids[k] != -1) infos_have_templ.push_back(shapes.infos[k]);
+            } else {
+                for (auto& info : shapes.infos) {
+                    // the call of test.cpp:185-186, argument for argument (in this fork the 4th parameter is `sscale`)
+                    int templ_id = detector.addTemplate(shapes.src_of(info), class_id, shapes.mask_of(info), int(num_feature * info.scale));
+                    if (templ_id != -1) infos_have_templ.push_back(info);
+                }
             }
             detector.writeClasses(fmt);
             shape_based_matching::shapeInfo_producer::save_infos(infos_have_templ, argv[9]);
@@ -461,11 +476,22 @@ int main(int argc, char** argv)
             return n_bad ? 2 : 0;
         }
         if (mode == "trainbatch") {
-            if (argc < 8 || (argc - 6) % 2) return usage();
+            // an optional "counts=a,b,..." before the sources: one feature count per source, the last argument of addTemplate
+            std::vector<int> counts;
+            int a0 = 6;
+            if (argc > 6 && !strncmp(argv[6], "counts=", 7)) {
+                for (const char* p = argv[6] + 7; *p;) {
+                    counts.push_back(atoi(p));
+                    while (*p && *p != ',') ++p;
+                    if (*p == ',') ++p;
+                }
+                a0 = 7;
+            }
+            if (argc < a0 + 2 || (argc - a0) % 2) return usage();
             const int num_features = atoi(argv[2]);
             const std::string loop_fmt = argv[3], batch_fmt = argv[4], class_id = argv[5];
             std::vector<Mat> sources, masks;
-            for (int a = 6; a + 1 < argc; a += 2) {
+            for (int a = a0; a + 1 < argc; a += 2) {
                 Mat img = imread(argv[a], IMREAD_UNCHANGED);
                 if (img.empty()) { fprintf(stderr, "cannot read %s\n", argv[a]); return 1; }
                 Mat mask;
@@ -478,8 +504,12 @@ int main(int argc, char** argv)
             }
             line2Dup::Detector loop(num_features, {4, 8}), batch(num_features, {4, 8});
             std::vector<int> loop_ids;
-            for (size_t k = 0; k < sources.size(); ++k) loop_ids.push_back(loop.addTemplate(sources[k], class_id, masks[k]));
-            const std::vector<int> batch_ids = batch.addTemplates(sources, class_id, masks);
+            if (!counts.empty() && counts.size() != sources.size()) return usage();
+            for (size_t k = 0; k < sources.size(); ++k)
+                loop_ids.push_back(counts.empty() ? loop.addTemplate(sources[k], class_id, masks[k])
+                                                  : loop.addTemplate(sources[k], class_id, masks[k], -1.0f, -1.0f, 0, "none", counts[k]));
+            const std::vector<int> batch_ids = counts.empty() ? batch.addTemplates(sources, class_id, masks)
+                                                              : batch.addTemplates(sources, class_id, masks, {}, {}, 0, "none", 0, counts);
             std::cout.flush();
             printf("loop");
             for (int id : loop_ids) printf(" %d", id);

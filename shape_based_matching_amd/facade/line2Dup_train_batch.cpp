@@ -1,9 +1,12 @@
 // line2Dup_train_batch.cpp — Detector::addTemplates: addTemplate for a list of sources over the engine's batched training
-// entry point (sbm_train_batch).  A translation unit of its own: it is the only part of the facade that needs that entry point.
+// entry points (sbm_train_batch for one geometry, sbm_train_ragged for any list), Detector::addTemplatesScaled and
+// shapeInfo_producer::addTemplates over the device scale sweep (sbm_train_sweep).  A translation unit of its own: it is the
+// only part of the facade that needs those entry points.
 #include "../../include/line2Dup.h"
 #include "../../include/sbm.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <iostream>
 #include <map>
@@ -46,9 +49,59 @@ sbm_ctx* train_ctx(const std::vector<int>& T, int levels, float weak_threshold)
     return ctx;
 }
 
+// no two accepted maxima within a 3 x 3 cell: the most features an image can have, level by level; and the engine's
+// scratch for it: the image and its float / byte planes per pixel, the lists per candidate
+void train_bounds(int rows, int cols, int ch, int levels, int64_t* feat_cap, int64_t* scratch)
+{
+    int64_t cap = 0, pixels = 0;
+    for (int l = 0; l < levels; ++l) {
+        cap += (int64_t)(((rows >> l) + 2) / 3) * (((cols >> l) + 2) / 3);
+        pixels += (int64_t)(rows >> l) * (cols >> l);
+    }
+    *feat_cap = cap;
+    *scratch = pixels * (ch + 11) + cap * 64 + 4096;
+}
+
+const int64_t kTrainBudget = (int64_t)256 << 20;
+
 } // namespace
 
 namespace line2Dup {
+
+// One trained image as a TemplatePyramid; false (and addTemplate's message) where the engine reports too few candidates.
+static bool train_result(int pyramid_levels, const sbm_template_level* levels, const sbm_train_feature* block, const int32_t* status, float sscale,
+                         float orientation, int tagFieldID, const std::string& fiducial_src, std::vector<Template>& tp)
+{
+    if (status[0] == 1) {
+        std::cout << "extractTemplate: too few candidate features at pyramid level " << status[1] << ", giving up on this template" << std::endl;
+        return false;
+    }
+    CV_Assert(status[0] == 0);
+    tp.assign((size_t)pyramid_levels, Template());
+    for (int l = 0; l < pyramid_levels; ++l) {
+        const sbm_template_level& lv = levels[l];
+        Template& t = tp[(size_t)l];
+        t.width = lv.width;
+        t.height = lv.height;
+        t.tl_x = lv.tl_x;
+        t.tl_y = lv.tl_y;
+        t.pyramid_level = lv.pyramid_level;
+        t.sscale = sscale;
+        t.orientation = orientation;
+        t.tagFieldID = tagFieldID;
+        t.fiducial_src = fiducial_src;
+        t.features.resize((size_t)lv.n_features);
+        const sbm_train_feature* f = block + (size_t)lv.feature_offset;
+        for (int j = 0; j < lv.n_features; ++j) {
+            Feature& o = t.features[(size_t)j];
+            o.x = f[j].x;
+            o.y = f[j].y;
+            o.label = f[j].label;
+            o.theta = f[j].theta;
+        }
+    }
+    return true;
+}
 
 // addTemplate for a list of sources (an extension: the reference's callers train in bulk, test_jabil.cpp:46-118).  The
 // sources are grouped by geometry and every group goes through sbm_train_batch -- gradients, maxima, tie resolution,
@@ -56,9 +109,10 @@ namespace line2Dup {
 // Element k is what the k-th call of a loop of addTemplate returns, and the detector afterwards is the loop's.
 std::vector<int> Detector::addTemplates(const std::vector<Mat>& sources, const std::string& class_id, const std::vector<Mat>& object_masks,
                                         const std::vector<float>& sscales, const std::vector<float>& orientations, int tagFieldID,
-                                        std::string fiducial_src, int num_features)
+                                        std::string fiducial_src, int num_features, const std::vector<int>& num_features_each)
 {
     const size_t n = sources.size();
+    CV_Assert(num_features_each.empty() || num_features_each.size() == n);
     CV_Assert(object_masks.empty() || object_masks.size() == n);
     CV_Assert(sscales.empty() || sscales.size() == n);
     CV_Assert(orientations.empty() || orientations.size() == n);
@@ -79,16 +133,56 @@ std::vector<int> Detector::addTemplates(const std::vector<Mat>& sources, const s
     std::vector<char> ok(n, 0);
     std::lock_guard<std::mutex> lock(g_train_mu);
     sbm_ctx* ctx = train_ctx(T_at_level, pyramid_levels, modality->weak_threshold);
-    for (const auto& g : groups) {
-        const int rows = std::get<0>(g.first), cols = std::get<1>(g.first), ch = CV_MAT_CN(std::get<2>(g.first));
-        // no two accepted maxima within a 3 x 3 cell: the most features an image can have, level by level
-        int64_t feat_cap = 0, pixels = 0;
-        for (int l = 0; l < pyramid_levels; ++l) {
-            feat_cap += (int64_t)(((rows >> l) + 2) / 3) * (((cols >> l) + 2) / 3);
-            pixels += (int64_t)(rows >> l) * (cols >> l);
+    const bool ragged = groups.size() > 1 || !num_features_each.empty();
+    // Any list: every source with its own size and count through sbm_train_ragged, in input order, in sub-batches whose
+    // scratch, summed per image, stays under the budget.
+    for (size_t first = 0; ragged && first < n;) {
+        std::vector<Mat> keep; // continuous copies of views
+        std::vector<sbm_train_image> imgs;
+        int64_t feats_total = 0, scratch_total = 0;
+        const int ch = sources[first].channels();
+        size_t m = 0;
+        for (; first + m < n && m < 4096; ++m) {
+            const size_t k = first + m;
+            Mat src = sources[k];
+            if (src.channels() != ch) break; // a call's images share the number of channels
+            int64_t cap, scratch;
+            train_bounds(src.rows, src.cols, ch, pyramid_levels, &cap, &scratch);
+            if (m > 0 && scratch_total + scratch > kTrainBudget) break;
+            if (!src.isContinuous()) keep.push_back(src = src.clone());
+            sbm_train_image im;
+            memset(&im, 0, sizeof im);
+            im.img = src.data;
+            if (!object_masks.empty() && !object_masks[k].empty()) {
+                Mat mk = object_masks[k];
+                if (!mk.isContinuous()) keep.push_back(mk = mk.clone());
+                im.mask = mk.data;
+            }
+            im.rows = src.rows, im.cols = src.cols, im.stride = src.cols * ch;
+            const int each = num_features_each.empty() ? 0 : num_features_each[k];
+            im.num_features = each > 0 ? each : nf; // addTemplate: a count <= 0 means the detector's
+            im.feat_first = feats_total, im.feat_cap = cap;
+            imgs.push_back(im);
+            feats_total += cap;
+            scratch_total += scratch;
         }
-        // the engine's scratch per image: the image and its float / byte planes per pixel, the lists per candidate
-        const int64_t per_image = pixels * (ch + 11) + feat_cap * 64 + 4096, budget = (int64_t)256 << 20;
+        std::vector<sbm_template_level> levels(m * (size_t)pyramid_levels);
+        std::vector<sbm_train_feature> feats((size_t)std::max<int64_t>(feats_total, 1));
+        std::vector<int32_t> status(m * 2);
+        check(sbm_train_ragged(ctx, imgs.data(), (int)m, ch, modality->strong_threshold, levels.data(), feats.data(), status.data()), "sbm_train_ragged");
+        for (size_t i = 0; i < m; ++i) {
+            const size_t k = first + i;
+            ok[k] = train_result(pyramid_levels, levels.data() + i * (size_t)pyramid_levels, feats.data() + imgs[i].feat_first, status.data() + 2 * i,
+                                 sscales.empty() ? -1.0f : sscales[k], orientations.empty() ? -1.0f : orientations[k], tagFieldID, fiducial_src, made[k]);
+        }
+        first += m;
+    }
+    for (const auto& g : groups) {
+        if (ragged) break;
+        const int rows = std::get<0>(g.first), cols = std::get<1>(g.first), ch = CV_MAT_CN(std::get<2>(g.first));
+        int64_t feat_cap, per_image;
+        train_bounds(rows, cols, ch, pyramid_levels, &feat_cap, &per_image);
+        const int64_t budget = kTrainBudget;
         const size_t sub = (size_t)std::max<int64_t>(1, std::min<int64_t>(budget / per_image, 4096));
         for (size_t first = 0; first < g.second.size(); first += sub) {
             const size_t m = std::min(sub, g.second.size() - first);
@@ -115,37 +209,8 @@ std::vector<int> Detector::addTemplates(const std::vector<Mat>& sources, const s
                   "sbm_train_batch");
             for (size_t i = 0; i < m; ++i) {
                 const size_t k = g.second[first + i];
-                if (status[2 * i] == 1) {
-                    std::cout << "extractTemplate: too few candidate features at pyramid level " << status[2 * i + 1] << ", giving up on this template"
-                              << std::endl;
-                    continue;
-                }
-                CV_Assert(status[2 * i] == 0);
-                TemplatePyramid tp((size_t)pyramid_levels);
-                for (int l = 0; l < pyramid_levels; ++l) {
-                    const sbm_template_level& lv = levels[i * (size_t)pyramid_levels + (size_t)l];
-                    Template& t = tp[(size_t)l];
-                    t.width = lv.width;
-                    t.height = lv.height;
-                    t.tl_x = lv.tl_x;
-                    t.tl_y = lv.tl_y;
-                    t.pyramid_level = lv.pyramid_level;
-                    t.sscale = sscales.empty() ? -1.0f : sscales[k];
-                    t.orientation = orientations.empty() ? -1.0f : orientations[k];
-                    t.tagFieldID = tagFieldID;
-                    t.fiducial_src = fiducial_src;
-                    t.features.resize((size_t)lv.n_features);
-                    const sbm_train_feature* f = feats.data() + i * (size_t)feat_cap + (size_t)lv.feature_offset;
-                    for (int j = 0; j < lv.n_features; ++j) {
-                        Feature& o = t.features[(size_t)j];
-                        o.x = f[j].x;
-                        o.y = f[j].y;
-                        o.label = f[j].label;
-                        o.theta = f[j].theta;
-                    }
-                }
-                made[k] = tp;
-                ok[k] = 1;
+                ok[k] = train_result(pyramid_levels, levels.data() + i * (size_t)pyramid_levels, feats.data() + i * (size_t)feat_cap, status.data() + 2 * i,
+                                     sscales.empty() ? -1.0f : sscales[k], orientations.empty() ? -1.0f : orientations[k], tagFieldID, fiducial_src, made[k]);
             }
         }
     }
@@ -160,4 +225,118 @@ std::vector<int> Detector::addTemplates(const std::vector<Mat>& sources, const s
     return ids;
 }
 
+// The scale sweep of one source over sbm_train_sweep: uploaded once, resized on the device, trained as one ragged batch
+// (in sub-batches under the scratch budget).  The loop of addTemplate(resize(source, s), class_id, resize(mask, s) > 0, ...).
+std::vector<int> Detector::addTemplatesScaled(const Mat& source, const std::string& class_id, const Mat& object_mask, const std::vector<float>& scales,
+                                              const std::vector<float>& sscales, const std::vector<float>& orientations, int tagFieldID,
+                                              std::string fiducial_src, const std::vector<int>& num_features_each)
+{
+    const size_t n = scales.size();
+    CV_Assert(sscales.empty() || sscales.size() == n);
+    CV_Assert(orientations.empty() || orientations.size() == n);
+    CV_Assert(num_features_each.empty() || num_features_each.size() == n);
+    CV_Assert(pyramid_levels >= 1 && pyramid_levels <= SBM_MAX_LEVELS && (int)T_at_level.size() >= pyramid_levels);
+    CV_Assert(!source.empty() && source.depth() == CV_8U && (source.channels() == 1 || source.channels() == 3));
+    CV_Assert(object_mask.empty() || (object_mask.type() == CV_8UC1 && object_mask.size() == source.size()));
+    std::vector<TemplatePyramid>& template_pyramids = class_templates[class_id];
+    std::vector<int> ids(n, -1);
+    if (n == 0) return ids;
+    const Mat src = source.isContinuous() ? source : source.clone();
+    const Mat mask = object_mask.empty() || object_mask.isContinuous() ? object_mask : object_mask.clone();
+    const int ch = src.channels();
+    std::lock_guard<std::mutex> lock(g_train_mu);
+    sbm_ctx* ctx = train_ctx(T_at_level, pyramid_levels, modality->weak_threshold);
+    bool any = false;
+    for (size_t first = 0; first < n;) {
+        std::vector<sbm_train_scale> sc;
+        int64_t feats_total = 0, scratch_total = 0;
+        size_t m = 0;
+        for (; first + m < n && m < 4096; ++m) {
+            const size_t k = first + m;
+            int32_t dr = 0, dc = 0;
+            check(sbm_resize_linear(ctx, src.data, src.rows, src.cols, src.cols * ch, ch, scales[k], scales[k], nullptr, 0, &dr, &dc), "sbm_resize_linear");
+            int64_t cap, scratch;
+            train_bounds(std::max(dr, 0), std::max(dc, 0), ch, pyramid_levels, &cap, &scratch);
+            scratch += (int64_t)std::max(dr, 0) * std::max(dc, 0) * (ch + 1); // the scaled image and mask
+            if (m > 0 && scratch_total + scratch > kTrainBudget) break;
+            sbm_train_scale s;
+            memset(&s, 0, sizeof s);
+            s.fx = s.fy = scales[k];
+            const int each = num_features_each.empty() ? 0 : num_features_each[k];
+            s.num_features = each > 0 ? each : (int)modality->num_features;
+            s.feat_first = feats_total, s.feat_cap = cap;
+            sc.push_back(s);
+            feats_total += cap;
+            scratch_total += scratch;
+        }
+        std::vector<sbm_template_level> levels(m * (size_t)pyramid_levels);
+        std::vector<sbm_train_feature> feats((size_t)std::max<int64_t>(feats_total, 1));
+        std::vector<int32_t> status(m * 2);
+        check(sbm_train_sweep(ctx, src.data, src.rows, src.cols, src.cols * ch, ch, mask.empty() ? nullptr : mask.data, sc.data(), (int)m,
+                              modality->strong_threshold, levels.data(), feats.data(), status.data()),
+              "sbm_train_sweep");
+        for (size_t i = 0; i < m; ++i) {
+            const size_t k = first + i;
+            TemplatePyramid tp;
+            if (!train_result(pyramid_levels, levels.data() + i * (size_t)pyramid_levels, feats.data() + sc[i].feat_first, status.data() + 2 * i,
+                              sscales.empty() ? -1.0f : sscales[k], orientations.empty() ? -1.0f : orientations[k], tagFieldID, fiducial_src, tp))
+                continue;
+            ids[k] = static_cast<int>(template_pyramids.size());
+            template_pyramids.push_back(tp);
+            any = true;
+        }
+        first += m;
+    }
+    if (any) templatesChanged();
+    return ids;
+}
+
 } // namespace line2Dup
+
+namespace shape_based_matching {
+
+// 0: no rotation (transform only resizes), 1: 90, 2: 180, 3: 270 -- the branches of transform (line2Dup.h:379-405)
+static int rotation_class(float angle)
+{
+    if (std::abs(angle - 90.0) < ANGLE_TOLERANCE) return 1;
+    if (std::abs(angle - 180.0) < ANGLE_TOLERANCE) return 2;
+    if (std::abs(angle - 270.0) < ANGLE_TOLERANCE) return 3;
+    return 0;
+}
+
+static Mat rotated(const Mat& m, int rc)
+{
+    if (rc == 0 || m.empty()) return m;
+    Mat dst;
+    cv::rotate(m, dst, rc == 1 ? cv::ROTATE_90_CLOCKWISE : rc == 2 ? cv::ROTATE_180 : cv::ROTATE_90_COUNTERCLOCKWISE);
+    return dst;
+}
+
+std::vector<int> shapeInfo_producer::addTemplates(line2Dup::Detector& detector, const std::string& class_id, const std::vector<Info>& infos_,
+                                                  const std::vector<float>& sscales, const std::vector<float>& orientations, int tagFieldID,
+                                                  std::string fiducial_src, const std::vector<int>& num_features_each)
+{
+    const size_t n = infos_.size();
+    CV_Assert(sscales.empty() || sscales.size() == n);
+    CV_Assert(orientations.empty() || orientations.size() == n);
+    CV_Assert(num_features_each.empty() || num_features_each.size() == n);
+    std::vector<int> ids;
+    for (size_t first = 0; first < n;) {
+        const int rc = rotation_class(infos_[first].angle);
+        size_t m = 1;
+        while (first + m < n && rotation_class(infos_[first + m].angle) == rc) ++m;
+        std::vector<float> scales(m);
+        for (size_t i = 0; i < m; ++i) scales[i] = infos_[first + i].scale;
+        auto part = [&](const std::vector<float>& v) { return v.empty() ? v : std::vector<float>(v.begin() + (long)first, v.begin() + (long)(first + m)); };
+        const std::vector<int> each = num_features_each.empty()
+                                          ? num_features_each
+                                          : std::vector<int>(num_features_each.begin() + (long)first, num_features_each.begin() + (long)(first + m));
+        const std::vector<int> got = detector.addTemplatesScaled(rotated(src, rc), class_id, rotated(mask, rc), scales, part(sscales), part(orientations),
+                                                                 tagFieldID, fiducial_src, each);
+        ids.insert(ids.end(), got.begin(), got.end());
+        first += m;
+    }
+    return ids;
+}
+
+} // namespace shape_based_matching
