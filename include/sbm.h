@@ -468,6 +468,10 @@ int sbm_get_source_form(sbm_ctx* ctx, int32_t* out);
  * replayed from a captured graph; with sbm_match's overflow retry, the retry's launch.  launched: the work items of the grid.
  * Waits for the device when a count is still outstanding.  A parity-test accessor. */
 int sbm_get_sparse_items(sbm_ctx* ctx, int32_t out[3]);
+/* {list_mode, slots_per_frame} of the last call's sparse level-0 gradient launch: list_mode 1 when it ran, by slots_per_frame
+ * waves per frame, from the per-frame lists of working items that the mark launch leaves (0, 0: a wave per item, each testing
+ * itself, or no sparse launch at all). */
+int sbm_get_sparse_list(sbm_ctx* ctx, int32_t out[2]);
 int sbm_level_dims(sbm_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols);
 
 /* Second half of match(): Detector::matchClass over the selected templates

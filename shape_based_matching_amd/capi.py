@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "sbm_get_source_form",
     "sbm_get_refine_form",
     "sbm_get_sparse_items",
+    "sbm_get_sparse_list",
     "sbm_match_batch_device_ptrs",
     "sbm_match_batch_device_planes",
 ]
@@ -222,6 +223,7 @@ def lib() -> C.CDLL:
     L.sbm_get_coarse_form.argtypes = [vp, vp]
     L.sbm_get_source_form.argtypes = [vp, vp]
     L.sbm_get_sparse_items.argtypes = [vp, vp]
+    L.sbm_get_sparse_list.argtypes = [vp, vp]
     L.sbm_get_refine_form.argtypes = [vp, i32, vp]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
@@ -839,6 +841,13 @@ class Context:
         2 by the record of need rectangles; working items are counted under profiling only (-1 otherwise)"""
         out = np.zeros(3, np.int32)
         _check(lib().sbm_get_sparse_items(self._h, _p(out)))
+        return tuple(int(v) for v in out)
+
+    def sparse_list(self) -> Tuple[int, int]:
+        """(list_mode, slots_per_frame) of the last call's sparse level-0 gradient launch: list_mode 1 when it ran from the lists
+        of working items, with slots_per_frame waves per frame; (0, 0) otherwise"""
+        out = np.zeros(2, np.int32)
+        _check(lib().sbm_get_sparse_list(self._h, _p(out)))
         return tuple(int(v) for v in out)
 
     def match_templates(self, threshold: float) -> np.ndarray:

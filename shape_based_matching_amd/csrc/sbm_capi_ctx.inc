@@ -104,6 +104,10 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //                             (sbm_quantize_stream.h, QS_SOURCE / QS_SPARSE); SBM_SPARSE_STRIPS=0 implies it
 //   SBM_SPARSE_RECTS=0        the sparse level-0 gradient pass takes its work items from the tile flags on the fixed strip grid instead of
 //                             from the record of need rectangles (sbm_refine_tiles.h: refine_need, gradient_rect_item_needed): the A/B knob
+//   SBM_SPARSE_LIST=0         the sparse level-0 gradient launch as one wave per item of its grid, every wave testing its own item, instead
+//                             of SBM_SPARSE_SLOTS waves per frame that run from the lists of working items k_mark_refine_tiles leaves
+//                             (sbm_refine_tiles.h: gradient_rect_list); nothing is allocated for the lists.  SBM_SPARSE_RECTS=0 implies it
+//   SBM_SPARSE_SLOTS=n        waves per frame of that launch (default and at most: the items per frame)
 //   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
 //   SBM_SOURCE_LINES=0        the source pass always in its strided form (QS_SOURCE), never as k_source_lines (sbm_source_lines.h), which
 //                             otherwise runs wherever the caller's layout admits it (source_lines_ok): the A/B knob of the two forms
@@ -113,6 +117,8 @@ struct Tuning {
     int bits_wide = -1, bits_dw = 0, bits_block = -1, match_bands = 0, local_bits = -1;
     bool sparse_strips = true, sparse_gradient = true, source_lines = true, sparse_rects = true;
     int src_hs = 0;
+    bool sparse_list = true;
+    int sparse_slots = 0;
 };
 static const Tuning& tuning()
 {
@@ -144,6 +150,8 @@ static const Tuning& tuning()
         k.sparse_strips = num("SBM_SPARSE_STRIPS", 1) != 0;
         k.sparse_gradient = k.sparse_strips && num("SBM_SPARSE_GRADIENT", 1) != 0;
         k.sparse_rects = k.sparse_gradient && num("SBM_SPARSE_RECTS", 1) != 0;
+        k.sparse_list = k.sparse_rects && num("SBM_SPARSE_LIST", 1) != 0;
+        k.sparse_slots = std::max(0, num("SBM_SPARSE_SLOTS", 0));
         k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
         k.source_lines = num("SBM_SOURCE_LINES", 1) != 0;
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
@@ -208,6 +216,12 @@ struct sbm_ctx {
     // hull {xmin, xmax} of the map columns some candidate's refinement depends on, emptied where the tile flags are cleared, widened
     // by k_mark_refine_tiles, read by the sparse gradient launch.  Device data: a replayed graph follows each call's candidates.
     DevBuf d_rects;
+    // ... and of those items the working ones, listed per frame by k_mark_refine_tiles for the launch to run from (SBM_SPARSE_LIST):
+    // items_cap entries per frame, room for every item of the grid at any rows per item.  sparse_list: {the last call's sparse
+    // launch ran from lists, its waves per frame}
+    DevBuf d_items;
+    int64_t items_cap = 0;
+    int32_t sparse_list[2] = {0, 0};
     DevBuf d_sparse_items;          // one int32: the working items of the last profiled sparse gradient launch
     int32_t sparse_items[3] = {0, 0, 0}; // {selection: 0 none, 1 tiles, 2 need rectangles; working items (-1: not counted); items launched}
     bool sparse_items_pending = false;   // the count is still on the device
@@ -467,6 +481,18 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             c->d_rects.release();
             if (c->d_src0.p && tuning().sparse_rects)
                 if (int e = c->d_rects.ensure(B * (size_t)refine_band_count(r) * 2 * sizeof(int32_t), true)) return e; // zeroed: every band empty
+            c->d_items.release();
+            c->items_cap = 0;
+            if (c->d_rects.p && tuning().sparse_list) {
+                const int64_t cap = refine_list_capacity(r, cc, QS_USEFUL);
+                if (cap < (int64_t)1 << 24) { // (else: no lists, every wave tests its own item)
+                    if (int e = c->d_items.ensure(B * (size_t)refine_list_stride(cap) * sizeof(int32_t))) return e;
+                    // no list anywhere until a reset says so too
+                    HIP_TRY(hipMemset(c->d_items.p, 0xff, B * (size_t)refine_list_stride(cap) * sizeof(int32_t)));
+                    HIP_TRY(hipStreamSynchronize(nullptr)); // (as in DevBuf::ensure: before anything is enqueued behind it)
+                    c->items_cap = cap;
+                }
+            }
             if (c->d_src0.p)
                 if (int e = c->d_sparse_items.ensure(256, true)) return e;
         }
@@ -506,6 +532,8 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
         c->d_tiles.release();
         c->d_src0.release();
         c->d_rects.release();
+        c->d_items.release();
+        c->items_cap = 0;
         c->map0_whole = true; // the caller sets the whole map
     }
     c->forms[l].forget();
@@ -617,6 +645,10 @@ struct QSForm {
     const int32_t* need_rects = nullptr; // QS_SPARSE: the record of need rectangles, n_bands pairs per frame; null: the tile-driven items
     int n_bands = 0;
     int32_t* item_count = nullptr;       // QS_SPARSE: where the working items are counted (profiling), or null
+    // QS_SPARSE by slots (sparse_list_plan): the frames' lists of working items and the grid they were made for; slots 0: a wave per item
+    const int32_t* item_list = nullptr;
+    int64_t list_stride = 0;
+    int list_cap = 0, slots = 0, list_hs = 0, list_n_full = 0;
 };
 
 // rows per work item of the source pass: its items run hs + 3 row iterations, in whole groups of 6
@@ -741,16 +773,27 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
                 a.need_rects = form->need_rects;
                 a.n_bands = form->n_bands;
             }
+            if (form->slots > 0) {
+                // (the lists were made for one grid: the one this launch runs)
+                if (form->list_hs != hs || form->list_n_full != (a.pack_lanes ? a.n_strips - 1 : a.n_strips) || !form->need_rects)
+                    return fail(SBM_ERR_STATE, "the lists of working items were made for another grid than the sparse gradient launch runs");
+                a.item_list = form->item_list;
+                a.list_stride = form->list_stride;
+                a.list_cap = form->list_cap;
+                a.slots = form->slots;
+            }
             c->sparse_items[0] = form->need_rects ? 2 : 1;
             c->sparse_items[1] = -1;
-            c->sparse_items[2] = quantize_stream_items(a);
+            c->sparse_items[2] = a.slots > 0 ? frames * a.slots + quantize_slots_packed(a) : quantize_stream_items(a);
             c->sparse_items_pending = form->item_count != nullptr;
+            c->sparse_list[0] = a.slots > 0, c->sparse_list[1] = a.slots;
         }
-        const dim3 g((unsigned)((quantize_stream_items(a) + 3) / 4));
+        const dim3 g((unsigned)(a.slots > 0 ? quantize_slots_groups(a) : (quantize_stream_items(a) + 3) / 4));
         // (one timing name for all three forms: the launches of the gradient stage)
 #define SBM_QS(CH_)                                                                                                         \
         do {                                                                                                                \
             if (stage == QS_SOURCE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SOURCE>), g, dim3(256), 0, s, a); \
+            else if (stage == QS_SPARSE && a.slots > 0) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream_slots<CH_>), g, dim3(256), 0, s, a); \
             else if (stage == QS_SPARSE) SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_SPARSE>), g, dim3(256), 0, s, a); \
             else SBM_LAUNCH(c, "k_quantize", (k_quantize_stream<CH_, QS_WHOLE>), g, dim3(256), 0, s, a);                     \
         } while (0)
@@ -1163,6 +1206,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
     c->source_form = 0;
     c->sparse_items[0] = 0, c->sparse_items[1] = -1, c->sparse_items[2] = 0;
     c->sparse_items_pending = false;
+    c->sparse_list[0] = c->sparse_list[1] = 0;
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
@@ -1232,6 +1276,8 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
                 a.n_tiles = refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]);
                 a.clear_rects = c->d_rects.as<int32_t>(); // (null without the record)
                 a.n_bands = refine_band_count(c->rows[0]);
+                a.clear_items = c->d_items.as<int32_t>(); // (null without the lists)
+                a.items_stride = refine_list_stride(c->items_cap);
             }
         }
         SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
@@ -1422,7 +1468,8 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
     if (!c->counters_fresh)
         hipLaunchKernelGGL(k_reset, dim3(1), dim3(64), 0, s, counters, d_count, clear_tiles ? c->d_tiles.as<uint8_t>() : (uint8_t*)nullptr,
                            clear_tiles ? refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]) : 0,
-                           clear_tiles ? c->d_rects.as<int32_t>() : (int32_t*)nullptr, clear_tiles ? refine_band_count(c->rows[0]) : 0);
+                           clear_tiles ? c->d_rects.as<int32_t>() : (int32_t*)nullptr, clear_tiles ? refine_band_count(c->rows[0]) : 0,
+                           clear_tiles ? c->d_items.as<int32_t>() : (int32_t*)nullptr);
     c->counters_fresh = false;
     const int n_active = (int)c->h_active.size();
     if (n_active > 0) {
@@ -1618,13 +1665,46 @@ bool sparse_refine(const sbm_ctx* c)
 // Between the coarse pass and the refinement of a sparse call: flag the tiles of level 0 that the candidates' patches lie in,
 // then build the bit strips of the flagged tiles from the orientation map (the bit-strip share of k_build_lm_rows; a
 // workgroup whose flag is 0 returns at once).  The unflagged tiles keep whatever an earlier call left: nothing reads them.
+// The grid of the sparse gradient launch of a call of `frames` frames and how many waves per frame run it from the lists of
+// working items: SBM_SPARSE_SLOTS or the default, at most the items of a frame.  slots 0: no lists, a wave per item.
+struct SparseListPlan {
+    int slots = 0, hs = 0, n_full = 0, n_rblocks = 0;
+};
+constexpr int SPARSE_SLOTS_DEFAULT = INT_MAX; // the items per frame (profiles/sparse_list.txt, section 5)
+SparseListPlan sparse_list_plan(const sbm_ctx* c, int frames, int ch)
+{
+    SparseListPlan p;
+    if (!tuning().sparse_list || !c->d_items.p || !c->d_rects.p || !c->d_src0.p) return p;
+    const FrameSource src = retained_frames(c, ch, frames);
+    const int rows = c->rows[0], cols = c->cols[0];
+    const int hs = quantize_stream_rows(c, rows, cols, src, MaskSource{}, false);
+    if (!hs) return p;
+    const int n_strips = (cols + QS_USEFUL - 1) / QS_USEFUL;
+    const int n_full = qs_pack_lanes(rows, cols, src, MaskSource{}) ? n_strips - 1 : n_strips, n_rblocks = (rows + hs - 1) / hs;
+    const int64_t per_frame = (int64_t)n_full * n_rblocks;
+    if (per_frame < 1 || per_frame > c->items_cap) return p;
+    p.hs = hs, p.n_full = n_full, p.n_rblocks = n_rblocks;
+    p.slots = (int)std::min<int64_t>(per_frame, tuning().sparse_slots > 0 ? tuning().sparse_slots : SPARSE_SLOTS_DEFAULT);
+    return p;
+}
+
 int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
 {
     const int T = c->cfg.T[0], W = c->cols[0] / T, H = c->rows[0] / T, n_tiles = refine_tile_count(W, H), n_bands = refine_band_count(c->rows[0]);
     // the record of need rectangles only where this call's gradient launch reads it (the flags alone serve the strip builder)
     int32_t* const rects = !c->map0_whole && tuning().sparse_rects ? c->d_rects.as<int32_t>() : nullptr;
+    // ... and the lists of working items where that launch runs from them
+    const SparseListPlan lp = rects ? sparse_list_plan(c, frames, c->src0_ch) : SparseListPlan{};
+    MarkList ml;
+    memset(&ml, 0, sizeof ml);
+    if (lp.slots > 0) {
+        ml.items = c->d_items.as<int32_t>();
+        ml.stride = refine_list_stride(c->items_cap);
+        ml.capacity = (int32_t)c->items_cap;
+        ml.n_full = lp.n_full, ml.n_rblocks = lp.n_rblocks, ml.hs = lp.hs, ml.useful = QS_USEFUL;
+    }
     SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
-               (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles, rects, n_bands);
+               (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles, rects, n_bands, ml);
     HIP_TRY(hipGetLastError());
     if (!c->map0_whole) {
         // the call ran the source pass only (BuildPlan::sparse_gradient): level 0's gradient stage now, from the retained
@@ -1632,6 +1712,12 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
         QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
         form.need_rects = rects;
         form.n_bands = n_bands;
+        if (lp.slots > 0) {
+            form.item_list = ml.items;
+            form.list_stride = ml.stride;
+            form.list_cap = ml.capacity;
+            form.slots = lp.slots, form.list_hs = lp.hs, form.list_n_full = lp.n_full;
+        }
         if (c->profiling && c->d_sparse_items.p) { // (no capture while profiling: graph_wanted)
             HIP_TRY(hipMemsetAsync(c->d_sparse_items.p, 0, sizeof(int32_t), s));
             form.item_count = c->d_sparse_items.as<int32_t>();
@@ -1806,8 +1892,10 @@ int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
 // sparse_grad: the captured call made level 0's map sparsely (its graph key says so)
 // any_batch: the captured call was a batch through k_build_lm_any (PlanInputs::any_batch)
 // sparse_rects: ... with its work items taken from the record of need rectangles
-void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch, bool sparse_rects = false)
+// sparse_slots: ... by that many waves per frame from the lists of working items (0: a wave per item)
+void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch, bool sparse_rects = false, int sparse_slots = 0)
 {
+    c->sparse_list[0] = sparse_slots > 0, c->sparse_list[1] = sparse_slots;
     c->sparse_items[0] = sparse_grad ? (sparse_rects ? 2 : 1) : 0;
     c->sparse_items[1] = -1; // a replay counts nothing
     c->sparse_items_pending = false;
@@ -1869,6 +1957,7 @@ GraphKey graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
     key.sparse_grad = kind > 0 && plans_sparse_gradient(c, m.src, m.mask, nullptr, false);
     key.sparse_rects = key.sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
+    key.sparse_slots = key.sparse_rects ? sparse_list_plan(c, m.src.frames, m.src.ch).slots : 0;
     return key;
 }
 
@@ -1903,7 +1992,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is the one-launch
             // builder's where that takes every level, else the batched any-stride builder's; the template loop builds nothing
             if (kind >= 0) {
-                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects);
+                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects, key.sparse_slots);
                 c->last_frames = m.src.frames;
             }
             return 0;

@@ -887,6 +887,13 @@ int sbm_get_sparse_items(sbm_ctx* c, int32_t out[3])
     return 0;
 }
 
+int sbm_get_sparse_list(sbm_ctx* c, int32_t out[2])
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    memcpy(out, c->sparse_list, sizeof c->sparse_list);
+    return 0;
+}
+
 int sbm_level_dims(sbm_ctx* c, int32_t level, int32_t* rows, int32_t* cols)
 {
     if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");

@@ -6,6 +6,7 @@
 #pragma once
 #include "sbm_common.h"
 #include "sbm_bitplane_math.h"
+#include "sbm_refine_tiles.h" // RT_LIST_NONE
 
 namespace sbm {
 
@@ -431,6 +432,10 @@ struct LmArgs {
     // where the flags are cleared
     int32_t* clear_rects;
     int32_t n_bands;
+    // clear_items (may be null): the frames' lists of working items (sbm_refine_tiles.h), items_stride int32 apart: none there
+    // until k_mark_refine_tiles writes one
+    int32_t* clear_items;
+    int64_t items_stride;
 };
 
 __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
@@ -445,6 +450,7 @@ __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
             for (int i = threadIdx.x; i < a.n_tiles; i += 256) a.clear_tiles[frame * a.n_tiles + i] = 0;
         if (a.clear_rects)
             for (int i = threadIdx.x; i < 2 * a.n_bands; i += 256) a.clear_rects[frame * a.n_bands * 2 + i] = (i & 1) ? 0 : 0x7fffffff;
+        if (a.clear_items && threadIdx.x == 0) a.clear_items[frame * a.items_stride] = RT_LIST_NONE;
     }
     // the level whose block range holds this block (the host orders the ranges heaviest blocks first)
     int l = 0, lb = -1;

@@ -115,6 +115,14 @@ struct QSArgs {
     const int32_t* need_rects;
     int32_t n_bands;
     int32_t* item_count; // QS_SPARSE under profiling (else null): every work item that works adds 1 (a packed wave: 1 per frame that needs it)
+    // QS_SPARSE from the lists of working items (k_quantize_stream_slots; sbm_refine_tiles.h: gradient_rect_list).  slots > 0: the
+    // strips that get a wave per frame are run by `slots` waves per frame -- wave j of frame f takes entries j, j + slots, ... of the
+    // frame's list, x_first from the entry and no test of its own; where the frame's count is RT_LIST_NONE, items j, j + slots, ...
+    // of the fixed grid, each through its own test as in the launch without lists.  The packed last-strip waves follow unchanged.
+    const int32_t* item_list; // frame 0's list, list_stride int32 from one frame's to the next
+    int64_t list_stride;
+    int32_t list_cap;         // entries a frame's list has room for: a larger count is cut to it
+    int32_t slots;
 };
 
 // Which part of the row loop a kernel instance holds (compile time):
@@ -354,8 +362,9 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
 
 // One work item: strip `strip`, output rows [rb*hs, min(rb*hs+hs, rows)), frame `frame`.
 // nseg == 0: the whole wave is strip `strip` of frame `frame`; nseg > 0: packed last strip of frames frame .. frame+nseg-1
+// x_listed >= 0 (QS_SPARSE): the item comes from a list of working items -- it works, and its strip begins at that column
 template <int CH, int STAGE = QS_WHOLE, bool PTRS = false, bool PLANES = false>
-__device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0)
+__device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0, int x_listed = -1)
 {
     using namespace wv;
     static_assert(!PLANES || (PTRS && CH == 3 && STAGE != QS_SPARSE), "the plane form is a table form of three channels");
@@ -366,7 +375,14 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
         return;
     }
     int x_first = strip * QS_USEFUL; // first useful column of the item's strip
-    if (STAGE == QS_SPARSE && a.tile_flags) { // wave-uniform: a few byte loads
+    if (STAGE == QS_SPARSE && x_listed >= 0) {
+        x_first = x_listed;
+#ifndef SBM_WAVE_EMU
+        if (a.item_count && (threadIdx.x & 63) == 0) atomicAdd(a.item_count, 1);
+#else
+        if (a.item_count) *a.item_count += 1;
+#endif
+    } else if (STAGE == QS_SPARSE && a.tile_flags) { // wave-uniform: a few byte loads
         int working = 0;
         // `working`: the frames of the wave (one, but for a packed last strip) whose item works
         for (int g = 0; g < (nseg ? nseg : 1); ++g) {
@@ -866,6 +882,59 @@ __device__ __forceinline__ void quantize_stream_item(const QSArgs& a, int item)
     }
 }
 
+// QS_SPARSE by slots (QSArgs::slots > 0), wave q of workgroup `group`: first the list waves, slots per frame, then the packed
+// last-strip waves as workgroups of their own, in their order of quantize_stream_item.
+// A workgroup of list waves is waves 4b .. 4b + 3 of one frame, the frames taking turns: block b of every frame before block
+// b + 1 of any.  So the working waves -- the lowest j of every frame -- fill whole workgroups, which measured best (a launch that
+// dealt them one or two to a workgroup over twice as many workgroups gained nothing over testing every item, profiles/sparse_list.txt),
+// and without a list, at slots = items per frame, a workgroup holds neighbouring strips of one row block as in quantize_stream_item.
+__host__ __device__ inline int quantize_slots_list_groups(const QSArgs& a) { return a.frames * ((a.slots + 3) / 4); }
+__host__ __device__ inline int quantize_slots_packed(const QSArgs& a) { return a.pack_lanes ? a.n_rblocks * a.pack_groups : 0; }
+__host__ __device__ inline int quantize_slots_groups(const QSArgs& a) { return quantize_slots_list_groups(a) + (quantize_slots_packed(a) + 3) / 4; }
+
+// v, as a value that depends on the trip e: not one to compute once in front of a loop and keep in a register across it
+__device__ __forceinline__ int qs_per_item(int v, int e)
+{
+#ifndef SBM_WAVE_EMU
+    asm("" : "+s"(v) : "s"(e));
+#endif
+    return v;
+}
+
+template <int CH>
+__device__ __forceinline__ void quantize_stream_slot_wave(const QSArgs& a, int group, int q)
+{
+    const int n_full = a.pack_lanes ? a.n_strips - 1 : a.n_strips, per_frame = n_full * a.n_rblocks;
+    const int lg = quantize_slots_list_groups(a);
+    if (group >= lg) { // a packed last-strip wave: its own test, as ever
+        const int j = (group - lg) * 4 + q;
+        if (j >= quantize_slots_packed(a)) return;
+        const int rb = j / a.pack_groups, grp = j - rb * a.pack_groups, per = 64 / a.pack_lanes, f0 = grp * per;
+        const int nseg = a.frames - f0 < per ? a.frames - f0 : per;
+        quantize_stream_wave<CH, QS_SPARSE>(a, a.n_strips - 1, rb, f0, nseg);
+        return;
+    }
+    const int b = group / a.frames, frame = group - b * a.frames, j = 4 * b + q;
+    if (j >= a.slots) return;
+    const int count = a.item_list ? a.item_list[(int64_t)frame * a.list_stride] : (int)RT_LIST_NONE;
+    const bool listed = count != RT_LIST_NONE;
+    const int n = listed ? (count < a.list_cap ? count : a.list_cap) : per_frame; // (a negative count: no trip)
+    // The row loop inside leaves no scalar register to spare: across an item the loop keeps e, n, the frame and `listed`, and
+    // takes everything else from the arguments again (qs_per_item: as far as the compiler knows, a new value per trip).
+    for (int e = j; e < n; e += a.slots) {
+        const int fr = qs_per_item(frame, e), nf = qs_per_item(a.n_strips, e) - (a.pack_lanes ? 1 : 0);
+        int k, rb, x = -1;
+        if (listed) {
+            const int32_t* ent = a.item_list + (int64_t)fr * a.list_stride + RT_LIST_HEAD + (int64_t)RT_LIST_ENTRY * e;
+            k = ent[0], rb = ent[1], x = ent[2];
+            if (k < 0 || k >= nf || rb < 0 || rb >= a.n_rblocks || x < 0 || x >= a.cols) continue; // no item of this launch
+        } else {
+            rb = e / nf, k = e - rb * nf;
+        }
+        quantize_stream_wave<CH, QS_SPARSE>(a, k, rb, fr, 0, x);
+    }
+}
+
 // segment lanes of a packed last strip for this geometry, 0 = the last strip gets a wave per frame like the others
 // mask_fs: bytes between the frames' masks (0: none, or one shared mask)
 __host__ __device__ inline int quantize_stream_pack_lanes(int rows, int cols, int ch, int frames, int64_t mask_fs = 0)
@@ -889,6 +958,14 @@ __global__ __launch_bounds__(256) void k_quantize_stream(const QSArgs a)
     // (row counters, stage gating, row base addresses) lives in SGPRs and branches are scalar
     const int item = (int)blockIdx.x * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     quantize_stream_item<CH, STAGE>(a, item);
+}
+
+// QS_SPARSE by slots: grid = quantize_slots_groups(a).  The waves per SIMD are those of k_quantize_stream, said aloud: around the
+// item loop the allocator otherwise takes four registers more, one too many for the sixth gray wave.
+template <int CH>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 : 6))) void k_quantize_stream_slots(const QSArgs a)
+{
+    quantize_stream_slot_wave<CH>(a, (int)blockIdx.x, (int)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
 // the table form: a.img (and a.mask, if not null) is a device array of a.frames addresses; launched with a.pack_lanes == 0

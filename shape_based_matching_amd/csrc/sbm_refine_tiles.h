@@ -5,7 +5,8 @@
 // Further down: which pixels of the level's orientation map a tile's strip builder loads, and which work items of the streaming
 // gradient kernel write them (gradient_item_needed: the sparse gradient pass of sbm_quantize_stream.h, tests/test_sparse_gradient.py).
 // Last: the finer record of what the refinement reads -- per band of pixel rows the hull of the needed map columns (refine_need) --
-// and the work items of the sparse gradient pass placed by it (gradient_rect_item_needed, tests/test_sparse_rects.py).
+// and the work items of the sparse gradient pass placed by it (gradient_rect_item_needed, tests/test_sparse_rects.py), listed per
+// frame for the launch to run from (gradient_rect_list, tests/test_sparse_list.py).
 //
 // A TILE is one workgroup of build_lm_strip4_allty<true> (sbm_lm_kernels.h): RT_STRIPS strips of 16 cells x RT_ROWS grid
 // rows, for all 128 (sub-plane, orientation) planes; tile (tx, ty) of a W x H grid has index ty * ((W + 31) / 32) + tx, the
@@ -226,6 +227,32 @@ SBM_RT_HD bool gradient_rect_item_needed(const int32_t* iv, const uint8_t* flags
     *x0 = s0;
     if (s0 >= xb) return false;
     return refine_rect_needed(flags, s0, r0, s1, r1, rows, cols, T, W, H);
+}
+
+// ---- the list of working items: what k_mark_refine_tiles leaves for the sparse gradient launch beside flags and hulls ----
+// The rect-driven items (k, rb) of one frame that get a wave of their own -- k < n_full strips (a packed last strip is not among
+// them), rb < n_rblocks -- tested once, where the hulls and the flags are made, instead of by every wave of the launch.
+// One frame's list: RT_LIST_HEAD int32, the first of them the count, then RT_LIST_ENTRY int32 per working item {k, rb, x_first, 0},
+// in any order.  Count RT_LIST_NONE: there is no list, every wave tests its own items.
+constexpr int RT_LIST_HEAD = 4, RT_LIST_ENTRY = 4; // (entries are 16 bytes, 16-byte aligned: one load each)
+constexpr int RT_LIST_NONE = -1;
+// entries a frame's list has room for whatever the rows per item (even, >= 2) of the call that fills it
+SBM_RT_HD int64_t refine_list_capacity(int rows, int cols, int useful) { return (int64_t)((cols + useful - 1) / useful) * ((rows + 1) / 2); }
+SBM_RT_HD int64_t refine_list_stride(int64_t capacity) { return RT_LIST_HEAD + RT_LIST_ENTRY * capacity; }
+
+// Items first, first + step, ... of the n_full * n_rblocks of a frame (item i: strip i % n_full of row block i / n_full):
+// append(k, rb, x_first) for each that works.  The kernel runs it with a thread per `first` and an atomic counter behind
+// `append`, tests/test_sparse_list.py with first = 0, step = 1.
+template <class F>
+SBM_RT_HD void gradient_rect_list(const int32_t* iv, const uint8_t* flags, int n_full, int n_rblocks, int hs, int useful, int rows, int cols,
+                                  int T, int W, int H, int first, int step, F append)
+{
+    const int n_items = n_full * n_rblocks;
+    for (int i = first; i < n_items; i += step) {
+        const int rb = i / n_full, k = i - rb * n_full;
+        int x0;
+        if (gradient_rect_item_needed(iv, flags, k, rb, hs, useful, rows, cols, T, W, H, &x0)) append(k, rb, x0);
+    }
 }
 
 } // namespace sbm

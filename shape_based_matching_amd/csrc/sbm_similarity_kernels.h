@@ -400,8 +400,9 @@ __global__ __launch_bounds__(256) void k_copy_bytes(const uint8_t* __restrict__ 
 // zero the per-call counters (one launch instead of two memsets)
 // tiles (may be null): frame 0's refinement-tile flags (sbm_refine_tiles.h), cleared for k_mark_refine_tiles
 // rects (may be null): ... and its record of need rectangles, n_bands {xmin, xmax} pairs, emptied
+// items (may be null): ... and its list of working items, which there is none of until k_mark_refine_tiles writes one
 __global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ out_count, uint8_t* __restrict__ tiles, int n_tiles,
-                        int32_t* __restrict__ rects, int n_bands)
+                        int32_t* __restrict__ rects, int n_bands, int32_t* __restrict__ items)
 {
     top_wave_priority();
     for (int i = threadIdx.x; i < CTR_STRIDE; i += blockDim.x) counters[i] = 0; // layout: sbm_common.h CTR_*
@@ -410,6 +411,7 @@ __global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ ou
         for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) tiles[i] = 0;
     if (rects)
         for (int i = threadIdx.x; i < 2 * n_bands; i += blockDim.x) rects[i] = (i & 1) ? 0 : 0x7fffffff;
+    if (items && threadIdx.x == 0) items[0] = RT_LIST_NONE;
 }
 
 // Between the coarse pass and the refinement of a level held as sparse bit strips (LM_BIT_STRIPS_SPARSE): a thread per coarse
@@ -418,10 +420,20 @@ __global__ void k_reset(int32_t* __restrict__ counters, int32_t* __restrict__ ou
 // fext[t * L + l] = largest feature x | largest feature y << 16 of template t's level l: the box the footprint is taken of
 // is the features' own (the reference's templates have features AT x = width, cropTemplates line2Dup.cpp:148, and an
 // uploaded template may declare any box), while the clamps use the declared one as the refinement pass does.
+// ml: the list of working items that the sparse gradient launch behind it runs from (sbm_refine_tiles.h: gradient_rect_list), made
+// for a frame that ONE workgroup holds -- at most 256 candidates, hulls and flags in LDS -- once the hulls are out: a thread per item
+// of the launch's grid tests it on the LDS copies and the working ones are compacted behind the frame's count.  Any other frame
+// keeps the count that the reset left (RT_LIST_NONE: the waves test their own items), and so does a frame without candidates.
+struct MarkList {
+    int32_t* items;          // frame 0's list (null: none is made), `stride` int32 from one frame's to the next
+    int64_t stride;
+    int32_t capacity;        // entries a frame's list has room for
+    int32_t n_full, n_rblocks, hs, useful; // the launch's grid: strips with a wave per frame, row blocks, rows per item, columns per strip
+};
 __global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restrict__ cands, const int32_t* __restrict__ counters, int cand_cap,
                                                            int rows, int cols, int T, int W, int H, const uint32_t* __restrict__ fext, int L,
                                                            int l, uint8_t* __restrict__ tiles, int n_tiles, int32_t* __restrict__ rects,
-                                                           int n_bands)
+                                                           int n_bands, const MarkList ml)
 {
     raise_wave_priority();
     const size_t frame = blockIdx.y;
@@ -440,13 +452,20 @@ __global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restric
     __shared__ int4 s_rect[512];
     __shared__ int s_n;
     const bool in_lds = n_bands <= MARK_LDS_BANDS;
+    // the list of working items: the frame's flags stay in LDS as well, and its hulls, flushed, lie pairwise where the rectangles were
+    constexpr int MARK_LDS_TILES = 2048;
+    __shared__ uint8_t s_flags[MARK_LDS_TILES];
+    __shared__ int s_items;
+    const bool listed = ml.items && iv && in_lds && n <= 256 && n_tiles <= MARK_LDS_TILES; // (the workgroup's: n is the frame's)
     // (the trip count is the workgroup's: every thread reaches the barriers below)
     for (int base = blockIdx.x * 256; base < n; base += gridDim.x * 256) {
         const int i = base + (int)threadIdx.x;
         RefineNeed need{{{0, -1, 0, 0}, {0, -1, 0, 0}}};
         if (iv && in_lds) {
             for (int b = threadIdx.x; b < n_bands; b += 256) s_lo[b] = 0x7fffffff, s_hi[b] = 0;
-            if (threadIdx.x == 0) s_n = 0;
+            if (threadIdx.x == 0) s_n = 0, s_items = 0;
+            if (listed)
+                for (int t = threadIdx.x; t < n_tiles; t += 256) s_flags[t] = 0;
             __syncthreads();
         }
         if (i < n) {
@@ -456,7 +475,10 @@ __global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restric
                 const uint32_t ext = fext[(size_t)c.t * L + l];
                 const int fw = (int)(ext & 0xffff) + 1, fh = (int)(ext >> 16) + 1;
                 refine_tiles_for_each(refine_tiles(o, fw, fh, rows, cols, T, W, H), W, H, [&](int tile) {
-                    if (tile >= 0 && tile < n_tiles) flags[tile] = 1;
+                    if (tile >= 0 && tile < n_tiles) {
+                        flags[tile] = 1;
+                        if (listed) s_flags[tile] = 1;
+                    }
                 });
                 if (iv) need = refine_need(o, fw, fh, rows, cols, T, W, H);
             }
@@ -495,12 +517,23 @@ __global__ __launch_bounds__(256) void k_mark_refine_tiles(const Cand* __restric
                 const int lo = s_lo[b], hi = s_hi[b];
                 if (alone) {
                     *(int2*)&iv[2 * b] = int2{lo, hi};
+                    if (listed) ((int2*)s_rect)[b] = int2{lo, hi}; // (the rectangles are spent)
                 } else if (lo < hi) {
                     atomicMin(&iv[2 * b], lo);
                     atomicMax(&iv[2 * b + 1], hi);
                 }
             }
             __syncthreads(); // (before the next round empties the arrays)
+            if (listed) { // (the only round of the frame's only workgroup)
+                int32_t* const list = ml.items + frame * ml.stride;
+                gradient_rect_list((const int32_t*)s_rect, s_flags, ml.n_full, ml.n_rblocks, ml.hs, ml.useful, rows, cols, T, W, H, (int)threadIdx.x, 256,
+                                   [&](int k, int rb, int x0) {
+                                       const int slot = atomicAdd(&s_items, 1);
+                                       if (slot < ml.capacity) *(int4*)&list[RT_LIST_HEAD + RT_LIST_ENTRY * (int64_t)slot] = int4{k, rb, x0, 0};
+                                   });
+                __syncthreads();
+                if (threadIdx.x == 0) list[0] = s_items < ml.capacity ? s_items : ml.capacity;
+            }
         }
     }
 }
