@@ -472,6 +472,25 @@ int sbm_get_sparse_items(sbm_ctx* ctx, int32_t out[3]);
  * waves per frame, from the per-frame lists of working items that the mark launch leaves (0, 0: a wave per item, each testing
  * itself, or no sparse launch at all). */
 int sbm_get_sparse_list(sbm_ctx* ctx, int32_t out[2]);
+/* How the linear memories of `level` were last built: out = {current, form, builder, split, allty, packed}.  current: the
+ * buffers that hold the level's current contents, as a bit set: 1 the 8 response planes, 2 the plane of spread bytes, 4 that
+ * plane is strip-interleaved, 8 the bit strips, 16 the coarsest level's bit planes.  form: the form of the last build, -1 none
+ * yet, 0 the 8 response planes, 1 the spread plane row-major, 2 the same in strips, 3 bit planes, 4 bit strips, 5 bit strips in
+ * the tiles the call's coarse candidates read only.  builder: 0 none, 1 the one-launch builder for strides 4 and 8, 2 the batched
+ * any-stride builder, 3 the generic single-frame builder, 4 the unfused spread / response / linearize kernels.  split, allty:
+ * work items per (pixel row, 4 cells) of an 8-plane level, and 1 where a thread built all four sub-rows of its cells (builder 1;
+ * else 0).  packed: 1 the bit planes were since packed from the spread plane, 2 from the 8 response planes, 0 neither.  A call
+ * replayed from a captured graph reports what it was captured with.  Reads a host-side record: no device work, no
+ * synchronisation, no state change.  A parity-test accessor. */
+int sbm_get_level_build(sbm_ctx* ctx, int32_t level, int32_t out[6]);
+/* One frame's whole share of one buffer of `level`, zero tail included, exactly as it lies in device memory.  which: 0 the 8
+ * response planes (8 * lm_stride bytes), 1 the plane of spread bytes (lm_stride), 2 the bit strips (the strips' dwords, then a
+ * zero tail up to the frame stride), 3 the refinement-tile flags of level 0 (one byte per tile).  *bytes: the size of that share;
+ * out_host may be null to ask for it alone.  Waits for the device and copies: nothing is rebuilt, expanded or completed, and the
+ * record of current buffers does not change -- whether the buffer is current is sbm_get_level_build's to say.  SBM_ERR_STATE
+ * when the buffer is not allocated, SBM_ERR_INVALID for a frame outside the last batch.  A parity-test accessor. */
+int sbm_get_level_stored(sbm_ctx* ctx, int32_t level, int32_t frame, int32_t which, uint8_t* out_host, int64_t cap_bytes,
+                         int64_t* bytes);
 int sbm_level_dims(sbm_ctx* ctx, int32_t level, int32_t* rows, int32_t* cols);
 
 /* Second half of match(): Detector::matchClass over the selected templates

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "sbm_get_sparse_list",
     "sbm_match_batch_device_ptrs",
     "sbm_match_batch_device_planes",
+    "sbm_get_level_build",
+    "sbm_get_level_stored",
 ]
 
 # sbm_match_batch_device_ptrs flags: the caller promises that every frame pointer is a multiple of 4
@@ -225,6 +227,8 @@ def lib() -> C.CDLL:
     L.sbm_get_sparse_items.argtypes = [vp, vp]
     L.sbm_get_sparse_list.argtypes = [vp, vp]
     L.sbm_get_refine_form.argtypes = [vp, i32, vp]
+    L.sbm_get_level_build.argtypes = [vp, i32, vp]
+    L.sbm_get_level_stored.argtypes = [vp, i32, i32, i32, vp, i64, C.POINTER(i64)]
     L.sbm_level_dims.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.sbm_match_templates.argtypes = [vp, f32, vp, i64, C.POINTER(i64)]
     L.sbm_quantized_orientations.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]
@@ -849,6 +853,24 @@ class Context:
         out = np.zeros(2, np.int32)
         _check(lib().sbm_get_sparse_list(self._h, _p(out)))
         return tuple(int(v) for v in out)
+
+    def level_build(self, level: int) -> Tuple[int, int, int, int, int, int]:
+        """(current, form, builder, split, allty, packed) of ``level``: the buffers that are current as the bit set planes8 1,
+        spread 2, strip 4, bit strips 8, bit planes 16; the LmForm of its last build (5: sparse bit strips); the builder 0 none,
+        1 k_build_lm_rows, 2 k_build_lm_any, 3 k_build_lm, 4 the unfused path; split and allty of that launch; packed 1 when
+        the bit planes came from k_pack_bitplanes_spread, 2 from k_pack_bitplanes, else 0"""
+        out = np.zeros(6, np.int32)
+        _check(lib().sbm_get_level_build(self._h, level, _p(out)))
+        return tuple(int(v) for v in out)
+
+    def level_stored(self, level: int, frame: int, which: int) -> np.ndarray:
+        """the bytes of frame ``frame``'s whole share of one buffer of ``level``, tail included, as they lie in device memory:
+        ``which`` 0 the 8 response planes, 1 the spread plane, 2 the bit strips, 3 the refinement-tile flags (level 0)"""
+        n = C.c_int64(0)
+        _check(lib().sbm_get_level_stored(self._h, level, frame, which, None, 0, C.byref(n)))
+        out = np.empty(n.value, np.uint8)
+        _check(lib().sbm_get_level_stored(self._h, level, frame, which, _p(out), out.nbytes, C.byref(n)))
+        return out
 
     def match_templates(self, threshold: float) -> np.ndarray:
         out = np.empty(self._cap, MATCH_DTYPE)

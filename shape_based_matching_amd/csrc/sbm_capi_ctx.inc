@@ -298,6 +298,7 @@ struct sbm_ctx {
         int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
         int32_t source_form = 0;               // ... and the captured source pass
         int32_t refine_form[SBM_MAX_LEVELS][6] = {}; // ... and what the captured enqueue_local launched per level
+        int32_t level_build[SBM_MAX_LEVELS][5] = {}; // ... and the captured builds of the levels' linear memories (LevelBuild)
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
@@ -314,6 +315,15 @@ struct sbm_ctx {
         const int32_t f[6] = {kind, LW, order, t8 ? 1 : 0, sparse ? 1 : 0, slots};
         memcpy(refine_form[l], f, sizeof f);
     }
+    // per level, what the last build of its linear memories was (sbm_get_level_build): the LmForm it was made in (LM_BIT_STRIPS_SPARSE
+    // included), the builder (0 none, 1 k_build_lm_rows, 2 k_build_lm_any, 3 k_build_lm, 4 the unfused path), LmWork's split and allty of
+    // that launch, and which kernel packed the coarsest level's bit planes since (1 k_pack_bitplanes_spread, 2 k_pack_bitplanes, 0 none).
+    // Noted where the launch is made; a replayed graph reports what it was captured with.
+    struct LevelBuild {
+        int32_t form = LM_NONE, builder = 0, split = 0, allty = 0, packed = 0;
+    };
+    LevelBuild level_build[SBM_MAX_LEVELS];
+    void note_level_build(int l, LmForm f, int builder, int split = 0, int allty = 0) { level_build[l] = LevelBuild{(int32_t)f, builder, split, allty, 0}; }
     void note_coarse_form(int kind, int P, bool wide, int dw)
     {
         coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw;
@@ -932,6 +942,7 @@ int launch_lm_level(sbm_ctx* c, hipStream_t s, int l, LmForm f)
     a.lv[0] = lm_level_args(c, l, f, 1, 0, &blocks);
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
+    c->note_level_build(l, f, 1, a.lv[0].split, a.lv[0].allty);
     return 0;
 }
 
@@ -949,6 +960,7 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
         dim3 grid((W + LM_GX - 1) / LM_GX, H);
         SBM_LAUNCH(c, "k_build_lm", k_build_lm, grid, dim3(256), smem, s, d_q, rows, cols, T, W, H, d_lm, lm_stride);
         HIP_TRY(hipGetLastError());
+        c->note_level_build(l, LM_PLANES8, 3);
         return 0;
     }
     // large strides: unfused path through scratch (spread, 8 response maps)
@@ -963,6 +975,7 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
     for (int o = 0; o < 8; ++o)
         hipLaunchKernelGGL(k_linearize, dim3(blocks), dim3(256), 0, s, maps + o * n, rows, cols, T, d_lm + o * lm_stride);
     HIP_TRY(hipGetLastError());
+    c->note_level_build(l, LM_PLANES8, 4);
     return 0;
 }
 
@@ -1193,6 +1206,7 @@ int launch_lm_any(sbm_ctx* c, hipStream_t s, const BuildPlan& plan, int frames, 
     }
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_any, dim3((unsigned)blocks, frames), dim3(LMA_THREADS), (size_t)smem, s, a);
     HIP_TRY(hipGetLastError());
+    for (int l = 0; l < c->L; ++l) c->note_level_build(l, plan.form[l], 2);
     return 0;
 }
 
@@ -1282,6 +1296,10 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
         }
         SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
+        for (int i = 0; i < a.n_levels; ++i) { // (a.lv[] is coarsest first and skips a sparse level 0)
+            const int l = c->L - 1 - i;
+            c->note_level_build(l, plan.form[l], 1, a.lv[i].split, a.lv[i].allty);
+        }
     } else if (pin.any_batch) {
         if (int e = launch_lm_any(c, s, plan, frames, reset_count)) return e;
     }
@@ -1291,6 +1309,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
         SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
                    c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
         HIP_TRY(hipGetLastError());
+        c->level_build[l].packed = 1;
     }
     record_build(c->forms, c->L, plan);
     c->levels_valid = c->L;
@@ -1428,6 +1447,7 @@ int pack_bitplanes(sbm_ctx* c, hipStream_t s, int frames)
                c->lm_stride[lc], (int64_t)8 * c->lm_stride[lc], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[lc]) / 4, n_dwords);
     HIP_TRY(hipGetLastError());
     c->forms[lc].bit_planes = true;
+    c->level_build[lc].packed = 2;
     return 0;
 }
 
@@ -1740,6 +1760,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     a.n_tiles = n_tiles;
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
+    c->note_level_build(0, LM_BIT_STRIPS_SPARSE, 1, a.lv[0].split, a.lv[0].allty);
     return 0;
 }
 
@@ -1860,6 +1881,8 @@ int graph_replay(sbm_ctx* c, const GraphKey& key, hipStream_t s, bool* launched,
         memcpy(ge.coarse_form, c->coarse_form, sizeof ge.coarse_form);
         ge.source_form = c->source_form;
         memcpy(ge.refine_form, c->refine_form, sizeof ge.refine_form);
+        static_assert(sizeof ge.level_build == sizeof c->level_build, "LevelBuild is five int32");
+        memcpy(ge.level_build, c->level_build, sizeof ge.level_build);
         c->graphs.push_back(ge);
         hit = &c->graphs.back();
     } else {
@@ -1870,6 +1893,9 @@ int graph_replay(sbm_ctx* c, const GraphKey& key, hipStream_t s, bool* launched,
     memcpy(c->coarse_form, hit->coarse_form, sizeof c->coarse_form);
     c->source_form = hit->source_form;
     memcpy(c->refine_form, hit->refine_form, sizeof c->refine_form);
+    // the builds: a match call's graph made every level; the template loop's (kind < 0) only level 0's sparse strips, if any
+    if (key.kind >= 0) memcpy(c->level_build, hit->level_build, sizeof c->level_build);
+    else if (hit->level_build[0][0] == LM_BIT_STRIPS_SPARSE) memcpy(&c->level_build[0], hit->level_build[0], sizeof c->level_build[0]);
     *launched = true;
     return 0;
 }

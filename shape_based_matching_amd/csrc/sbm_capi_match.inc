@@ -894,6 +894,40 @@ int sbm_get_sparse_list(sbm_ctx* c, int32_t out[2])
     return 0;
 }
 
+int sbm_get_level_build(sbm_ctx* c, int32_t level, int32_t out[6])
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    if (level < 0 || level >= c->L) return fail(SBM_ERR_INVALID, "level %d of %d", level, c->L);
+    const LevelForms& f = c->forms[level];
+    const sbm_ctx::LevelBuild& b = c->level_build[level];
+    out[0] = (f.planes8 ? 1 : 0) | (f.spread ? 2 : 0) | (f.spread && f.spread_strip ? 4 : 0) | (f.bit_strips ? 8 : 0) | (f.bit_planes ? 16 : 0);
+    out[1] = b.form, out[2] = b.builder, out[3] = b.split, out[4] = b.allty, out[5] = b.packed;
+    return 0;
+}
+
+int sbm_get_level_stored(sbm_ctx* c, int32_t level, int32_t frame, int32_t which, uint8_t* out, int64_t cap_bytes, int64_t* bytes)
+{
+    if (!c || !bytes) return fail(SBM_ERR_INVALID, "null argument");
+    if (level < 0 || level >= c->L || which < 0 || which > 3 || (which == 3 && level != 0))
+        return fail(SBM_ERR_INVALID, "no buffer %d at level %d", which, level);
+    const DevBuf& buf = which == 0 ? c->d_lm[level] : which == 1 ? c->d_lmc[level] : which == 2 ? c->d_lbits[level] : c->d_tiles;
+    if (!buf.p) return fail(SBM_ERR_STATE, "buffer %d of level %d is not allocated", which, level);
+    if (frame < 0 || frame >= c->last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->last_frames);
+    const int T = c->cfg.T[level];
+    const int64_t need = which == 0   ? 8 * c->lm_stride[level]
+                         : which == 1 ? c->lm_stride[level]
+                         : which == 2 ? lbits_frame_bytes(c, level)
+                                      : (int64_t)refine_tile_count(c->cols[0] / T, c->rows[0] / T);
+    *bytes = need;
+    if (!out) return 0;
+    if (cap_bytes < need) return fail(SBM_ERR_CAPACITY, "need %lld bytes", (long long)need);
+    if ((int64_t)(frame + 1) * need > (int64_t)buf.cap) return fail(SBM_ERR_STATE, "buffer %d of level %d holds no frame %d", which, level, frame);
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    HIP_TRY(hipDeviceSynchronize()); // the batch may have been built on the caller's stream
+    HIP_TRY(hipMemcpy(out, (const uint8_t*)buf.p + (size_t)frame * need, (size_t)need, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int sbm_level_dims(sbm_ctx* c, int32_t level, int32_t* rows, int32_t* cols)
 {
     if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");

@@ -6,6 +6,7 @@
 #pragma once
 #include "sbm_common.h"
 #include "sbm_bitplane_math.h"
+#include "sbm_lm_layout.h" // lm_strip_offset, lm_bits_offset, lm_bits_dwords
 #include "sbm_refine_tiles.h" // RT_LIST_NONE
 
 namespace sbm {
@@ -85,15 +86,7 @@ __global__ __launch_bounds__(256) void k_build_lm(const uint8_t* __restrict__ q,
     }
 }
 
-// Strip-interleaved compact plane of a refinement-only level (needs W % 16 == 0): inside sub-plane
-// sub = (y%T)*T + x%T the W x H grid is cut into W/16 column strips of 16 cells, and a strip is stored row after
-// row, 16 bytes per row:  offset = sub*W*H + ((gx / 16) * H + gy) * 16 + gx % 16.
-// similarityLocal (line2Dup.cpp:860-922) reads 16 x 16 cells per feature; row-major that is 16 pieces of 16 bytes in
-// 16 different 128-byte lines, here it is two runs of 256 contiguous bytes at most (one when gx % 16 == 0).
-__host__ __device__ __forceinline__ int64_t lm_strip_offset(int sub, int gy, int gx, int W, int H)
-{
-    return (int64_t)sub * W * H + ((int64_t)(gx >> 4) * H + gy) * 16 + (gx & 15);
-}
+// (the strip-interleaved compact plane of a refinement-only level: lm_strip_offset, sbm_lm_layout.h)
 
 // ---- register-only variant for T = 4 and T = 8 (the reference's strides) ----
 // One lane owns 4 consecutive grid cells (4*T pixels) of one (ty, gy) pixel row
@@ -299,12 +292,7 @@ __device__ __forceinline__ void build_lm_rows_item(const uint8_t* __restrict__ q
 // instead of 2 and its launch goes from 19 to 33 us; strip pairs side by side 17.0 / 23; this form 17.7 / 19.5.
 // After the LDS hop a thread takes two units (sub, strip, row pair): the 32 spread bytes of two strip rows -> 8 bit-plane
 // dwords (bytes32_to_bitplanes) -> 8 stores of 8 bytes.
-__host__ __device__ __forceinline__ int64_t lm_bits_offset(int plane, int strip, int gy, int W, int H)
-{
-    return ((int64_t)plane * (W >> 4) + strip) * H + gy;
-}
-// dwords of a level stored as bit strips, without the zero tail
-__host__ __device__ __forceinline__ int64_t lm_bits_dwords(int W, int H) { return (int64_t)128 * (W >> 4) * H; }
+// (lm_bits_offset and lm_bits_dwords: sbm_lm_layout.h)
 
 template <bool BITS = false>
 __device__ __forceinline__ void build_lm_strip4_allty(const uint8_t* __restrict__ q, int rows, int cols, int W, int H,
