@@ -216,6 +216,16 @@ public:
 
     int addTemplate_rotate(const std::string& class_id, int zero_id, float theta, cv::Point2f center);
 
+    /* MI355X extension: the loop
+     *     for b in order: for k in order: addTemplate_rotate(class_id, zero_ids[b], thetas[k], centers[b])
+     * as one call on the device (sbm_train_rotate, on the training context addTemplates keeps): the ids in that order,
+     * and the detector afterwards is the loop's.  zero_ids name templates that exist before the call; centers has one
+     * entry per zero_id.  The engine's domain (include/sbm.h: |theta| <= 36000, |centre| <= 65536, a base with features,
+     * their orientations within [-720, 720]) is narrower than the loop's: outside it the call throws and leaves the
+     * detector as it was.  addTemplate_rotate itself stays host code. */
+    std::vector<int> addTemplates_rotate(const std::string& class_id, const std::vector<int>& zero_ids,
+                                         const std::vector<float>& thetas, const std::vector<cv::Point2f>& centers);
+
     const cv::Ptr<ColorGradient>& getModalities() const { return modality; }
     int getT(int pyramid_level) const { return T_at_level[pyramid_level]; }
     int pyramidLevels() const { return pyramid_levels; }

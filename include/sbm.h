@@ -644,6 +644,56 @@ int sbm_train_sweep(sbm_ctx* ctx, const uint8_t* img_host, int32_t rows, int32_t
                     const uint8_t* mask_host, const sbm_train_scale* scales, int32_t n_scales, float strong_threshold,
                     sbm_template_level* levels, sbm_train_feature* feats, int32_t* status);
 
+/* ---- rotated template families -------------------------------------------------
+ * Detector::addTemplate_rotate (line2Dup.cpp:1395-1451) for n_bases trained pyramids and n_thetas angles each, in one
+ * call on the device: the reference's demo trains one template and calls addTemplate_rotate once per angle
+ * (test.cpp:303-313).  Pair p = b * n_thetas + k is exactly what addTemplate_rotate(class, base b, thetas[k],
+ * centre of b) makes of that pair alone -- every rounding step of the rotation kept (float differences, double
+ * products and sums without fused multiply-add, truncation of r + 0.5f), the orientation wrapped and its label taken
+ * as there, cropTemplates (:115-161) over the pair's levels.  cos and sin of each angle are computed once on the host
+ * and travel to the kernel as a table, so no device libm enters the result.
+ *   levels[p * n_levels + l]   the rotated template of level l; feature_offset counts from the pair's feature block,
+ *                              level l's features directly behind level l-1's
+ *   feats[bases[b].out_first + k * bases[b].out_cap ...]   the pair's block of out_cap records
+ *   status[2 * p], status[2 * p + 1]
+ *       {0, features}          ok
+ *       {1, level}             the base's own training failure: its status pair began with 1, and the pair is copied
+ *       {2, features needed}   out_cap too small
+ *       {3, reason}            the base is not rotatable: 1 its status pair is neither ok nor a training failure (its
+ *                              features overflowed their block), 2 it has no feature at all or a level's n_features
+ *                              is outside 0 .. 8191, 3 a feature lies outside the domain below
+ * The level records of a pair that is not ok are zeroed, as in training; one pair never touches another's output.
+ * Domain: every theta finite with |theta| <= 36000, every centre component finite with |c| <= 65536 (SBM_ERR_INVALID
+ * otherwise, nothing enqueued); every base feature's theta finite and in [-720, 720] and its coordinate (x + tl_x,
+ * y + tl_y) in 0 .. 32767 -- in the device form the host cannot see these, so a feature outside gives its pairs status
+ * {3, 3}; the wrap loops of the orientation carry a fixed bound (103 steps) and cannot spin.
+ * SBM_ERR_INVALID, with nothing enqueued: a null argument, n_bases or n_thetas < 1, n_bases * n_thetas >
+ * 2^31 / n_levels, a negative out_first or out_cap, output blocks (a base's n_thetas * out_cap records from out_first)
+ * that overlap, a theta or a centre outside the domain.  Output blocks must not overlap any base's own features. */
+typedef struct sbm_rotate_base {          /* one trained pyramid and where its rotations go (48 bytes) */
+    const sbm_template_level* levels;     /* n_levels records, as sbm_train_* wrote them (tl_x/tl_y set) */
+    const sbm_train_feature*  feats;      /* the block the levels' feature_offset counts from */
+    const int32_t*            status;     /* NULL, or the base's status pair from a training call */
+    float center_x, center_y;             /* level-0 centre of rotation */
+    int64_t out_first, out_cap;           /* rotation k's feature block: [out_first + k*out_cap, +out_cap) */
+} sbm_rotate_base;
+
+/* Device form.  `bases` and `thetas` are HOST arrays, read during the call only; the pointers inside a record are
+ * device addresses, and may be the very output buffers of a preceding sbm_train_*_device call on the same stream
+ * (sweep, then rotate, never returning to the host).  d_levels: n_bases * n_thetas * n_levels sbm_template_level;
+ * d_feats: the feature array the blocks lie in; d_status: n_bases * n_thetas * 2 int32.  Stream-ordered on `stream`
+ * (NULL: the context's): the records and the angle table travel on the stream from the pinned slot of the ragged
+ * training table, so calls enqueued back to back need no synchronisation between them.  The
+ * one-training-scratch-per-context rule of sbm_train_batch_device stands.  Not capturable into a hipGraph (the host
+ * wait for the slot, and the tables' contents are the call's). */
+int sbm_train_rotate_device(sbm_ctx* ctx, const sbm_rotate_base* bases, int32_t n_bases, const float* thetas,
+                            int32_t n_thetas, void* d_levels, void* d_feats, void* d_status, void* stream);
+/* Host form: levels, feats and status inside the records are host addresses (a base's features are read up to the end
+ * its level records give), and so are levels, feats and status of the result.  Uploads, runs the device form on the
+ * context's stream, downloads and synchronises; of the feature array only the blocks of pairs that are ok are written. */
+int sbm_train_rotate(sbm_ctx* ctx, const sbm_rotate_base* bases, int32_t n_bases, const float* thetas,
+                     int32_t n_thetas, sbm_template_level* levels, sbm_train_feature* feats, int32_t* status);
+
 /* ---- measurement ---------------------------------------------------------
  * Per-kernel HIP-event timings of the last sbm_match/sbm_build_pyramid/
  * sbm_match_templates call when profiling was enabled (adds synchronisation;

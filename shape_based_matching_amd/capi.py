@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_host", "sbm_match_batch_host_begin", "sbm_match_batch_host_end", "sbm_extract_local_maxima",
     "sbm_train_batch", "sbm_train_batch_device",
     "sbm_train_ragged", "sbm_train_ragged_device", "sbm_train_sweep", "sbm_train_sweep_device",
+    "sbm_train_rotate", "sbm_train_rotate_device",
     "sbm_set_pipeline_depth", "sbm_set_coarse_mode", "sbm_set_refine_order", "sbm_set_refine_bits", "sbm_get_coarse_bitplanes",
     "sbm_comm_count", "sbm_match_templates_device_sharded", "sbm_graph_count",
     "sbm_nms_batch_device", "sbm_match_batch_host_end_nms",
@@ -98,6 +99,19 @@ class SbmTrainScale(C.Structure):
         ("reserved", C.c_int32),
         ("feat_first", C.c_int64),
         ("feat_cap", C.c_int64),
+    ]
+
+
+class SbmRotateBase(C.Structure):
+    """sbm_rotate_base: one trained pyramid of a rotate call and where its rotations go (48 bytes)"""
+    _fields_ = [
+        ("levels", C.c_void_p),
+        ("feats", C.c_void_p),
+        ("status", C.c_void_p),
+        ("center_x", C.c_float),
+        ("center_y", C.c_float),
+        ("out_first", C.c_int64),
+        ("out_cap", C.c_int64),
     ]
 
 
@@ -263,6 +277,8 @@ def lib() -> C.CDLL:
     L.sbm_train_ragged.argtypes = [vp, vp, i32, i32, f32, vp, vp, vp]
     L.sbm_train_sweep_device.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, vp, vp]
     L.sbm_train_sweep.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, f32, vp, vp, vp]
+    L.sbm_train_rotate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.sbm_train_rotate.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
     L.sbm_set_pipeline_depth.argtypes = [vp, i32]
     L.sbm_set_coarse_mode.argtypes = [vp, i32]
     L.sbm_set_refine_order.argtypes = [vp, i32]
@@ -667,6 +683,71 @@ class Context:
         num_features_each[k]) for every scale s, the source uploaded once and resized on the device: a list of
         (levels, feats), None where addTemplate returns -1."""
         return self.train_sweep_status(img, mask, scales, strong, num_features_each)[0]
+
+    # ---- rotated template families: Detector::addTemplate_rotate for every (base, angle) pair of a call ----------------
+    def train_rotate_device(self, bases: Sequence["SbmRotateBase"], thetas: Sequence[float], d_levels: int, d_feats: int, d_status: int,
+                            stream: int = 0):
+        """sbm_train_rotate_device: `bases` are records of device addresses (read during the call only, as `thetas`); pair
+        p = b * len(thetas) + k writes its n_levels level records at d_levels, its features in rotation k's block of base
+        b, {status, value} at d_status + 2*p."""
+        arr = (SbmRotateBase * max(len(bases), 1))(*bases)
+        th = np.ascontiguousarray(thetas, np.float32)
+        _check(lib().sbm_train_rotate_device(self._h, arr, len(bases), _p(th), len(th), C.c_void_p(d_levels),
+                                             C.c_void_p(d_feats) if d_feats else None, C.c_void_p(d_status),
+                                             C.c_void_p(stream) if stream else None))
+
+    def train_rotate_raw(self, bases, thetas: Sequence[float], centers, out_caps: Sequence[int], out_firsts: Optional[Sequence[int]] = None,
+                         feats: Optional[np.ndarray] = None):
+        """sbm_train_rotate as it is: (levels[n_bases, n_thetas, n_levels], feats[total], status[n_bases, n_thetas, 2],
+        firsts[n_bases]).  A base is (levels, feats) or (levels, feats, status pair); rotation k of base b has the block of
+        out_caps[b] records from out_firsts[b] + k * out_caps[b] (None: the bases' blocks behind each other); `feats`, if
+        given, is the feature array the call writes into (a caller's fill stays where no pair that is ok writes)."""
+        nb, th = len(bases), np.ascontiguousarray(thetas, np.float32)
+        nt = len(th)
+        if len(centers) != nb or len(out_caps) != nb:
+            raise ValueError("one centre and one capacity per base")
+        firsts = list(np.cumsum([0] + [max(int(c), 0) * nt for c in out_caps])[:-1]) if out_firsts is None else list(out_firsts)
+        keep, desc = [], (SbmRotateBase * max(nb, 1))()
+        for b, base in enumerate(bases):
+            lv = np.ascontiguousarray(base[0], LEVEL_DTYPE)
+            ft = np.ascontiguousarray(base[1], TRAIN_FEATURE_DTYPE)
+            if len(ft) == 0:
+                ft = np.zeros(1, TRAIN_FEATURE_DTYPE)
+            st = None if len(base) < 3 or base[2] is None else np.ascontiguousarray(base[2], np.int32)
+            if len(lv) != self.n_levels or (st is not None and st.shape != (2,)):
+                raise ValueError("a base: n_levels level records, its features, and None or a status pair")
+            keep.append((lv, ft, st))
+            desc[b] = SbmRotateBase(lv.ctypes.data, ft.ctypes.data, None if st is None else st.ctypes.data, float(centers[b][0]), float(centers[b][1]),
+                                    int(firsts[b]), int(out_caps[b]))
+        end = max([int(f) + max(int(c), 0) * nt for f, c in zip(firsts, out_caps)] + [0])
+        if feats is None:
+            feats = np.zeros(max(end, 1), TRAIN_FEATURE_DTYPE)
+        levels = np.zeros((nb, max(nt, 1), self.n_levels), LEVEL_DTYPE)
+        status = np.zeros((nb, max(nt, 1), 2), np.int32)
+        _check(lib().sbm_train_rotate(self._h, desc, nb, _p(th), nt, _p(levels), _p(feats), _p(status)))
+        return levels, feats, status, firsts
+
+    def train_rotate(self, bases, thetas: Sequence[float], centers):
+        """Detector::addTemplate_rotate(class, base b, thetas[k], centers[b]) for every base and angle in one call.  A base
+        is (levels, feats) as the train_* calls return it, or None (a template whose training failed).  Returns a list over
+        the pairs p = b * len(thetas) + k of (levels, feats), None for the pairs of a base that is None."""
+        zero = np.zeros(self.n_levels, LEVEL_DTYPE)
+        failed = np.array([1, 0], np.int32)
+        full = [(zero, np.zeros(1, TRAIN_FEATURE_DTYPE), failed) if b is None else (b[0], b[1], None) for b in bases]
+        caps = [0 if b is None else max(int(np.asarray(b[0]["n_features"]).clip(0).sum()), 1) for b in bases]
+        levels, feats, status, firsts = self.train_rotate_raw(full, thetas, centers, caps)
+        out = []
+        for b in range(len(bases)):
+            for k in range(len(thetas)):
+                code, value = int(status[b, k, 0]), int(status[b, k, 1])
+                if code == 1:
+                    out.append(None)
+                    continue
+                if code != 0:
+                    raise SbmError(-3, f"base {b}, angle {k}: status {{{code}, {value}}}")
+                first = firsts[b] + k * caps[b]
+                out.append((levels[b, k].copy(), feats[first: first + value].copy()))
+        return out
 
     def select_templates(self, idx: Sequence[int]):
         a = np.ascontiguousarray(idx, np.int32)

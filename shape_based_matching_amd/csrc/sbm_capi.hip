@@ -25,6 +25,7 @@
 #include "sbm_frame_planes_plan.h"
 #include "sbm_frame_source.h"
 #include "sbm_train_kernels.h"
+#include "sbm_rotate_kernels.h"
 #include "sbm_nms_kernels.h"
 
 using namespace sbm;

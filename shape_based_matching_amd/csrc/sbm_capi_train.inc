@@ -2,7 +2,9 @@
 // template training, Detector::addTemplate (line2Dup.cpp:1299-1353) for a batch of images of one geometry with no host
 // round trip (sbm_train_batch_device) and its host-array sibling (sbm_train_batch); the ragged form for images of
 // different sizes and feature counts (sbm_train_ragged_device, sbm_train_ragged), whose host rules are
-// sbm_train_plan.h's, and the scale sweep of one source on top of it (sbm_train_sweep_device, sbm_train_sweep).
+// sbm_train_plan.h's, and the scale sweep of one source on top of it (sbm_train_sweep_device, sbm_train_sweep); at the
+// end, Detector::addTemplate_rotate (line2Dup.cpp:1395-1451) for every (base, angle) pair of a call
+// (sbm_train_rotate_device, sbm_train_rotate), whose scalar rule is sbm_rotate_math.h's.
 // ---------------------------------------------------------------------------
 
 namespace {
@@ -543,6 +545,159 @@ int sbm_train_sweep(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, 
                                    (int32_t*)(d_out + o.o_status), &job)))
         return rc;
     return train_out_download(c, imgs.data(), n_scales, o, levels, feats, status);
+}
+
+} // extern "C"
+
+// ---- rotated template families ---------------------------------------------------------------------------------------------
+
+namespace {
+
+// What the host can judge of a rotate call: the counts, the angles and centres against the domain of sbm_rotate_math.h,
+// the output blocks (base b's n_thetas * out_cap records from out_first) against each other.  *feats_end: the end of the
+// feature array the blocks lie in, in records.
+int train_rotate_check(const sbm_ctx* c, const sbm_rotate_base* bases, int n_bases, const float* thetas, int n_thetas, int64_t* feats_end)
+{
+    if (n_bases < 1 || n_thetas < 1) return fail(SBM_ERR_INVALID, "%d bases and %d angles: at least one of each", n_bases, n_thetas);
+    if ((int64_t)n_bases * n_thetas > ((int64_t)1 << 31) / c->L)
+        return fail(SBM_ERR_INVALID, "%d bases x %d angles exceed 2^31 / %d levels", n_bases, n_thetas, c->L);
+    for (int k = 0; k < n_thetas; ++k)
+        if (!rotate_theta_ok(thetas[k])) return fail(SBM_ERR_INVALID, "angle %d: not finite or beyond +-36000 degrees", k);
+    std::vector<std::pair<int64_t, int64_t>> blocks; // [first, end) of the bases that write anything
+    int64_t end = 0;
+    for (int b = 0; b < n_bases; ++b) {
+        const sbm_rotate_base& r = bases[b];
+        if (!r.levels || !r.feats) return fail(SBM_ERR_INVALID, "base %d: null levels or features", b);
+        if (!rotate_center_ok(r.center_x) || !rotate_center_ok(r.center_y)) return fail(SBM_ERR_INVALID, "base %d: centre not finite or beyond +-65536", b);
+        if (r.out_first < 0 || r.out_cap < 0) return fail(SBM_ERR_INVALID, "base %d: negative out_first or out_cap", b);
+        if (r.out_cap > (INT64_MAX / (int64_t)sizeof(sbm_train_feature) - r.out_first) / n_thetas) return fail(SBM_ERR_INVALID, "base %d: output block too large", b);
+        if (r.out_cap == 0) continue;
+        blocks.emplace_back(r.out_first, r.out_first + r.out_cap * n_thetas);
+        end = std::max(end, blocks.back().second);
+    }
+    std::sort(blocks.begin(), blocks.end());
+    for (size_t i = 1; i < blocks.size(); ++i)
+        if (blocks[i].first < blocks[i - 1].second) return fail(SBM_ERR_INVALID, "the output blocks of two bases overlap");
+    *feats_end = end;
+    return 0;
+}
+
+// The records and the angle table through the pinned slot onto the stream, into the training scratch, then the one launch.
+int train_rotate_enqueue(sbm_ctx* c, hipStream_t s, const sbm_rotate_base* bases, int n_bases, const float* thetas, int n_thetas, sbm_template_level* d_levels,
+                         sbm_train_feature* d_feats, int32_t* d_status)
+{
+    const size_t base_bytes = train_align((size_t)n_bases * sizeof(sbm_rotate_base)), total = base_bytes + train_align((size_t)n_thetas * sizeof(RotateAngle));
+    if (total > c->d_train.cap) {
+        HIP_TRY(hipDeviceSynchronize()); // calls in flight may use the old scratch
+        if (int e = c->d_train.ensure(total)) return e;
+    }
+    uint8_t* d_table = c->d_train.as<uint8_t>();
+    uint8_t* slot = nullptr;
+    if (int e = train_table_slot(c, total, &slot)) return e;
+    memset(slot, 0, total);
+    memcpy(slot, bases, (size_t)n_bases * sizeof(sbm_rotate_base));
+    RotateAngle* angles = (RotateAngle*)(slot + base_bytes);
+    for (int k = 0; k < n_thetas; ++k) angles[k] = rotate_angle(thetas[k]);
+    c->train_table_busy = true; // as train_ragged_enqueue: from before the copy
+    c->train_table_stream = s;
+    c->train_table_recorded = false;
+    HIP_TRY(hipMemcpyAsync(d_table, slot, total, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(c->ev_train_table, s));
+    c->train_table_recorded = true;
+    SBM_LAUNCH(c, "k_train_rotate", k_train_rotate, dim3(n_thetas, std::min(n_bases, 65535)), dim3(256), 0, s, (const sbm_rotate_base*)d_table,
+               (const RotateAngle*)(d_table + base_bytes), c->L, n_bases, d_levels, d_feats, d_status);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int sbm_train_rotate_device(sbm_ctx* c, const sbm_rotate_base* bases, int32_t n_bases, const float* thetas, int32_t n_thetas, void* d_levels, void* d_feats,
+                            void* d_status, void* stream)
+{
+    if (!c || !bases || !thetas || !d_levels || !d_status) return fail(SBM_ERR_INVALID, "null argument");
+    int64_t feats_end = 0;
+    if (int e = train_rotate_check(c, bases, n_bases, thetas, n_thetas, &feats_end)) return e;
+    if (!d_feats && feats_end > 0) return fail(SBM_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    hipStream_t s = launch_stream(c, stream);
+    if (c->profiling && !c->profiling_keep) c->clear_timings();
+    return train_rotate_enqueue(c, s, bases, n_bases, thetas, n_thetas, (sbm_template_level*)d_levels, (sbm_train_feature*)d_feats, (int32_t*)d_status);
+}
+
+int sbm_train_rotate(sbm_ctx* c, const sbm_rotate_base* bases, int32_t n_bases, const float* thetas, int32_t n_thetas, sbm_template_level* levels,
+                     sbm_train_feature* feats, int32_t* status)
+{
+    if (!c || !bases || !thetas || !levels || !status) return fail(SBM_ERR_INVALID, "null argument");
+    int64_t feats_end = 0;
+    if (int e = train_rotate_check(c, bases, n_bases, thetas, n_thetas, &feats_end)) return e;
+    if (!feats && feats_end > 0) return fail(SBM_ERR_INVALID, "null argument");
+    const int L = c->L;
+    const size_t nb = (size_t)n_bases, pairs = nb * (size_t)n_thetas;
+    // the bases as one block of host bytes: per base its level records, its status pair, its features up to the end the
+    // records give (none of a base that is not ok, or whose counts the kernel refuses: it reads no feature of those)
+    std::vector<size_t> o_lv(nb), o_st(nb), o_ft(nb), n_ft(nb, 0);
+    size_t in_bytes = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        const sbm_rotate_base& r = bases[b];
+        o_lv[b] = in_bytes;
+        in_bytes += train_align((size_t)L * sizeof(sbm_template_level));
+        o_st[b] = in_bytes;
+        in_bytes += 256;
+        o_ft[b] = in_bytes;
+        if (rotate_base_verdict(r.status, r.levels, L, INT64_MAX).code != ROTATE_OK) continue;
+        int64_t ext = 0;
+        for (int l = 0; l < L; ++l) {
+            if (r.levels[l].n_features == 0) continue;
+            if (r.levels[l].feature_offset < 0) return fail(SBM_ERR_INVALID, "base %zu: negative feature_offset at level %d", b, l);
+            ext = std::max(ext, r.levels[l].feature_offset + r.levels[l].n_features);
+        }
+        n_ft[b] = (size_t)ext;
+        in_bytes += train_align(n_ft[b] * sizeof(sbm_train_feature));
+    }
+    std::vector<uint8_t> in(in_bytes, 0);
+    for (size_t b = 0; b < nb; ++b) {
+        memcpy(in.data() + o_lv[b], bases[b].levels, (size_t)L * sizeof(sbm_template_level));
+        if (bases[b].status) memcpy(in.data() + o_st[b], bases[b].status, 8);
+        if (n_ft[b]) memcpy(in.data() + o_ft[b], bases[b].feats, n_ft[b] * sizeof(sbm_train_feature));
+    }
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    if (int e = order_after_caller_work(c)) return e;
+    const size_t lv_bytes = pairs * (size_t)L * sizeof(sbm_template_level), ft_bytes = (size_t)feats_end * sizeof(sbm_train_feature),
+                 o_feats = train_align(lv_bytes), o_status = o_feats + train_align(ft_bytes), out_total = o_status + pairs * 8;
+    if (in_bytes > c->d_train_in.cap || out_total > c->d_train_out.cap) HIP_TRY(hipStreamSynchronize(c->stream));
+    int rc = 0;
+    if ((rc = c->d_train_in.ensure(in_bytes)) || (rc = c->d_train_out.ensure(out_total))) return rc;
+    hipStream_t s = c->stream;
+    uint8_t* d_in = c->d_train_in.as<uint8_t>();
+    uint8_t* d_out = c->d_train_out.as<uint8_t>();
+    std::vector<sbm_rotate_base> dev(bases, bases + nb);
+    for (size_t b = 0; b < nb; ++b) {
+        dev[b].levels = (const sbm_template_level*)(d_in + o_lv[b]);
+        dev[b].status = bases[b].status ? (const int32_t*)(d_in + o_st[b]) : nullptr;
+        dev[b].feats = (const sbm_train_feature*)(d_in + o_ft[b]);
+    }
+    HIP_TRY(hipMemcpyAsync(d_in, in.data(), in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_out, 0, out_total, s));
+    if (c->profiling && !c->profiling_keep) c->clear_timings();
+    if ((rc = train_rotate_enqueue(c, s, dev.data(), n_bases, thetas, n_thetas, (sbm_template_level*)d_out, (sbm_train_feature*)(d_out + o_feats),
+                                   (int32_t*)(d_out + o_status))))
+        return rc;
+    // of the feature array only the records the call made reach the caller's (train_out_download)
+    std::vector<sbm_train_feature> made((size_t)feats_end);
+    HIP_TRY(hipMemcpyAsync(levels, d_out, lv_bytes, hipMemcpyDeviceToHost, s));
+    if (ft_bytes) HIP_TRY(hipMemcpyAsync(made.data(), d_out + o_feats, ft_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status, d_out + o_status, pairs * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t b = 0; b < nb; ++b)
+        for (size_t k = 0; k < (size_t)n_thetas; ++k) {
+            const size_t p = b * (size_t)n_thetas + k;
+            const int64_t first = bases[b].out_first + (int64_t)k * bases[b].out_cap;
+            if (status[2 * p] == 0 && status[2 * p + 1] > 0) memcpy(feats + first, made.data() + first, (size_t)status[2 * p + 1] * sizeof(sbm_train_feature));
+        }
+    return 0;
 }
 
 } // extern "C"

@@ -4,6 +4,8 @@
 //       readClasses + (optional zero padding, crop to multiples of 16) + match; prints the matches
 //   demo train <image.ppm> <mask.pgm> <num_features> <n_rot> <angle_step> <templ_fmt> <class_id> [info.yaml]
 //       addTemplate (angle 0) + addTemplate_rotate for the remaining angles + writeClasses
+//   demo train_rot ...  the arguments and the output of train, the rotations through one Detector::addTemplates_rotate:
+//       every angle rotated on the device in one call (sbm_train_rotate)
 //   demo convert <in_fmt> <class_id> <out_fmt>
 //       readClasses + writeClasses (no GPU needed)
 //   demo scale_train <image.ppm> <num_features> <scale_lo> <scale_hi> <scale_step> <templ_fmt> <class_id> <info.yaml>
@@ -133,7 +135,7 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if (mode == "train") {
+        if (mode == "train" || mode == "train_rot") {
             if (argc < 9) return usage();
             Mat img = imread(argv[2], IMREAD_UNCHANGED), mask = imread(argv[3], IMREAD_GRAYSCALE);
             const int num_features = atoi(argv[4]), n_rot = atoi(argv[5]);
@@ -143,14 +145,28 @@ int main(int argc, char** argv)
             line2Dup::Detector detector(num_features, {4, 8});
             shape_based_matching::shapeInfo_producer shapes(img, mask);
             std::vector<shape_based_matching::shapeInfo_producer::Info> infos;
+            const auto t_train = std::chrono::steady_clock::now();
             int first_id = detector.addTemplate(shapes.src, class_id, shapes.mask); // test.cpp:304
             if (first_id < 0) { fprintf(stderr, "addTemplate failed\n"); return 1; }
             infos.emplace_back(0.f, 1.f);
+            std::vector<float> angles;
             for (int k = 1; k <= n_rot; ++k) { // test.cpp:310-312
                 float angle = 0.f;
                 for (int j = 0; j < k; ++j) angle += angle_step; // same float accumulation as produce_infos
-                detector.addTemplate_rotate(class_id, first_id, angle, {shapes.src.cols / 2.0f, shapes.src.rows / 2.0f});
+                angles.push_back(angle);
                 infos.emplace_back(angle, 1.f);
+            }
+            const Point2f center(shapes.src.cols / 2.0f, shapes.src.rows / 2.0f);
+            const auto t0 = std::chrono::steady_clock::now();
+            if (mode == "train_rot") { // the same loop as one call: every angle rotated on the device
+                if (n_rot > 0) detector.addTemplates_rotate(class_id, {first_id}, angles, {center});
+            } else {
+                for (float angle : angles) detector.addTemplate_rotate(class_id, first_id, angle, center);
+            }
+            if (getenv("SBM_DEMO_TIMING")) { // the training section's two parts, for tools/bench_train_rotate.py
+                const auto t1 = std::chrono::steady_clock::now();
+                fprintf(stderr, "add_template_ms %.3f rotate_ms %.3f\n", std::chrono::duration<double, std::milli>(t0 - t_train).count(),
+                        std::chrono::duration<double, std::milli>(t1 - t0).count());
             }
             detector.writeClasses(fmt);
             if (argc > 9) shape_based_matching::shapeInfo_producer::save_infos(infos, argv[9]);

@@ -291,6 +291,105 @@ std::vector<int> Detector::addTemplatesScaled(const Mat& source, const std::stri
     return ids;
 }
 
+// The loop of addTemplate_rotate over bases and angles as sbm_train_rotate calls: every base flattened once (its level
+// records with packed feature offsets, its features), rotation k of base b in a block of the base's feature count.  One
+// call where the whole family's features stay under the budget; otherwise base by base, the angles in runs that do.
+std::vector<int> Detector::addTemplates_rotate(const std::string& class_id, const std::vector<int>& zero_ids, const std::vector<float>& thetas,
+                                               const std::vector<Point2f>& centers)
+{
+    const size_t nb = zero_ids.size(), nt = thetas.size();
+    CV_Assert(centers.size() == nb);
+    CV_Assert(pyramid_levels >= 1 && pyramid_levels <= SBM_MAX_LEVELS && (int)T_at_level.size() >= pyramid_levels);
+    std::vector<TemplatePyramid>& template_pyramids = class_templates[class_id];
+    const int have = static_cast<int>(template_pyramids.size());
+    for (int id : zero_ids) CV_Assert(id >= 0 && id < have);
+    std::vector<int> ids;
+    if (nb == 0 || nt == 0) return ids;
+    const size_t L = (size_t)pyramid_levels;
+    std::vector<sbm_template_level> base_levels(nb * L);
+    std::vector<std::vector<sbm_train_feature>> base_feats(nb);
+    std::vector<int64_t> count(nb, 0);
+    int64_t family = 0; // features of all rotations
+    for (size_t b = 0; b < nb; ++b) {
+        const TemplatePyramid& tp = template_pyramids[(size_t)zero_ids[b]];
+        CV_Assert(tp.size() == L);
+        for (size_t l = 0; l < L; ++l) {
+            sbm_template_level& lv = base_levels[b * L + l];
+            lv.width = tp[l].width, lv.height = tp[l].height, lv.tl_x = tp[l].tl_x, lv.tl_y = tp[l].tl_y;
+            lv.pyramid_level = (int)l;
+            lv.n_features = (int)tp[l].features.size();
+            lv.feature_offset = count[b];
+            for (const Feature& f : tp[l].features) {
+                sbm_train_feature g;
+                g.x = f.x, g.y = f.y, g.label = f.label, g.theta = f.theta;
+                base_feats[b].push_back(g);
+            }
+            count[b] += lv.n_features;
+        }
+        if (base_feats[b].empty()) base_feats[b].resize(1);
+        family += count[b] * (int64_t)nt;
+    }
+    const int64_t budget = kTrainBudget / (int64_t)sizeof(sbm_train_feature);
+    std::vector<TemplatePyramid> made(nb * nt);
+    std::lock_guard<std::mutex> lock(g_train_mu);
+    sbm_ctx* ctx = train_ctx(T_at_level, pyramid_levels, modality->weak_threshold);
+    // bases [b0, b1) at the angles [k0, k1): one engine call
+    auto run = [&](size_t b0, size_t b1, size_t k0, size_t k1) {
+        const size_t m = k1 - k0;
+        std::vector<sbm_rotate_base> recs(b1 - b0);
+        int64_t first = 0;
+        for (size_t b = b0; b < b1; ++b) {
+            sbm_rotate_base& r = recs[b - b0];
+            memset(&r, 0, sizeof r);
+            r.levels = base_levels.data() + b * L;
+            r.feats = base_feats[b].data();
+            r.center_x = centers[b].x, r.center_y = centers[b].y;
+            r.out_first = first, r.out_cap = count[b];
+            first += count[b] * (int64_t)m;
+        }
+        std::vector<sbm_template_level> levels(recs.size() * m * L);
+        std::vector<sbm_train_feature> feats((size_t)std::max<int64_t>(first, 1));
+        std::vector<int32_t> status(recs.size() * m * 2);
+        check(sbm_train_rotate(ctx, recs.data(), (int)recs.size(), thetas.data() + k0, (int)m, levels.data(), feats.data(), status.data()), "sbm_train_rotate");
+        for (size_t b = b0; b < b1; ++b)
+            for (size_t k = 0; k < m; ++k) {
+                const size_t p = (b - b0) * m + k;
+                if (status[2 * p] != 0)
+                    CV_Error(Error::StsBadArg, cv::format("addTemplates_rotate: template %d at angle %zu is outside the engine's domain (status %d, %d)",
+                                                          zero_ids[b], k0 + k, status[2 * p], status[2 * p + 1]));
+                TemplatePyramid& tp = made[b * nt + k0 + k];
+                tp.assign(L, Template());
+                const sbm_train_feature* block = feats.data() + recs[b - b0].out_first + (int64_t)k * recs[b - b0].out_cap;
+                for (size_t l = 0; l < L; ++l) {
+                    const sbm_template_level& lv = levels[p * L + l];
+                    Template& t = tp[l];
+                    t.width = lv.width, t.height = lv.height, t.tl_x = lv.tl_x, t.tl_y = lv.tl_y;
+                    t.pyramid_level = lv.pyramid_level;
+                    t.features.resize((size_t)lv.n_features);
+                    const sbm_train_feature* f = block + lv.feature_offset;
+                    for (int j = 0; j < lv.n_features; ++j) {
+                        Feature& o = t.features[(size_t)j];
+                        o.x = f[j].x, o.y = f[j].y, o.label = f[j].label, o.theta = f[j].theta;
+                    }
+                }
+            }
+    };
+    if (family <= budget) {
+        run(0, nb, 0, nt);
+    } else {
+        for (size_t b = 0; b < nb; ++b) {
+            const size_t step = (size_t)std::max<int64_t>(1, std::min<int64_t>((int64_t)nt, budget / std::max<int64_t>(count[b], 1)));
+            for (size_t k0 = 0; k0 < nt; k0 += step) run(b, b + 1, k0, std::min(nt, k0 + step));
+        }
+    }
+    for (size_t p = 0; p < made.size(); ++p) { // the loop's order: base by base, angle by angle
+        ids.push_back(static_cast<int>(template_pyramids.size()));
+        template_pyramids.push_back(std::move(made[p]));
+    }
+    templatesChanged();
+    return ids;
+}
+
 } // namespace line2Dup
 
 namespace shape_based_matching {
