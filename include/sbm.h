@@ -694,6 +694,64 @@ int sbm_train_rotate_device(sbm_ctx* ctx, const sbm_rotate_base* bases, int32_t 
 int sbm_train_rotate(sbm_ctx* ctx, const sbm_rotate_base* bases, int32_t n_bases, const float* thetas,
                      int32_t n_thetas, sbm_template_level* levels, sbm_train_feature* feats, int32_t* status);
 
+/* ---- device-trained families as the match set ---------------------------------------
+ * sbm_upload_templates for pyramids that lie in device memory as a sbm_train_*_device call wrote them: the loop of
+ * addTemplate / addTemplate_rotate that fills the reference's TemplatesMap (test.cpp:303-313; line2Dup.cpp:1299-1353,
+ * :1395-1451) ends in the map matchClass walks (:1160-1172), and here in the context's template set, without the
+ * features leaving the device.  A source is a run of n_pyramids pyramids of one class: pyramid i's n_levels level
+ * records at d_levels + i * n_levels, its feature block the records [feat_first + i * feat_pitch, + feat_cap) of
+ * d_feats (a level's feature_offset counts from the block's start and its features must lie inside the block), its
+ * status pair at d_status + 2 * i (NULL: every pyramid is ok).
+ *   sbm_train_batch_device:   feat_first = 0, feat_pitch = feat_cap
+ *   sbm_train_rotate_device:  one source per base, feat_first = out_first, feat_pitch = feat_cap = out_cap
+ *   ragged images / a sweep's scales with irregular feat_first: one source each
+ * The reference demo's family is two sources of one class: the base, then its rotations.
+ * Kept: a pyramid whose status pair begins with 0.  Any other pyramid is skipped, which is no error: addTemplate returns
+ * -1 for it and adds nothing (line2Dup.cpp:1343).  The kept pyramids become templates 0, 1, ... in source order;
+ * template_id is the running count of kept pyramids of the pyramid's class_idx (line2Dup.cpp:1312);
+ * template_index_out[j] (host, may be NULL) is the template index of input pyramid j over all sources, -1 if skipped.
+ * Afterwards the context holds exactly what sbm_upload_templates leaves for the kept pyramids' level records, their
+ * features without theta and those class and id arrays -- every device table byte for byte, features packed tightly in
+ * template and level order -- and the same state changes apply (every class selected, graphs dropped).  Zero kept
+ * pyramids give an empty set.
+ * `sources` is a host array, read during the call only.  The kernels run on `stream` (NULL: the context's), behind the
+ * training calls that made the sources: no synchronisation is needed between training and this call.  The call waits
+ * for the device before it swaps the tables, as sbm_upload_templates does; it is not capturable.  Only the kept
+ * pyramids' level sizes, the kept flags and a verdict reach the host, never a feature.
+ * SBM_ERR_INVALID, the former template set untouched and still matchable, the message naming source, pyramid and level:
+ * a null argument; n_sources < 1; a negative n_pyramids, feat_first, feat_pitch or feat_cap; more than 2^31 / n_levels
+ * pyramids; a kept pyramid with a level whose n_features is outside 0 .. 8191 (CV_Error, line2Dup.cpp:1195, :1260) or
+ * whose [feature_offset, + n_features) leaves [0, feat_cap) -- the first such level in source order; otherwise 2^31 - 1
+ * features or more in total; otherwise a feature with x or y outside 0 .. 65535 or a label outside 0 .. 7 (CV_DbgAssert,
+ * line2Dup.cpp:788-789), the first in source order. */
+typedef struct sbm_template_source {  /* a run of trained pyramids in device memory (56 bytes) */
+    const void* d_levels;   /* n_pyramids * n_levels sbm_template_level, as a sbm_train_* call wrote them */
+    const void* d_feats;    /* the sbm_train_feature array the pyramids' blocks lie in */
+    const void* d_status;   /* n_pyramids status pairs of that call, or NULL: every pyramid is ok */
+    int32_t n_pyramids;
+    int32_t class_idx;      /* label of every pyramid of the run */
+    int64_t feat_first, feat_pitch, feat_cap; /* pyramid i's block: records [feat_first + i*feat_pitch, +feat_cap) */
+} sbm_template_source;
+
+int sbm_upload_templates_device(sbm_ctx* ctx, const sbm_template_source* sources, int32_t n_sources,
+                                int32_t* template_index_out, void* stream);
+
+/* The installed set in the input form of sbm_upload_templates, after either upload: levels_out [n_templates][n_levels]
+ * (width, height, n_features and a tightly packed feature_offset as the context holds them; tl_x = tl_y = 0, which the
+ * match path never reads; pyramid_level = the level), feats_out up to feat_cap records, class_idx_out and
+ * template_id_out n_templates each.  Any output may be NULL; n_templates / n_features are always written, so a call with
+ * NULL outputs queries the sizes.  SBM_ERR_CAPACITY when feats_out is given and feat_cap < n_features.  Waits for the
+ * device and copies; changes no state.  A parity-test accessor. */
+int sbm_get_templates(sbm_ctx* ctx, sbm_template_level* levels_out, sbm_feature* feats_out, int64_t feat_cap,
+                      int32_t* class_idx_out, int32_t* template_id_out, int32_t* n_templates, int64_t* n_features);
+/* One template table exactly as it lies in device memory.  which: 0 the level records {width, height, n_features,
+ * feature_offset} int32 per (template, level); 1 the features x | y << 16; 2 their labels (bytes); 3 their levels (bytes);
+ * 4 and 5 the copies of 1 and 2 sorted inside each (template, level) by (x / T) & 15 (stable); 6 the 17 uint16 class
+ * offsets of those per (template, level); 7 largest x | largest y << 16 per (template, level); 8 class_idx and 9
+ * template_id per template.  *bytes: the table's size; out_host may be NULL to ask for it alone.  Waits for the device
+ * and copies; changes no state.  SBM_ERR_CAPACITY when cap_bytes is too small.  A parity-test accessor. */
+int sbm_get_template_table(sbm_ctx* ctx, int32_t which, void* out_host, int64_t cap_bytes, int64_t* bytes);
+
 /* ---- measurement ---------------------------------------------------------
  * Per-kernel HIP-event timings of the last sbm_match/sbm_build_pyramid/
  * sbm_match_templates call when profiling was enabled (adds synchronisation;

@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_device_planes",
     "sbm_get_level_build",
     "sbm_get_level_stored",
+    "sbm_upload_templates_device", "sbm_get_templates", "sbm_get_template_table",
 ]
 
 # sbm_match_batch_device_ptrs flags: the caller promises that every frame pointer is a multiple of 4
@@ -113,6 +114,25 @@ class SbmRotateBase(C.Structure):
         ("out_first", C.c_int64),
         ("out_cap", C.c_int64),
     ]
+
+
+class SbmTemplateSource(C.Structure):
+    """sbm_template_source: a run of trained pyramids of one class in device memory (56 bytes)"""
+    _fields_ = [
+        ("d_levels", C.c_void_p),
+        ("d_feats", C.c_void_p),
+        ("d_status", C.c_void_p),
+        ("n_pyramids", C.c_int32),
+        ("class_idx", C.c_int32),
+        ("feat_first", C.c_int64),
+        ("feat_pitch", C.c_int64),
+        ("feat_cap", C.c_int64),
+    ]
+
+
+# sbm_get_template_table's tables, in its order, with the element type of each
+TEMPLATE_TABLES = (("tls", np.int32), ("fxy", np.uint32), ("flabel", np.uint8), ("flevel", np.uint8), ("fxy_s", np.uint32), ("flabel_s", np.uint8),
+                   ("fcls", np.uint16), ("fext", np.uint32), ("class", np.int32), ("tid", np.int32))
 
 
 class SbmError(RuntimeError):
@@ -294,6 +314,9 @@ def lib() -> C.CDLL:
     L.sbm_match_batch_device_banded.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, f32, vp, i64, vp, vp, i32, vp]
     L.sbm_nms_batch_device.argtypes = [vp, vp, vp, i64, i32, i32, i64, C.POINTER(SbmNmsParams), vp, i64, vp, vp]
     L.sbm_match_batch_host_end_nms.argtypes = [vp, C.POINTER(SbmNmsParams), vp, i64, vp]
+    L.sbm_upload_templates_device.argtypes = [vp, vp, i32, vp, vp]
+    L.sbm_get_templates.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(i32), C.POINTER(i64)]
+    L.sbm_get_template_table.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("sbm_last_error", "sbm_destroy", "sbm_canonicalize"):
@@ -366,6 +389,39 @@ class Context:
         ti = np.ascontiguousarray(ts.template_id, np.int32)
         _check(lib().sbm_upload_templates(self._h, ts.n_templates, _p(levels), _p(feats), len(feats), _p(ci), _p(ti)))
         self.n_templates = ts.n_templates
+
+    def upload_templates_device(self, sources: Sequence["SbmTemplateSource"], stream: int = 0) -> np.ndarray:
+        """sbm_upload_templates_device: the pyramids of `sources` (records of device addresses, read during the call only), as the
+        sbm_train_*_device calls enqueued before on `stream` leave them, become the template set; a pyramid whose status pair
+        does not begin with 0 is skipped.  Returns the template index of every input pyramid, -1 for a skipped one."""
+        arr = (SbmTemplateSource * max(len(sources), 1))(*sources)
+        n = sum(max(int(s.n_pyramids), 0) for s in sources)
+        index = np.full(max(n, 1), -1, np.int32)
+        _check(lib().sbm_upload_templates_device(self._h, arr, len(sources), _p(index), C.c_void_p(stream) if stream else None))
+        index = index[:n]
+        self.n_templates = int((index >= 0).sum())
+        return index
+
+    def get_templates(self) -> TemplateSet:
+        """the installed set in the input form of upload_templates, after either upload (sbm_get_templates)"""
+        nt, nf = C.c_int32(0), C.c_int64(0)
+        _check(lib().sbm_get_templates(self._h, None, None, 0, None, None, C.byref(nt), C.byref(nf)))
+        levels = np.zeros((nt.value, self.n_levels), LEVEL_DTYPE)
+        feats = np.zeros(nf.value, FEATURE_DTYPE)
+        ci, ti = np.zeros(nt.value, np.int32), np.zeros(nt.value, np.int32)
+        _check(lib().sbm_get_templates(self._h, _p(levels), _p(feats), len(feats), _p(ci), _p(ti), C.byref(nt), C.byref(nf)))
+        return TemplateSet(self.n_levels, levels, feats, ci, ti)
+
+    def get_template_table(self, which) -> np.ndarray:
+        """one of the ten template tables exactly as it lies in device memory (sbm_get_template_table): `which` is its number
+        or its name in TEMPLATE_TABLES"""
+        if isinstance(which, str):
+            which = [name for name, _ in TEMPLATE_TABLES].index(which)
+        n = C.c_int64(0)
+        _check(lib().sbm_get_template_table(self._h, which, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        _check(lib().sbm_get_template_table(self._h, which, _p(out), out.nbytes, C.byref(n)))
+        return out.view(TEMPLATE_TABLES[which][1])
 
     def select_classes(self, class_idx: Sequence[int]):
         a = np.asarray(list(class_idx), np.int32)

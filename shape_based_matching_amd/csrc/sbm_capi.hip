@@ -27,6 +27,7 @@
 #include "sbm_train_kernels.h"
 #include "sbm_rotate_kernels.h"
 #include "sbm_nms_kernels.h"
+#include "sbm_install_kernels.h"
 
 using namespace sbm;
 
@@ -37,3 +38,4 @@ using namespace sbm;
 #include "sbm_capi_multi.inc"   // RCCL, sharded / banded steps, sbm_match_sharded
 #include "sbm_capi_nms.inc"     // match epilogue + NMS on the device
 #include "sbm_capi_train.inc"   // batched template training on the device
+#include "sbm_capi_install.inc" // device-trained families as the template set

@@ -53,6 +53,11 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+    void swap(DevBuf& o)
+    {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
     template <class T>
     T* as() const { return (T*)p; }
 };
@@ -183,6 +188,15 @@ struct sbm_ctx {
     DevBuf d_fxy_s, d_flabel_s, d_fcls; // refinement pass on the strip plane: features sorted by (x / T) & 15 per template level + 17 class offsets
     bool have_thr = false;
     float thr_cached = 0.f;
+    // sbm_upload_templates_device (sbm_capi_install.inc): the ten tables above are built in this second set and change places
+    // with the live ones once the kernels' verdict is in, so a refused call leaves the live set as it was; d_install is the
+    // call's scratch (sbm_install_plan.h).  h_fxy is then not filled: features_in_bounds is its only reader, and it fetches
+    // d_fxy on first need (ensure_host_fxy).
+    struct TemplateTables {
+        DevBuf tls, fxy, flabel, flevel, fxy_s, flabel_s, fcls, fext, cls, tid;
+    } staged;
+    DevBuf d_install;
+    bool h_fxy_valid = true;
 
     // pyramid
     int rows[SBM_MAX_LEVELS]{}, cols[SBM_MAX_LEVELS]{};
@@ -1467,7 +1481,20 @@ int host_template_npos(const DevTL& tl, int T, int W, int H)
     return (H - hf) * W + (W - wf) + 1;
 }
 
-// features of a template level that lie inside a rows x cols level: the ones its coarse pass adds
+// h_fxy after an upload that left the features on the device: one copy of d_fxy, at the first call that counts features on
+// the host (sbm_partition_templates, sbm_coarse_bytes).  The upload ended with a device-wide wait, so d_fxy is complete.
+int ensure_host_fxy(sbm_ctx* c)
+{
+    if (c->h_fxy_valid) return 0;
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    std::vector<uint32_t> fxy((size_t)c->n_features);
+    if (!fxy.empty()) HIP_TRY(hipMemcpy(fxy.data(), c->d_fxy.p, fxy.size() * 4, hipMemcpyDeviceToHost));
+    c->h_fxy.swap(fxy);
+    c->h_fxy_valid = true;
+    return 0;
+}
+
+// features of a template level that lie inside a rows x cols level: the ones its coarse pass adds (after ensure_host_fxy)
 int64_t features_in_bounds(const sbm_ctx* c, const DevTL& tl, int rows, int cols)
 {
     int64_t n = 0;
@@ -2055,6 +2082,41 @@ void collect_timings(sbm_ctx* c)
 }
 
 bool feature_in_bounds(const sbm_feature& f) { return f.x >= 0 && f.y >= 0 && f.x <= 65535 && f.y <= 65535 && f.label >= 0 && f.label < 8; }
+
+// The step both template uploads end with, after the device-wide wait: the new set becomes the context's.  sbm_upload_templates
+// has written the live device tables in place (staged false); sbm_upload_templates_device has built them in c->staged, which
+// changes places with the live set here.  fxy_valid false: h_fxy is fetched from d_fxy on first need.  Then what follows from
+// new templates: thresholds, feature offsets and the NMS label table are stale, captured graphs hold the old tables and grid
+// sizes, every class is selected.
+struct TemplateCommit {
+    int32_t n_templates = 0;
+    int64_t n_features = 0;
+    std::vector<DevTL> tls;
+    std::vector<uint32_t> fxy;
+    std::vector<int32_t> cls, tid;
+    bool fxy_valid = true, staged = false;
+};
+int commit_templates(sbm_ctx* c, TemplateCommit& k)
+{
+    if (k.staged) {
+        sbm_ctx::TemplateTables& st = c->staged;
+        c->d_tls.swap(st.tls), c->d_fxy.swap(st.fxy), c->d_flabel.swap(st.flabel), c->d_flevel.swap(st.flevel);
+        c->d_fxy_s.swap(st.fxy_s), c->d_flabel_s.swap(st.flabel_s), c->d_fcls.swap(st.fcls), c->d_fext.swap(st.fext);
+        c->d_class.swap(st.cls), c->d_tid.swap(st.tid);
+    }
+    c->n_templates = k.n_templates;
+    c->n_features = k.n_features;
+    c->h_tls.swap(k.tls);
+    c->h_fxy.swap(k.fxy);
+    c->h_fxy_valid = k.fxy_valid;
+    c->h_class.swap(k.cls);
+    c->h_tid.swap(k.tid);
+    c->have_thr = false;
+    c->foff_dirty = true;
+    ++c->templates_gen;
+    c->drop_graphs();
+    return sbm_select_classes(c, nullptr, 0);
+}
 
 } // namespace
 

@@ -176,17 +176,14 @@ int sbm_upload_templates(sbm_ctx* c, int32_t n_templates, const sbm_template_lev
         HIP_TRY(hipMemcpy(c->d_class.p, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c->d_tid.p, tid.data(), tid.size() * 4, hipMemcpyHostToDevice));
     }
-    c->n_templates = n_templates;
-    c->n_features = n_features;
-    c->h_tls.swap(tls);
-    c->h_fxy.swap(fxy);
-    c->h_class.swap(cls);
-    c->h_tid.swap(tid);
-    c->have_thr = false;
-    c->foff_dirty = true;
-    ++c->templates_gen;
-    c->drop_graphs();
-    return sbm_select_classes(c, nullptr, 0);
+    TemplateCommit k;
+    k.n_templates = n_templates;
+    k.n_features = n_features;
+    k.tls.swap(tls);
+    k.fxy.swap(fxy);
+    k.cls.swap(cls);
+    k.tid.swap(tid);
+    return commit_templates(c, k); // (sbm_capi_ctx.inc: the step shared with sbm_upload_templates_device)
 }
 
 static int set_active(sbm_ctx* c, std::vector<int32_t>& act)
@@ -239,6 +236,7 @@ int sbm_partition_templates(sbm_ctx* c, int32_t rows, int32_t cols, const int32_
     }
     const int L = c->L, lc = L - 1, T = c->cfg.T[lc];
     const int rl = rows >> lc, cl = cols >> lc, W = cl / T, H = rl / T;
+    if (int e = ensure_host_fxy(c)) return e; // (a device install leaves the features on the device)
     // work of a template = byte-adds of its coarse pass (in-bounds features x template_positions, line2Dup.cpp:818-837);
     // at least 1 so that templates without work still spread out
     std::vector<double> cum(list.size() + 1, 0.0);
