@@ -460,6 +460,14 @@ int sbm_get_refine_form(sbm_ctx* ctx, int32_t level, int32_t out[6]);
  * and whose width is a multiple of 64 (SBM_SOURCE_LINES=0 in the environment: never).  A call replayed from a captured graph
  * reports the form it was captured with.  Reads a host-side record, like sbm_get_coarse_form.  A parity-test accessor. */
 int sbm_get_source_form(sbm_ctx* ctx, int32_t* out);
+/* out = {calls whose source pass stored the retained copy of level 0's source, calls whose source pass left it unwritten}, over
+ * the life of the context.  A call of the sparse level-0 path on frames a fixed number of bytes apart stores the copy only while
+ * no later match call is enqueued on the context behind it: the copy's readers -- sbm_get_quantized*, sbm_set_quantized(0),
+ * the stage entry points and the template loop on the resident pyramid -- see the last call's state, and wait for that call.
+ * The call's frames must stay valid until its work is done.  Calls on a table of frame or plane pointers, and every call with
+ * SBM_RETAIN_ALWAYS=1 in the environment, always store it; a call that builds level 0's map whole counts in neither.  The
+ * totals are device counters: the getter waits for the device.  A parity-test accessor. */
+int sbm_get_source_retention(sbm_ctx* ctx, int32_t out[2]);
 /* The sparse level-0 gradient launch of the last call of this context: out = {selection, working, launched}.  selection: 0 the
  * call made no such launch (level 0's map was built whole, or no call yet), 1 its work items were chosen by the refinement-tile
  * flags on the fixed strip grid, 2 by the record of need rectangles (per band of 8 pixel rows the hull of the map columns some

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "sbm_match_batch_device_masked", "sbm_match_batch_host_begin_masked", "sbm_match_batch_host_masked", "sbm_get_quantized_frame",
     "sbm_get_coarse_form",
     "sbm_get_source_form",
+    "sbm_get_source_retention",
     "sbm_get_refine_form",
     "sbm_get_sparse_items",
     "sbm_get_sparse_list",
@@ -258,6 +259,7 @@ def lib() -> C.CDLL:
     L.sbm_get_coarse_bitplanes.argtypes = [vp, i32, vp, i64]
     L.sbm_get_coarse_form.argtypes = [vp, vp]
     L.sbm_get_source_form.argtypes = [vp, vp]
+    L.sbm_get_source_retention.argtypes = [vp, vp]
     L.sbm_get_sparse_items.argtypes = [vp, vp]
     L.sbm_get_sparse_list.argtypes = [vp, vp]
     L.sbm_get_refine_form.argtypes = [vp, i32, vp]
@@ -976,6 +978,13 @@ class Context:
         out = C.c_int32(0)
         _check(lib().sbm_get_source_form(self._h, C.byref(out)))
         return int(out.value)
+
+    def source_retention(self) -> Tuple[int, int]:
+        """(retained, skipped): the calls of this context whose source pass stored the retained copy of level 0's source, and
+        those whose source pass left it unwritten because a later call was already enqueued behind them; waits for the device"""
+        out = np.zeros(2, np.int32)
+        _check(lib().sbm_get_source_retention(self._h, _p(out)))
+        return tuple(int(v) for v in out)
 
     def sparse_items(self) -> Tuple[int, int, int]:
         """(selection, working, launched) of the last call's sparse level-0 gradient launch: selection 0 none, 1 by tile flags,

@@ -116,6 +116,9 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
 //   SBM_SOURCE_LINES=0        the source pass always in its strided form (QS_SOURCE), never as k_source_lines (sbm_source_lines.h), which
 //                             otherwise runs wherever the caller's layout admits it (source_lines_ok): the A/B knob of the two forms
+//   SBM_RETAIN_ALWAYS=1       every call of the sparse level-0 path stores the retained copy of its source and runs its sparse gradient
+//                             launch on that copy, instead of storing it only while no later call is enqueued behind it and reading
+//                             the caller's frames (DESIGN.md section 5): the A/B knob
 struct Tuning {
     int coarse = 0, quantize = 0, hs0 = 0, hs1 = 0, local_grid = 0, local_waves = 0, local_order = -1;
     bool qs_pack = true, full_lm = false, strip_lm = true, graph_fork = true, fused_bits = true, lm_allty = true;
@@ -124,6 +127,7 @@ struct Tuning {
     int src_hs = 0;
     bool sparse_list = true;
     int sparse_slots = 0;
+    bool retain_always = false;
 };
 static const Tuning& tuning()
 {
@@ -159,6 +163,7 @@ static const Tuning& tuning()
         k.sparse_slots = std::max(0, num("SBM_SPARSE_SLOTS", 0));
         k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
         k.source_lines = num("SBM_SOURCE_LINES", 1) != 0;
+        k.retain_always = num("SBM_RETAIN_ALWAYS", 0) != 0;
         k.match_bands = std::min(8, std::max(0, num("SBM_MATCH_BANDS", 0)));
         k.bits_dw = num("SBM_BITS_DW", 0) == 2 ? 2 : (num("SBM_BITS_DW", 0) == 1 ? 1 : 0);
         return k;
@@ -241,6 +246,20 @@ struct sbm_ctx {
     bool sparse_items_pending = false;   // the count is still on the device
     int src0_ch = 0;
     bool map0_whole = true;
+    // ... and that copy is stored by the last match call enqueued on the context only (section 5 of DESIGN.md has the argument).
+    // h_enqueued: a word of pinned host memory that one thread per launch reads in place (d_enqueued: its device address) --
+    // match calls whose enqueue has ended (call_enqueued); d_call: CALL_WORDS words of device memory (sbm_lm_kernels.h) -- calls
+    // executed, that count as last read, the source pass's note, the totals of sbm_get_source_retention.  call_counted: the launches of the call being enqueued
+    // hold the one that counts it.  ev_call: recorded behind the last match call enqueued, on its stream (ensure_level0_map waits
+    // for it); call_recorded: it was -- else that reader waits for the device.
+    // sparse_src: the frames the call's sparse gradient launch reads -- the caller's own, or the retained copy.
+    uint32_t* h_enqueued = nullptr;
+    uint32_t* d_enqueued = nullptr;
+    DevBuf d_call;
+    bool call_counted = false;
+    hipEvent_t ev_call = nullptr;
+    bool call_recorded = false;
+    FrameSource sparse_src;
     // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
     // (sbm_level_forms.h; per level, not per frame: the forms rebuilt on demand cover frame 0 only)
     LevelForms forms[SBM_MAX_LEVELS];
@@ -673,6 +692,10 @@ struct QSForm {
     const int32_t* item_list = nullptr;
     int64_t list_stride = 0;
     int list_cap = 0, slots = 0, list_hs = 0, list_n_full = 0;
+    // QS_SOURCE: the call counters the work items decide by whether they store the copy, and where the decision is noted (QSArgs)
+    const uint32_t* call_enqueued = nullptr;
+    const uint32_t* call_executed = nullptr;
+    uint32_t* call_note = nullptr;
 };
 
 // rows per work item of the source pass: its items run hs + 3 row iterations, in whole groups of 6
@@ -748,6 +771,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
         a.frames = frames;
         a.keep = form->keep;
         a.keep_fs = form->keep_fs;
+        a.call_enqueued = form->call_enqueued, a.call_executed = form->call_executed, a.call_note = form->call_note;
         const dim3 g((unsigned)((sl_items(cols, a.n_rblocks, frames) + 3) / 4));
         if (table && ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines_ptrs<1>), g, dim3(256), 0, s, a);
         else if (table) SBM_LAUNCH(c, "k_quantize", (k_source_lines_ptrs<3>), g, dim3(256), 0, s, a);
@@ -784,6 +808,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
         if (stage == QS_SOURCE) {
             a.keep = form->keep;
             a.keep_fs = form->keep_fs;
+            a.call_enqueued = form->call_enqueued, a.call_executed = form->call_executed, a.call_note = form->call_note;
         } else if (stage == QS_SPARSE) {
             a.pyr = nullptr;
             a.tile_flags = form->tile_flags;
@@ -1123,6 +1148,20 @@ int check_bands(const sbm_ctx* c, int n_bands)
 FrameSource level_frames(const sbm_ctx* c, int l, int frames) { return packed_frames(c->d_img[l].p, c->rows[l], c->cols[l], c->channels, frames); }
 FrameSource retained_frames(const sbm_ctx* c, int ch, int frames) { return packed_frames(c->d_src0.p, c->rows[0], c->cols[0], ch, frames); }
 
+// The frames the sparse gradient launch of a call on `src` reads.  The caller's own where they are a fixed number of bytes apart
+// and the streaming kernel takes their layout (it read callers' layouts, padded rows and frames included, before there was a
+// sparse path): they stay valid until the call's work is done, and the call's source pass may then leave the retained copy
+// unwritten (source_pass_retains).  Frames behind a table, a layout the kernel refuses and SBM_RETAIN_ALWAYS=1: the retained
+// copy, which the source pass of such a call always stores.
+FrameSource sparse_gradient_frames(const sbm_ctx* c, const FrameSource& src)
+{
+    const FrameSource kept = retained_frames(c, src.ch, src.frames);
+    if (tuning().retain_always || src.kind != FRAMES_STRIDED || !src.base) return kept;
+    if (!quantize_stream_rows(c, c->rows[0], c->cols[0], src, MaskSource{}, false)) return kept;
+    return src;
+}
+bool reads_retained(const sbm_ctx* c, const FrameSource& sparse_src) { return sparse_src.base == c->d_src0.p; }
+
 // A call's cursor down the pyramid: the caller's frames and masks at level 0, the context's own from level 1 on
 struct PyramidCursor {
     FrameSource src;
@@ -1237,6 +1276,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
     c->sparse_list[0] = c->sparse_list[1] = 0;
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
+    c->call_counted = false;
     // A match entry point (it passes reset_count and has set the threshold already) whose coarse pass will run on bit planes
     // builds the coarsest level as bit planes ONLY, inside the one linear-memory launch, and its T = 4 strip levels as bit strips.
     // The stage entry points keep the 8 response planes there (the bit planes are then packed from them on demand).
@@ -1263,7 +1303,15 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
             }
             if (l == 0 && plan.sparse_gradient) {
                 // the source pass: level 1's image and the retained copy; the map waits for the coarse candidates (enqueue_sparse_strips)
-                const QSForm form{QS_SOURCE, c->d_src0.as<uint8_t>(), (int64_t)c->rows[0] * c->cols[0] * c->channels, nullptr, 0, 0, 0, 0};
+                QSForm form{QS_SOURCE, c->d_src0.as<uint8_t>(), (int64_t)c->rows[0] * c->cols[0] * c->channels, nullptr, 0, 0, 0, 0};
+                // The copy is stored while no later call is enqueued behind this one -- where this call's own sparse launch reads
+                // the caller's frames.  Where it reads the copy, the counters it is given are the word that is always 0.
+                c->sparse_src = sparse_gradient_frames(c, src0);
+                uint32_t* const w = c->d_call.as<uint32_t>();
+                const bool follows = !reads_retained(c, c->sparse_src) && c->d_enqueued;
+                form.call_enqueued = follows ? w + CALL_SEEN : w + CALL_ZERO; // (the host's count as a launch before this one read it)
+                form.call_executed = follows ? w + CALL_EXECUTED : w + CALL_ZERO;
+                form.call_note = w + CALL_NOTE;
                 QuantizeLaunch q;
                 q.src = src0;
                 q.rows = c->rows[0], q.cols = c->cols[0];
@@ -1299,6 +1347,9 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
             a.counters = c->d_counters.as<int32_t>();
             a.out_count = reset_count;
             c->counters_fresh = true;
+            a.call_words = c->d_call.as<uint32_t>(); // a match call: counted where its counters are reset (enqueue_match)
+            a.call_enqueued = c->d_enqueued;         // (null: nothing is read, every call keeps its copy)
+            c->call_counted = true;
             if (plan.form[0] == LM_BIT_STRIPS_SPARSE) {
                 a.clear_tiles = c->d_tiles.as<uint8_t>();
                 a.n_tiles = refine_tile_count(c->cols[0] / c->cfg.T[0], c->rows[0] / c->cfg.T[0]);
@@ -1339,6 +1390,14 @@ int ensure_level0_map(sbm_ctx* c, hipStream_t s)
     if (c->map0_whole || c->levels_valid < 1) return 0;
     const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
     if (!c->d_src0.p || (size_t)c->last_frames * rows * cols * ch > c->d_src0.cap) return fail(SBM_ERR_STATE, "level 0's source is not retained");
+    // The copy this reads is the one of the last match call enqueued, which stores it unless a later call is enqueued before its
+    // source pass runs (source_pass_retains).  Wait for that call here: it then ran as the last one enqueued and has stored its
+    // copy, whatever the host enqueues behind this reader.  The context's own event stands for the call: the caller's stream may
+    // be gone by now.
+    if (!c->call_recorded || hipEventSynchronize(c->ev_call) != hipSuccess) {
+        (void)hipGetLastError();
+        HIP_TRY(hipDeviceSynchronize());
+    }
     QuantizeLaunch q;
     q.src = retained_frames(c, ch, c->last_frames);
     q.rows = rows, q.cols = cols;
@@ -1718,11 +1777,10 @@ struct SparseListPlan {
     int slots = 0, hs = 0, n_full = 0, n_rblocks = 0;
 };
 constexpr int SPARSE_SLOTS_DEFAULT = INT_MAX; // the items per frame (profiles/sparse_list.txt, section 5)
-SparseListPlan sparse_list_plan(const sbm_ctx* c, int frames, int ch)
+SparseListPlan sparse_list_plan(const sbm_ctx* c, const FrameSource& src)
 {
     SparseListPlan p;
     if (!tuning().sparse_list || !c->d_items.p || !c->d_rects.p || !c->d_src0.p) return p;
-    const FrameSource src = retained_frames(c, ch, frames);
     const int rows = c->rows[0], cols = c->cols[0];
     const int hs = quantize_stream_rows(c, rows, cols, src, MaskSource{}, false);
     if (!hs) return p;
@@ -1741,7 +1799,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     // the record of need rectangles only where this call's gradient launch reads it (the flags alone serve the strip builder)
     int32_t* const rects = !c->map0_whole && tuning().sparse_rects ? c->d_rects.as<int32_t>() : nullptr;
     // ... and the lists of working items where that launch runs from them
-    const SparseListPlan lp = rects ? sparse_list_plan(c, frames, c->src0_ch) : SparseListPlan{};
+    const SparseListPlan lp = rects ? sparse_list_plan(c, c->sparse_src) : SparseListPlan{};
     MarkList ml;
     memset(&ml, 0, sizeof ml);
     if (lp.slots > 0) {
@@ -1770,7 +1828,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
             form.item_count = c->d_sparse_items.as<int32_t>();
         }
         QuantizeLaunch q;
-        q.src = retained_frames(c, c->src0_ch, frames);
+        q.src = c->sparse_src; // the caller's frames, or the retained copy (sparse_gradient_frames)
         q.rows = c->rows[0], q.cols = c->cols[0];
         q.weak = c->cfg.weak_threshold;
         q.out = c->d_quant[0].as<uint8_t>();
@@ -1785,6 +1843,9 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     if (blocks != n_tiles) return fail(SBM_ERR_STATE, "level 0: %d strip workgroups for %d refinement tiles", blocks, n_tiles);
     a.tile_flags = c->d_tiles.as<uint8_t>();
     a.n_tiles = n_tiles;
+    // the last launch but one of a sparse call: where the host's count of calls enqueued is read for the NEXT call's source pass
+    a.call_words = c->d_call.as<uint32_t>();
+    a.call_enqueued = c->d_enqueued;
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
     c->note_level_build(0, LM_BIT_STRIPS_SPARSE, 1, a.lv[0].split, a.lv[0].allty);
@@ -1960,10 +2021,33 @@ void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch,
     if (sparse_grad) c->src0_ch = c->channels;
 }
 
+// A match call is counted on the device by one thread of one of its launches, behind its source pass (CALL_EXECUTED,
+// sbm_lm_kernels.h): by the clearing block of the one-launch builder where the call has one, else by a launch of its own here.
+// The host counts the call once its enqueue has ended (call_enqueued).
+int enqueue_call_executed(sbm_ctx* c, hipStream_t s)
+{
+    if (c->call_counted) return 0;
+    hipLaunchKernelGGL(k_call_executed, dim3(1), dim3(64), 0, s, c->d_call.as<uint32_t>(), (const uint32_t*)c->d_enqueued); // (no timing of its own)
+    HIP_TRY(hipGetLastError());
+    c->call_counted = true;
+    return 0;
+}
+
+// The enqueue of a match call on stream s has ended, as plain launches or as the replay of its graph: the source pass of every
+// call before it that has not run yet may now leave the retained copy unwritten.  The release orders the store behind everything
+// the host wrote for this call.
+void call_enqueued(sbm_ctx* c, hipStream_t s)
+{
+    c->call_recorded = c->ev_call && hipEventRecord(c->ev_call, s) == hipSuccess;
+    if (!c->call_recorded) (void)hipGetLastError();
+    if (c->h_enqueued) __atomic_store_n(c->h_enqueued, *c->h_enqueued + 1, __ATOMIC_RELEASE); // (the host alone writes the word)
+}
+
 // every launch of a match call, in order
 int enqueue_match(sbm_ctx* c, hipStream_t s, const MatchCall& m, const Bands* bands = nullptr, bool level0_gradient_done = false)
 {
     if (int e = enqueue_pyramid(c, s, m.src, m.mask, m.counts, bands, level0_gradient_done)) return e;
+    if (int e = enqueue_call_executed(c, s)) return e;
     return enqueue_loop(c, s, m.out, m.cap, m.counts, m.src.frames, false);
 }
 
@@ -1988,6 +2072,8 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
     }
     record_build(c->forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
     c->map0_whole = true;
+    c->call_counted = false;
+    if (int e = enqueue_call_executed(c, st)) return e;
     if (int e = enqueue_coarse(c, st, m.out, m.cap, m.counts)) return e;
     if (forked && (hipEventRecord(c->ev_join, sd) != hipSuccess || hipStreamWaitEvent(st, c->ev_join, 0) != hipSuccess))
         return fail(SBM_ERR_HIP, "graph join failed");
@@ -2010,7 +2096,7 @@ GraphKey graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
     key.sparse_grad = kind > 0 && plans_sparse_gradient(c, m.src, m.mask, nullptr, false);
     key.sparse_rects = key.sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
-    key.sparse_slots = key.sparse_rects ? sparse_list_plan(c, m.src.frames, m.src.ch).slots : 0;
+    key.sparse_slots = key.sparse_rects ? sparse_list_plan(c, sparse_gradient_frames(c, m.src)).slots : 0;
     return key;
 }
 
@@ -2047,11 +2133,15 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             if (kind >= 0) {
                 record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects, key.sparse_slots);
                 c->last_frames = m.src.frames;
+                call_enqueued(c, s); // (the graph holds the launch that counts the call on the device)
             }
             return 0;
         }
     }
-    return kind < 0 ? enqueue_templates(c, s, m.thr, m.out, m.cap, m.counts) : enqueue_match(c, s, m);
+    if (kind < 0) return enqueue_templates(c, s, m.thr, m.out, m.cap, m.counts);
+    if (int e = enqueue_match(c, s, m)) return e;
+    call_enqueued(c, s);
+    return 0;
 }
 
 int fetch_results(sbm_ctx* c, hipStream_t s, sbm_match_rec* out_host, int64_t cap, int64_t* n_out)

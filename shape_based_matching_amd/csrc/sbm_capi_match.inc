@@ -32,7 +32,8 @@ int sbm_create(const sbm_config* cfg, sbm_ctx** out)
         return fail(SBM_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
     }
     if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming) != hipSuccess) {
         sbm_destroy(c);
         return fail(SBM_ERR_HIP, "stream/event creation failed");
     }
@@ -43,10 +44,19 @@ int sbm_create(const sbm_config* cfg, sbm_ctx** out)
         }
     int rc = 0;
     if ((rc = c->d_cands.ensure((size_t)c->cand_cap * sizeof(Cand))) || (rc = c->d_counters.ensure(CTR_STRIDE * sizeof(int32_t) + 256, true)) ||
-        (rc = c->d_out.ensure((size_t)c->cand_cap * sizeof(sbm_match_rec))) || (rc = c->d_outcount.ensure(16, true))) {
+        (rc = c->d_out.ensure((size_t)c->cand_cap * sizeof(sbm_match_rec))) || (rc = c->d_outcount.ensure(16, true)) ||
+        (rc = c->d_call.ensure(CALL_WORDS * sizeof(uint32_t), true))) {
         sbm_destroy(c);
         return rc;
     }
+    // the count of match calls enqueued: host memory one thread per launch reads in place.  Without it every call keeps its copy.
+    if (hipHostMalloc((void**)&c->h_enqueued, 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
+        *c->h_enqueued = 0;
+        if (hipHostGetDevicePointer((void**)&c->d_enqueued, c->h_enqueued, 0) != hipSuccess) c->d_enqueued = nullptr;
+    } else {
+        c->h_enqueued = nullptr;
+    }
+    (void)hipGetLastError();
     *out = c;
     return 0;
 }
@@ -71,11 +81,13 @@ void sbm_destroy(sbm_ctx* c)
     if (c->h_res_count) (void)hipHostFree(c->h_res_count);
     if (c->h_nms_counts) (void)hipHostFree(c->h_nms_counts);
     if (c->h_train_table) (void)hipHostFree(c->h_train_table);
+    if (c->h_enqueued) (void)hipHostFree(c->h_enqueued);
     if (c->ev_train_table) (void)hipEventDestroy(c->ev_train_table);
     c->drop_graphs();
     for (int l = 0; l < SBM_MAX_LEVELS; ++l)
         if (c->ev_fork[l]) (void)hipEventDestroy(c->ev_fork[l]);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    if (c->ev_call) (void)hipEventDestroy(c->ev_call);
     if (c->side) (void)hipStreamDestroy(c->side);
     c->clear_timings();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -527,6 +539,7 @@ static int host_batch_begin(sbm_ctx* c, const uint8_t* const* frames, int32_t n_
         m.src.frames = nf;
         mirror.to((sbm_match_rec*)c->h_bout + (size_t)f0 * cap, h_counts + 2 * f0);
         rc = enqueue_match(c, c->stream, m);
+        if (!rc) call_enqueued(c, c->stream);
         if (!rc && hipEventRecord(c->ev_free[buf], c->stream) != hipSuccess) rc = fail(SBM_ERR_HIP, "event record failed");
     }
     if (rc) {
@@ -721,6 +734,7 @@ int sbm_match(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols, int32_
             mirror.to(c->h_res, c->h_res_count);
         }
         if (int e = enqueue_match(c, c->stream, m, nullptr, l0_done)) return e;
+        call_enqueued(c, c->stream);
     }
     if (own_mirror) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -870,6 +884,17 @@ int sbm_get_source_form(sbm_ctx* c, int32_t* out)
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
     *out = c->source_form;
+    return 0;
+}
+
+int sbm_get_source_retention(sbm_ctx* c, int32_t out[2])
+{
+    if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->cfg.device_id));
+    HIP_TRY(hipDeviceSynchronize()); // the totals are the device's: every call enqueued has been counted
+    uint32_t w[CALL_WORDS];
+    HIP_TRY(hipMemcpy(w, c->d_call.p, sizeof w, hipMemcpyDeviceToHost));
+    out[0] = (int32_t)w[CALL_RETAINED], out[1] = (int32_t)w[CALL_SKIPPED];
     return 0;
 }
 

@@ -205,6 +205,7 @@ extern "C" int sbm_match_batch_device_banded(sbm_ctx* c, const void* d_imgs, int
     if (int e = begin_match(c, stream, m, &s, &b)) return e;
     // a result mirror set on the context would be written by the last kernel; the gathered mirror below replaces it
     if (int e = enqueue_match(c, s, m, &b)) return e;
+    call_enqueued(c, s);
     // the second exchange of the step: the per-rank match lists
     return gather_shards(c, s, d_local, bytes, d_gathered, gathered_mirror);
 }

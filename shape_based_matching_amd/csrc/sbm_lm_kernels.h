@@ -424,7 +424,43 @@ struct LmArgs {
     // until k_mark_refine_tiles writes one
     int32_t* clear_items;
     int64_t items_stride;
+    // call_words (may be null): the context's CALL_WORDS words.  One thread of the launch counts the call there where the launch
+    // also resets the counters (call_executed), and notes there how many calls the host has enqueued (call_observe) where
+    // call_enqueued, the host's word, is given
+    uint32_t* call_words;
+    const uint32_t* call_enqueued;
 };
+
+// The words of device memory by which a context's match calls are counted (the retained copy of level 0's
+// source is kept for the last call enqueued only).  One thread of one launch per call, behind the call's source pass, adds 1 to
+// CALL_EXECUTED -- what the source pass of the NEXT call compares with CALL_SEEN -- and moves the note that this call's source
+// pass left into the two totals sbm_get_source_retention reads.  CALL_SEEN is the host's count of calls enqueued as one thread
+// last read it: the host's word lies in host memory, and ONE read of it per launch is all a launch can afford (2048 waves
+// reading it made the headline step 3x as long, profiles/source_retention.txt).  It is read behind the source pass of every
+// call and again by the call's sparse strip builder, so what the next call's source pass sees is one or two launches old: a
+// stale low value only keeps a copy that nobody reads.  CALL_ZERO is never written: a source pass given its address for both
+// counters always keeps its copy.
+enum CallWord : int { CALL_EXECUTED = 0, CALL_NOTE = 1, CALL_RETAINED = 2, CALL_SKIPPED = 3, CALL_ZERO = 4, CALL_SEEN = 5, CALL_WORDS = 8 };
+__device__ __forceinline__ void call_executed(uint32_t* w)
+{
+    const uint32_t note = w[CALL_NOTE];
+    if (note == 1) w[CALL_RETAINED] += 1;
+    if (note == 2) w[CALL_SKIPPED] += 1;
+    w[CALL_NOTE] = 0;
+    atomicAdd(&w[CALL_EXECUTED], 1u);
+}
+__device__ __forceinline__ void call_observe(uint32_t* w, const uint32_t* host_enqueued)
+{
+    const uint32_t n = __hip_atomic_load(host_enqueued, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&w[CALL_SEEN], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ... for the calls whose launches have no clearing block of k_build_lm_rows.  host_enqueued may be null.
+__global__ void k_call_executed(uint32_t* w, const uint32_t* host_enqueued)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    call_executed(w);
+    if (host_enqueued) call_observe(w, host_enqueued);
+}
 
 __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
 {
@@ -439,6 +475,10 @@ __global__ __launch_bounds__(256) void k_build_lm_rows(const LmArgs a)
         if (a.clear_rects)
             for (int i = threadIdx.x; i < 2 * a.n_bands; i += 256) a.clear_rects[frame * a.n_bands * 2 + i] = (i & 1) ? 0 : 0x7fffffff;
         if (a.clear_items && threadIdx.x == 0) a.clear_items[frame * a.items_stride] = RT_LIST_NONE;
+    }
+    if (a.call_words && blockIdx.x == 0 && frame == 0 && threadIdx.x == 0) {
+        if (a.counters) call_executed(a.call_words);
+        if (a.call_enqueued) call_observe(a.call_words, a.call_enqueued);
     }
     // the level whose block range holds this block (the host orders the ranges heaviest blocks first)
     int l = 0, lb = -1;

@@ -57,6 +57,7 @@
 #endif
 #include SBM_WAVE_HEADER
 #include "sbm_refine_tiles.h"
+#include "sbm_source_lines_plan.h"
 
 #ifdef SBM_WAVE_EMU
 // the streamed stores of the source pass in terms of the emulation's plain ones (the cache hint has no meaning on the CPU)
@@ -70,6 +71,8 @@ inline void buf_store_u32x3_nt(const Buf& b, const V& voff, uint32_t soff, const
     buf_store_u32(b, voff, soff + 4, v1);
     buf_store_u32(b, voff, soff + 8, v2);
 }
+// (a word the host may have written is a word of memory)
+inline uint32_t load_word_system(const uint32_t* p) { return *p; }
 } // namespace wv
 #endif
 
@@ -123,7 +126,28 @@ struct QSArgs {
     int64_t list_stride;
     int32_t list_cap;         // entries a frame's list has room for: a larger count is cut to it
     int32_t slots;
+    // QS_SOURCE (and k_source_lines): the two call counters that decide whether a work item stores its rows of the retained copy
+    // (source_pass_retains, sbm_source_lines_plan.h) -- two words of device memory: the host's count of calls enqueued as an
+    // earlier launch last read it from host memory, and the calls executed (sbm_lm_kernels.h, CallWord).  The addresses never
+    // change, the values are data: a replayed graph follows them.  Null: the copy is always stored.  call_note (may be null): where the launch's first work item leaves its decision, 1 stored / 2 skipped, for
+    // the thread that counts the call (call_executed, sbm_lm_kernels.h).
+    const uint32_t* call_enqueued;
+    const uint32_t* call_executed;
+    uint32_t* call_note;
 };
+
+// QS_SOURCE, k_source_lines: the range of a work item's buffer over the retained copy -- `bytes`, or 0 where the call does not
+// keep its copy: the range check then drops every store of it, and the row loop has no branch for the decision.  One read of the
+// two counters per work item, in front of the loop.  first: the launch's first work item notes the decision.
+__device__ __forceinline__ uint32_t source_keep_range(const QSArgs& a, uint32_t bytes, bool first)
+{
+    using namespace wv;
+    bool keeps = true;
+    if (a.call_enqueued && a.call_executed) keeps = source_pass_retains(load_word_system(a.call_enqueued), load_word_system(a.call_executed));
+    const Buf note = make_buf(reinterpret_cast<uint8_t*>(a.call_note), a.call_note && first ? 4u : 0u);
+    buf_store_u32(note, select(eq(lane_id(), splat(0u)), 0u, BUF_DROP), 0u, splat(keeps ? 1u : 2u));
+    return keeps ? bytes : 0u;
+}
 
 // Which part of the row loop a kernel instance holds (compile time):
 //   QS_WHOLE   everything (the header comment above)
@@ -230,7 +254,8 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
     const Buf pyr_buf = make_buf(a.pyr + (int64_t)frame * a.pyr_fs, nseg ? nfr * (uint32_t)a.pyr_fs : (uint32_t)drows * (uint32_t)dcols * CH);
     const V pyr_off = select(store_ok, (CH == 3 ? (c0 >> 1) + ((c0 >> 1) << 1) : (c0 >> 1)) + segc * (uint32_t)a.pyr_fs, BUF_DROP);
     // the retained copy: the lane's dwords as loaded (a useful lane's columns are inside the image: lcol == c0)
-    const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, nseg ? nfr * (uint32_t)a.keep_fs : (uint32_t)rows * (uint32_t)cols * CH);
+    const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs,
+                                  source_keep_range(a, nseg ? nfr * (uint32_t)a.keep_fs : (uint32_t)rows * (uint32_t)cols * CH, strip == 0 && rb == 0 && frame == 0));
     const V keep_off = select(store_ok, (CH == 3 ? c0 + (c0 << 1) : c0) + segc * (uint32_t)a.keep_fs, BUF_DROP);
     V selA = splat(0x03020100u), selB = splat(0x03020100u), selC = splat(0x07060504u);
     if (IL3) {

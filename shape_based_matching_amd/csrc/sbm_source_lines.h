@@ -86,7 +86,7 @@ __device__ __forceinline__ void source_lines_wave(const QSArgs& a, int strip, in
     const V row_off = select(in_img, CH == 3 ? c0 + (c0 << 1) : c0, BUF_DROP); // the lane's bytes in a source row and in a row of the copy
     const uint8_t* img = PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
     const Buf src_buf = make_buf(const_cast<uint8_t*>(img), sl_frame_bytes(rows, cols, CH, a.stride));
-    const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, (uint32_t)rows * (uint32_t)cols * CH);
+    const Buf keep_buf = make_buf(a.keep + (int64_t)frame * a.keep_fs, source_keep_range(a, (uint32_t)rows * (uint32_t)cols * CH, strip == 0 && rb == 0 && frame == 0));
     const Buf pyr_buf = make_buf(a.pyr + (int64_t)frame * a.pyr_fs, (uint32_t)drows * (uint32_t)dcols * CH);
     const V pyr_off = select(p_and(in_img, eq(lane & 1u, splat(0u))), CH == 3 ? (c0 >> 1) + ((c0 >> 1) << 1) : (c0 >> 1), BUF_DROP);
     // the edge load: lane 0 and lane 63 of a strip with a neighbour on that side

@@ -36,6 +36,13 @@ SBM_SL_HD bool source_lines_ok(uint64_t base, int64_t stride, int64_t frame_stri
     return (rows - 1) * stride + (int64_t)cols * ch < SL_MAX_FRAME_BYTES;
 }
 
+// Whether a work item of the source pass (either form) stores its rows of the retained copy.  enqueued: match calls the host has
+// fully enqueued on the context, this one included once its enqueue has ended; executed: calls whose launches up to the
+// linear-memory builder have run -- every call before this one.  The copy's readers need the copy of the
+// last call enqueued only, so a call keeps its copy unless a later one has been enqueued behind it.  A stale low `enqueued` keeps
+// once too often; the word never runs ahead.  The counters wrap: the difference is what counts.
+SBM_SL_HD bool source_pass_retains(uint32_t enqueued, uint32_t executed) { return (int32_t)(enqueued - executed) <= 1; }
+
 // bytes of one frame that the pass may load: the buffer the lane offsets are checked against
 SBM_SL_HD uint32_t sl_frame_bytes(int rows, int cols, int ch, int stride) { return (uint32_t)((int64_t)(rows - 1) * stride + (int64_t)cols * ch); }
 

@@ -126,6 +126,14 @@ __device__ __forceinline__ P p_not(P a) { return !a; }
 __device__ __forceinline__ V select(P p, V a, V b) { return p ? a : b; }
 __device__ __forceinline__ bool all(P p) { return __builtin_amdgcn_ballot_w64(!p) == 0ull; } // wave-uniform
 __device__ __forceinline__ uint32_t read_first(V a) { return __builtin_amdgcn_readfirstlane(a); }
+// one word that an earlier launch, or the host, may have written: read from memory, past the caches (a relaxed atomic load of
+// system scope).  Wave-uniform, and ONE lane loads: 64 lanes' loads of one uncached word would be 64 requests.
+__device__ __forceinline__ uint32_t load_word_system(const uint32_t* p)
+{
+    uint32_t v = 0;
+    if (lane_id() == 0) v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return __builtin_amdgcn_readfirstlane(v);
+}
 
 // memory: wave-uniform base pointer + per-lane byte offset
 __device__ __forceinline__ V load_u32(const uint8_t* base, V off) { return *(const wv_u32_unaligned*)(base + off); }
