@@ -1,6 +1,6 @@
 // Stand-in for the part of OpenCV 4's core module that the reference's line2Dup.cpp compiles against.
 //
-// TEST INFRASTRUCTURE ONLY (oracle/ref_match.mk, oracle/ref_train.mk).  Written for this project; it shares no code with OpenCV or with the
+// TEST INFRASTRUCTURE ONLY (oracle/ref_match.mk, oracle/ref_train.mk, oracle/ref_nms.mk).  Written for this project; it shares no code with OpenCV or with the
 // product's own cv:: subset (include/sbm_cvlite.h), so that a misreading in one cannot hide on both sides of the
 // comparison the reference binary makes.
 //
@@ -13,6 +13,10 @@
 // gradient half's filters and Mat arithmetic (GaussianBlur, Sobel, phase, pyrDown, mul, +, convertTo) do nothing and
 // return an empty Mat: that is how the training driver obtains a ColorGradientPyramid, whose constructor and pyrDown()
 // call update(), without any gradient arithmetic (see oracle/ref_train_driver.cpp).
+// The reference's nms.hpp (oracle/ref_nms.mk) uses Rect_::area() and operator&.  Both are restated here from OpenCV's
+// documented behaviour (area = width * height; a & b = the intersection, or the empty Rect_() when the boxes share no
+// extent in x or y).  With OpenCV absent, nothing checks this restatement against OpenCV's code: it is the one piece
+// of the NMS oracle chain that stays unpinned.
 //
 // Allocation follows OpenCV: rows are continuous (step == cols * elemSize) and the buffer starts on a 64-byte
 // boundary (orUnaligned8u's scalar prologue depends on the alignment).  Unlike OpenCV, every buffer is zero-filled and
@@ -32,6 +36,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include <iostream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -132,7 +137,16 @@ template <typename T> struct Rect_ {
     T x, y, width, height;
     Rect_() : x(0), y(0), width(0), height(0) {}
     Rect_(T x_, T y_, T w, T h) : x(x_), y(y_), width(w), height(h) {}
+    T area() const { return width * height; }
 };
+// the intersection: from the larger of the two origins to the smaller of the two far edges, per axis; the
+// default-constructed empty rectangle when that leaves no extent in x or in y
+template <typename T> Rect_<T> operator&(const Rect_<T>& a, const Rect_<T>& b) {
+    const T x1 = std::max(a.x, b.x), y1 = std::max(a.y, b.y);
+    const T x2 = std::min(a.x + a.width, b.x + b.width), y2 = std::min(a.y + a.height, b.y + b.height);
+    if (x2 <= x1 || y2 <= y1) return Rect_<T>();
+    return Rect_<T>(x1, y1, x2 - x1, y2 - y1);
+}
 typedef Rect_<int> Rect;
 
 struct Scalar {

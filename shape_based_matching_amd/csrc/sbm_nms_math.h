@@ -1,6 +1,8 @@
 // sbm_nms_math.h — the arithmetic of the NMS stage (sbm_nms_kernels.h): the overlap of two boxes, the adaptive threshold
 // and the in-chunk greedy resolution.  Plain scalar code, host and device: tests/test_nms_math.py compiles the host pass
-// for the CPU suite and checks it against the Python restatement of the reference (test_nms.py::py_nms).
+// for the CPU suite and checks it against the Python restatement of the reference (test_nms.py::py_nms), which
+// tests/test_reference_nms.py pins, with this file's overlap bits and chunked walk, to the reference's own nms.hpp
+// compiled as a test binary.
 //
 // Reference: include/nms.hpp (cv_dnn::NMSBoxes / rectOverlap, nms.hpp:21-96 of the reference), the step every caller runs
 // after Detector::match (test.cpp:491, test_jabil.cpp:148).  Built with -ffp-contract=off -fno-fast-math: the double

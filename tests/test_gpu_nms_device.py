@@ -1,7 +1,8 @@
 """-m gpu: the match epilogue + NMS on the device (sbm_nms_batch_device, sbm_match_batch_host_end_nms,
 Detector::matchBatchNMS).  The expected list is always computed here: raw lists -> canonical order -> the reference's
 adjacent unique on (x, y, similarity, class) -> test_nms.py::py_nms over boxes (x, y, level-0 width, height) -- the
-reference callers' loop (test.cpp:470-491, test_jabil.cpp:128-148)."""
+reference callers' loop (test.cpp:470-491, test_jabil.cpp:128-148).  The helpers that compute it live in tests/nms_form_cases.py,
+shared with tests/test_gpu_nms_forms.py (the kernel at its edges); tests/test_reference_nms.py pins py_nms to the reference's nms.hpp."""
 import os
 import subprocess
 
@@ -11,59 +12,11 @@ import pytest
 from conftest import ROOT
 from shape_based_matching_amd import capi, synth
 from shape_based_matching_amd.templates import MATCH_DTYPE, TemplateSet, write_class_yaml
-from test_nms import py_nms
+from nms_form_cases import epilogue, expected, rows_of, run_nms, sizes_of, synth_list
 
 pytestmark = pytest.mark.gpu
 DEMO = os.path.join(ROOT, "shape_based_matching_amd", "sbm_facade_demo")
 REC = MATCH_DTYPE.itemsize
-
-
-def epilogue(recs):
-    """sort by (similarity desc, template_id, class_idx, y, x), then drop a record equal to its predecessor in
-    (x, y, similarity, class_idx) (Match::operator== under std::unique)"""
-    r = np.ascontiguousarray(recs, MATCH_DTYPE)
-    order = sorted(range(len(r)), key=lambda i: (-float(r[i]["similarity"]), int(r[i]["template_id"]), int(r[i]["class_idx"]),
-                                                  int(r[i]["y"]), int(r[i]["x"])))
-    out = []
-    for i in order:
-        m = r[i]
-        if out and (int(out[-1]["x"]), int(out[-1]["y"]), float(out[-1]["similarity"]), int(out[-1]["class_idx"])) == \
-                (int(m["x"]), int(m["y"]), float(m["similarity"]), int(m["class_idx"])):
-            continue
-        out.append(m)
-    return np.array(out, MATCH_DTYPE) if out else np.zeros(0, MATCH_DTYPE)
-
-
-def expected(recs, sizes, score_thr, nms_thr, eta=1.0, top_k=0):
-    """sizes: {(class_idx, template_id): (w0, h0)}; an unknown label has an empty box"""
-    e = epilogue(recs)
-    boxes = [[int(m["x"]), int(m["y"])] + list(sizes.get((int(m["class_idx"]), int(m["template_id"])), (0, 0))) for m in e]
-    keep = py_nms(boxes, [float(m["similarity"]) for m in e], score_thr, nms_thr, eta, top_k)
-    return e[keep] if keep else np.zeros(0, MATCH_DTYPE)
-
-
-def sizes_of(ts):
-    return {(int(ts.class_idx[t]), int(ts.template_id[t])): (int(ts.levels[t, 0]["width"]), int(ts.levels[t, 0]["height"]))
-            for t in range(ts.n_templates)}
-
-
-def rows_of(a):
-    return np.ascontiguousarray(a, MATCH_DTYPE).tolist()
-
-
-def run_nms(ctx, d_recs, d_counts, cap, n_frames, score, thr, eta=1.0, top_k=0, out_cap=None, n_parts=1, part_stride=0, stream=0):
-    import torch
-
-    out_cap = cap * n_parts if out_cap is None else out_cap
-    d_out = torch.zeros(max(n_frames * out_cap * REC, 1), dtype=torch.uint8, device="cuda:0")
-    d_oc = torch.full((n_frames * 2,), -1, dtype=torch.int32, device="cuda:0")
-    torch.cuda.synchronize()
-    ctx.nms_batch_device(d_recs, d_counts, cap, n_frames, d_out.data_ptr(), out_cap, d_oc.data_ptr(), score, thr, eta, top_k,
-                         n_parts=n_parts, part_stride=part_stride, stream=stream)
-    torch.cuda.synchronize()
-    oc = d_oc.cpu().numpy().reshape(-1, 2)
-    out = d_out.cpu().numpy()[: n_frames * out_cap * REC].reshape(n_frames, out_cap * REC) if out_cap else None
-    return [(out[f].view(MATCH_DTYPE)[: min(oc[f, 0], out_cap)] if out_cap else np.zeros(0, MATCH_DTYPE)) for f in range(n_frames)], oc
 
 
 def case1_setup(oracle, case1, ch, n=16):
@@ -172,25 +125,6 @@ def synth_templates(case1):
     ts.class_idx[:] = np.arange(ts.n_templates) % 3
     ts.template_id[:] = np.arange(ts.n_templates) // 3
     return ts
-
-
-def synth_list(rs, n, sizes, sims, spread):
-    labels = list(sizes)
-    r = np.zeros(n, MATCH_DTYPE)
-    r["x"] = rs.randint(0, spread, n)
-    r["y"] = rs.randint(0, spread, n)
-    r["similarity"] = rs.choice(sims, n)  # ties
-    lab = [labels[i] for i in rs.randint(0, len(labels), n)]
-    r["class_idx"] = [l[0] for l in lab]
-    r["template_id"] = [l[1] for l in lab]
-    r["raw"] = (r["similarity"] * 4).astype(np.int32)
-    if n >= 8:
-        r[1] = r[0]  # an exact duplicate
-        r[3] = r[2]
-        r[3]["template_id"] = (int(r[2]["template_id"]) + 1) % 20  # same (x, y, sim, class), other template: adjacent ...
-        r[n - 1] = r[4]
-        r[n - 1]["template_id"] = (int(r[4]["template_id"]) + 7) % 20  # ... and, with other templates between, not adjacent
-    return r
 
 
 def test_synthetic_lists(ctx_factory, case1):

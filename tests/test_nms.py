@@ -1,5 +1,6 @@
 """NMS: include/nms.hpp's cv_dnn::NMSBoxes against a direct Python restatement of the
-reference semantics (nms.hpp:21-96): score filter, stable sort, greedy IoU with adaptive threshold."""
+reference semantics (nms.hpp:21-96): score filter, stable sort, greedy IoU with adaptive threshold.  The restatement
+itself (py_nms) is pinned to the reference's own nms.hpp, compiled into oracle/_ref/ref_nms, by tests/test_reference_nms.py."""
 import ctypes as C
 import os
 

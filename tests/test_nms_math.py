@@ -1,6 +1,7 @@
 """CPU (not gpu): the arithmetic of the device NMS stage (shape_based_matching_amd/csrc/sbm_nms_math.h: overlap, adaptive
 threshold, in-chunk greedy resolution), host pass compiled here, against test_nms.py::py_nms -- the Python restatement
-of include/nms.hpp (cv_dnn::NMSBoxes, the step after Detector::match in test.cpp:491 / test_jabil.cpp:148)."""
+of include/nms.hpp (cv_dnn::NMSBoxes, the step after Detector::match in test.cpp:491 / test_jabil.cpp:148).  py_nms and the
+overlap's bit patterns are pinned to the reference's own nms.hpp (oracle/_ref/ref_nms) by tests/test_reference_nms.py."""
 import ctypes as C
 import itertools
 import os

@@ -25,6 +25,10 @@ With --ref-train, only:
                                 oracle/ref_train.mk) makes of the 96 x 96 rectangle of tests/train_batch_cases.py under its
                                 four masks and of the 64 x 64 rectangle under its left half (which fails), two levels, 63
                                 features: per case the level records, the features (theta as bits) and the failing level.
+With --ref-nms, only:
+  ref_nms_cases.npz          <- what the reference's own cv_dnn::NMSBoxes (oracle/_ref/ref_nms, built by oracle/ref_nms.mk)
+                                keeps of every case of tests/nms_form_cases.py and of its lists with score ties: the kept
+                                indices alone (one uint16 array, the keys -- case name and parameters -- and the offsets).
 No reference source text is copied.
 """
 import gzip
@@ -127,8 +131,23 @@ def ref_train_fixture():
     np.savez_compressed(f"{OUT}/ref_train_cases.npz", **out)
 
 
+def ref_nms_fixture():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nms_form_cases as NC
+    from oracle import ref_nms as RN
+
+    problems = {NC.recorded_key(c): NC.problem(c) for _, _, c in NC.all_cases()}
+    problems.update(NC.tie_problems())
+    kept = RN.run_many(list(problems.values()))
+    assert all(len(p[1]) < 65536 for p in problems.values())
+    np.savez_compressed(f"{OUT}/ref_nms_cases.npz", **NC.pack_recorded(dict(zip(problems, kept))))
+    print(f"ref_nms_cases: {len(problems)} problems, {sum(len(v) for v in kept)} kept indices")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["--ref"]:
+    if sys.argv[1:] == ["--ref-nms"]:
+        ref_nms_fixture()
+    elif sys.argv[1:] == ["--ref"]:
         ref_match_fixture()
     elif sys.argv[1:] == ["--ref-train"]:
         ref_train_fixture()
