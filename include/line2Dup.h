@@ -296,7 +296,34 @@ public:
      * detector.  addTemplate*, read*, setDevice(s) and setConcurrency mutate the detector and must not run concurrently
      * with anything else on it -- also as in the reference. */
     void setConcurrency(int max_concurrent_calls);
-    struct Engine; /* opaque: the lane pool, defined in facade/line2Dup_amd.cpp */
+    struct Engine; /* opaque: the lane pool, defined in facade/line2Dup_engine.h */
+
+    /* ---- the verify stage (HCORR of the reference's production driver, test_jabil.cpp:152-207), in
+     * facade/line2Dup_verify.cpp ----
+     * verifyPatch: the fiducial patch of a template as test_jabil.cpp:187-191 makes it with rotateScaleImage
+     *   (utils.cpp:157-187): fiducial_gray (CV_8UC1) resized by t0.sscale when |sscale - 1| > FLT_EPSILON, rotated clockwise
+     *   by 90, 180 or 270 degrees for (int)t0.orientation in {90, -270}, {180, -180}, {270, -90}, cropped to Rect(t0.tl_x,
+     *   t0.tl_y, t0.width, t0.height).  An empty Mat when the crop leaves the image (the reference would throw).
+     * setFiducials: the gray images by Template::fiducial_src, the map of utils.cpp:236-243.  Every template pyramid whose
+     *   level-0 fiducial_src is in the map and whose crop fits gets a patch; the patches are uploaded to each pooled engine
+     *   context when it is next used (sbm_upload_verify_patches), as templates are.  Mutates the detector (see the
+     *   threading contract).
+     * matchBatchVerified: matchBatchNMS followed by the reference's false-positive filter: per frame the matches NMS kept
+     *   whose ROI Rect(m.x, m.y, templ[0].width, templ[0].height), gray and min-max normalised, correlates
+     *   (TM_CCORR_NORMED) with the template's normalised patch by at least min_corr (the reference: 0.8), each with that
+     *   correlation.  A match without a patch, or whose ROI leaves the frame, has hcorr -1 and is kept only with
+     *   keep_unverified.  All three stages run on the device on one upload of the frames
+     *   (sbm_match_batch_host_verified; include/sbm.h states the arithmetic). */
+    struct VerifiedMatch {
+        Match match;
+        float hcorr;
+    };
+    static cv::Mat verifyPatch(const Template& t0, const cv::Mat& fiducial_gray);
+    void setFiducials(const std::map<std::string, cv::Mat>& gray_by_src);
+    std::vector<std::vector<VerifiedMatch>> matchBatchVerified(const std::vector<cv::Mat>& sources, float threshold,
+                                                               const std::vector<std::string>& class_ids, float score_threshold,
+                                                               float nms_threshold, double min_corr, float eta = 1.f, int top_k = 0,
+                                                               bool keep_unverified = false) const;
 
 protected:
     cv::Ptr<ColorGradient> modality;

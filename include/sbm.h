@@ -410,6 +410,74 @@ int sbm_nms_batch_device(sbm_ctx* ctx, const void* d_recs, const void* d_counts,
  * as _end does.  SBM_ERR_CAPACITY when some frame has flag bit 0 or 1 (its stored records are still returned). */
 int sbm_match_batch_host_end_nms(sbm_ctx* ctx, const sbm_nms_params* p, sbm_match_rec* out, int64_t out_cap, int32_t* counts);
 
+/* ---- verify stage on the device: normalised correlation per kept match --------
+ * What the reference's production driver does with the matches NMS kept (HCORR, test_jabil.cpp:152-207): cut
+ * Rect(match.x, match.y, templ[0].width, templ[0].height) out of the frame, convert it to gray, min-max normalise it to
+ * 0..255, correlate it (TM_CCORR_NORMED) with the template's fiducial patch -- the fiducial image scaled and rotated as the
+ * template was and cropped to Rect(tl_x, tl_y, width, height) (test_jabil.cpp:187-191 with utils.cpp:157-187) -- and drop
+ * the match when the correlation is below 0.8.  Both images have one size, so the correlation map is one number.
+ *
+ * The arithmetic ("verify rule", csrc/sbm_verify_math.h; DESIGN.md has its standing relative to OpenCV):
+ *   1. gray: a 3-channel pixel is B, G, R and becomes (B*1868 + G*9617 + R*4899 + 8192) >> 14; a 1-channel pixel is used
+ *      as it is; planar frames give B, G, R from the caller's three planes in the order listed.
+ *   2. normalise a gray image with minimum lo and maximum hi: all 0 if hi == lo; else, in double, scale = 255.0 *
+ *      (1.0 / (hi - lo)), shift = 0.0 - lo * scale, a = (float)scale, b = (float)shift, and a value g becomes
+ *      round-to-nearest-even((float)g * a + b) with both float operations rounded, clamped to 0..255.
+ *   3. score: Sab = sum n_roi * n_patch, Saa = sum n_roi^2, Sbb = sum n_patch^2 as unsigned 64-bit integers; den =
+ *      sqrt((double)Saa * (double)Sbb); q = den == 0 ? 0 : (double)Sab / den, at most 1; score = (float)q.
+ *   4. a record is kept iff (double)score >= min_corr.
+ *   5. a record whose label (class_idx, template_id) has no patch, or whose ROI is not wholly inside the frame (or is
+ *      empty), is unverifiable: score -1, kept iff keep_unverified != 0.  (The reference would throw.)
+ *
+ * The patch set: one gray patch per label, of the label's level-0 width x height, rows `stride` bytes apart.  The upload
+ * normalises each by rule 2 and stores the normalised bytes and Sbb.  n = 0 clears the set (every record is then
+ * unverifiable).  SBM_ERR_INVALID, naming the patch index, for a label the current template upload does not have, a size
+ * other than the template's level-0 size, a duplicate label, or stride < width; a refused call leaves the former set in
+ * place.  The set belongs to one template upload: after another sbm_upload_templates* call the verify calls return
+ * SBM_ERR_STATE until patches are uploaded again.  The upload synchronises the device.
+ * sbm_get_verify_patch reads a stored (normalised) patch back, and its Sbb. */
+typedef struct sbm_verify_patch {
+    int32_t class_idx, template_id, width, height, stride, reserved;
+    const uint8_t* gray;
+} sbm_verify_patch;
+int sbm_upload_verify_patches(sbm_ctx* ctx, const sbm_verify_patch* patches, int32_t n);
+int sbm_get_verify_patch(sbm_ctx* ctx, int32_t class_idx, int32_t template_id, uint8_t* out_host, int64_t cap_bytes, uint64_t* sbb);
+
+/* The stage.  The frame arguments are those of sbm_match_batch_device, _ptrs and _planes (the same tables serve).
+ * Input: frame f's records at d_recs + f * cap (records), its int32 pair at d_counts + 2 * f -- the output layout of
+ * sbm_nms_batch_device, and of sbm_match_batch_device itself ({n_matches, overflow}); min(count, cap) records are read.
+ * Output: the kept records at d_out + f * out_cap in input order, their scores (float) at d_scores + f * out_cap,
+ * {n_kept, flags} at d_out_counts + 2 * f.  flags: bit 0 the input pair's second word was non-zero or count > cap; bit 1
+ * n_kept > out_cap (the first out_cap are stored); bit 2 some record had no patch; bit 3 some ROI was not inside the frame.
+ * The output must not overlap the input.  Stream-ordered and safe to capture: steady-state calls never synchronise,
+ * allocate or read device memory from the host; a call with a larger n_frames * cap grows the scratch and synchronises the
+ * device then.  The scratch is the context's: calls on one context are ordered by their streams.  The output order is the
+ * input order on every run. */
+typedef struct sbm_verify_params {
+    double min_corr;         /* the reference: 0.8 */
+    int32_t keep_unverified; /* rule 5 */
+    int32_t reserved;
+} sbm_verify_params;
+int sbm_verify_batch_device(sbm_ctx* ctx, const void* d_imgs, int64_t frame_stride, int32_t n_frames, int32_t rows, int32_t cols,
+                            int32_t stride, int32_t channels, const void* d_recs, const void* d_counts, int64_t cap,
+                            const sbm_verify_params* p, void* d_out, void* d_scores, int64_t out_cap, void* d_out_counts, void* stream);
+int sbm_verify_batch_device_ptrs(sbm_ctx* ctx, const void* d_frame_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                 int32_t channels, const void* d_recs, const void* d_counts, int64_t cap, const sbm_verify_params* p,
+                                 void* d_out, void* d_scores, int64_t out_cap, void* d_out_counts, void* stream);
+int sbm_verify_batch_device_planes(sbm_ctx* ctx, const void* d_plane_ptrs, int32_t n_frames, int32_t rows, int32_t cols, int32_t stride,
+                                   const void* d_recs, const void* d_counts, int64_t cap, const sbm_verify_params* p, void* d_out,
+                                   void* d_scores, int64_t out_cap, void* d_out_counts, void* stream);
+/* The three stages of the reference's driver (MATCH, NMS, HCORR) for frames in host memory, blocking: uploads the frames
+ * into one block of the context's, runs the sbm_match_batch_device path, sbm_nms_batch_device and the verify stage on
+ * the context's stream, and copies back only the kept records (frame f's at out + f * out_cap), their scores (scores +
+ * f * out_cap) and {n_kept, flags} (counts + 2 * f; the flags of the verify stage, bit 0 where the NMS stage flagged the
+ * frame, that is where its raw list overflowed).  cap: records per frame of the raw match lists, and of the NMS stage's
+ * output, which therefore never runs out of room.  SBM_ERR_CAPACITY when some frame has flag bit 0 or 1 (the rule of
+ * sbm_match_batch_host_end_nms; its stored records are still returned). */
+int sbm_match_batch_host_verified(sbm_ctx* ctx, const uint8_t* const* frames, int32_t n_frames, int32_t rows, int32_t cols,
+                                  int32_t stride, int32_t channels, float threshold, int64_t cap, const sbm_nms_params* nms,
+                                  const sbm_verify_params* verify, sbm_match_rec* out, float* scores, int64_t out_cap, int32_t* counts);
+
 /* ---- pyramid state ------------------------------------------------------
  * sbm_build_pyramid: the first half of match() (line2Dup.cpp:1084-1120):
  * quantizedOrientations -> [pyrDown -> quantizedOrientations]* -> per level

@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "sbm_get_level_build",
     "sbm_get_level_stored",
     "sbm_upload_templates_device", "sbm_get_templates", "sbm_get_template_table",
+    "sbm_upload_verify_patches", "sbm_get_verify_patch", "sbm_verify_batch_device", "sbm_verify_batch_device_ptrs",
+    "sbm_verify_batch_device_planes", "sbm_match_batch_host_verified",
 ]
 
 # sbm_match_batch_device_ptrs flags: the caller promises that every frame pointer is a multiple of 4
@@ -75,6 +77,28 @@ class SbmNmsParams(C.Structure):
         ("nms_threshold", C.c_float),
         ("eta", C.c_float),
         ("top_k", C.c_int32),
+    ]
+
+
+class SbmVerifyPatch(C.Structure):
+    """sbm_verify_patch: the gray fiducial patch of one template label (32 bytes)"""
+    _fields_ = [
+        ("class_idx", C.c_int32),
+        ("template_id", C.c_int32),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("stride", C.c_int32),
+        ("reserved", C.c_int32),
+        ("gray", C.c_void_p),
+    ]
+
+
+class SbmVerifyParams(C.Structure):
+    """sbm_verify_params: the verify stage's threshold (the reference: 0.8) and what becomes of unverifiable records"""
+    _fields_ = [
+        ("min_corr", C.c_double),
+        ("keep_unverified", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 
@@ -319,6 +343,13 @@ def lib() -> C.CDLL:
     L.sbm_upload_templates_device.argtypes = [vp, vp, i32, vp, vp]
     L.sbm_get_templates.argtypes = [vp, vp, vp, i64, vp, vp, C.POINTER(i32), C.POINTER(i64)]
     L.sbm_get_template_table.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+    pv = C.POINTER(SbmVerifyParams)
+    L.sbm_upload_verify_patches.argtypes = [vp, vp, i32]
+    L.sbm_get_verify_patch.argtypes = [vp, i32, i32, vp, i64, C.POINTER(C.c_uint64)]
+    L.sbm_verify_batch_device.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, i64, pv, vp, vp, i64, vp, vp]
+    L.sbm_verify_batch_device_ptrs.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, i64, pv, vp, vp, i64, vp, vp]
+    L.sbm_verify_batch_device_planes.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i64, pv, vp, vp, i64, vp, vp]
+    L.sbm_match_batch_host_verified.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, i64, C.POINTER(SbmNmsParams), pv, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)
         if name not in ("sbm_last_error", "sbm_destroy", "sbm_canonicalize"):
@@ -517,6 +548,82 @@ class Context:
         _check(lib().sbm_match_batch_host_begin(self._h, ptrs, len(arrs), r, c, c * ch, ch, _p(m), C.c_float(threshold), cap, sub_batch))
         _check(lib().sbm_match_batch_host_end_nms(self._h, C.byref(prm), _p(out), out_cap, _p(counts)))
         return [out[f, : counts[f, 0]].copy() for f in range(len(arrs))], counts
+
+    def upload_verify_patches(self, patches: Sequence[Tuple[int, int, np.ndarray]]):
+        """sbm_upload_verify_patches: (class_idx, template_id, gray patch HxW uint8) per label, each of its template's level-0
+        size; an array that is not contiguous along its rows is copied, a row stride is passed as it is.  [] clears the set."""
+        arrs = []
+        for _, _, g in patches:
+            g = np.asarray(g, np.uint8)
+            assert g.ndim == 2
+            arrs.append(g if g.size == 0 or g.strides[1] == 1 and g.strides[0] >= g.shape[1] else np.ascontiguousarray(g))
+        recs = (SbmVerifyPatch * max(len(arrs), 1))()
+        for i, ((cls, tid, _), g) in enumerate(zip(patches, arrs)):
+            recs[i] = SbmVerifyPatch(cls, tid, g.shape[1], g.shape[0], g.strides[0] if g.size else g.shape[1], 0, g.ctypes.data)
+        _check(lib().sbm_upload_verify_patches(self._h, recs if arrs else None, len(arrs)))
+
+    def upload_verify_patches_raw(self, recs: Sequence[SbmVerifyPatch]):
+        """sbm_upload_verify_patches with the caller's own records (any width, height and stride)"""
+        arr = (SbmVerifyPatch * max(len(recs), 1))(*recs)
+        _check(lib().sbm_upload_verify_patches(self._h, arr, len(recs)))
+
+    def get_verify_patch(self, class_idx: int, template_id: int, width: int, height: int) -> Tuple[np.ndarray, int]:
+        """sbm_get_verify_patch: the stored (normalised) patch of a label and the sum of its squares"""
+        out = np.zeros((height, width), np.uint8)
+        sbb = C.c_uint64(0)
+        _check(lib().sbm_get_verify_patch(self._h, class_idx, template_id, _p(out), out.nbytes, C.byref(sbb)))
+        return out, int(sbb.value)
+
+    def verify_batch_device(self, d_imgs: int, frame_stride: int, n_frames: int, rows: int, cols: int, stride: int, channels: int,
+                            d_recs: int, d_counts: int, cap: int, min_corr: float, d_out: int, d_scores: int, out_cap: int,
+                            d_out_counts: int, keep_unverified: bool = False, stream: int = 0):
+        """normalised correlation per record against its label's patch (sbm_verify_batch_device): frame f's records at
+        d_recs + f*cap records, its {n, overflow} at d_counts + 2*f int32 (sbm_nms_batch_device's output layout); kept records at
+        d_out + f*out_cap in input order, scores at d_scores + f*out_cap floats, {n_kept, flags} at d_out_counts + 2*f."""
+        prm = SbmVerifyParams(min_corr, int(keep_unverified), 0)
+        _check(lib().sbm_verify_batch_device(self._h, C.c_void_p(d_imgs), frame_stride, n_frames, rows, cols, stride, channels,
+                                             C.c_void_p(d_recs), C.c_void_p(d_counts), cap, C.byref(prm), C.c_void_p(d_out) if d_out else None,
+                                             C.c_void_p(d_scores) if d_scores else None, out_cap, C.c_void_p(d_out_counts),
+                                             C.c_void_p(stream) if stream else None))
+
+    def verify_batch_device_ptrs(self, d_frame_ptrs: int, n_frames: int, rows: int, cols: int, stride: int, channels: int, d_recs: int,
+                                 d_counts: int, cap: int, min_corr: float, d_out: int, d_scores: int, out_cap: int, d_out_counts: int,
+                                 keep_unverified: bool = False, stream: int = 0):
+        """verify_batch_device on the frames a device table of addresses names (match_batch_device_ptrs's table)"""
+        prm = SbmVerifyParams(min_corr, int(keep_unverified), 0)
+        _check(lib().sbm_verify_batch_device_ptrs(self._h, C.c_void_p(d_frame_ptrs) if d_frame_ptrs else None, n_frames, rows, cols, stride,
+                                                  channels, C.c_void_p(d_recs), C.c_void_p(d_counts), cap, C.byref(prm),
+                                                  C.c_void_p(d_out) if d_out else None, C.c_void_p(d_scores) if d_scores else None, out_cap,
+                                                  C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None))
+
+    def verify_batch_device_planes(self, d_plane_ptrs: int, n_frames: int, rows: int, cols: int, stride: int, d_recs: int, d_counts: int,
+                                   cap: int, min_corr: float, d_out: int, d_scores: int, out_cap: int, d_out_counts: int,
+                                   keep_unverified: bool = False, stream: int = 0):
+        """verify_batch_device on planar frames: a device table of 3 plane addresses per frame, B, G, R in the order listed"""
+        prm = SbmVerifyParams(min_corr, int(keep_unverified), 0)
+        _check(lib().sbm_verify_batch_device_planes(self._h, C.c_void_p(d_plane_ptrs) if d_plane_ptrs else None, n_frames, rows, cols, stride,
+                                                    C.c_void_p(d_recs), C.c_void_p(d_counts), cap, C.byref(prm),
+                                                    C.c_void_p(d_out) if d_out else None, C.c_void_p(d_scores) if d_scores else None, out_cap,
+                                                    C.c_void_p(d_out_counts), C.c_void_p(stream) if stream else None))
+
+    def match_batch_host_verified(self, frames: Sequence[np.ndarray], threshold: float, score_threshold: float, nms_threshold: float,
+                                  min_corr: float, eta: float = 1.0, top_k: int = 0, keep_unverified: bool = False, cap: int = 1024,
+                                  out_cap: int = 256):
+        """sbm_match_batch_host_verified: match, NMS and verify on one upload of the frames; per frame the kept records and
+        their scores (lists of arrays), and the {n_kept, flags} pairs"""
+        arrs = [_img(f) for f in frames]
+        r, c, ch = arrs[0][1:]
+        assert all(a[1:] == (r, c, ch) for a in arrs)
+        ptrs = (C.c_void_p * len(arrs))(*[a[0].ctypes.data for a in arrs])
+        out = np.zeros((len(arrs), out_cap), MATCH_DTYPE)
+        scores = np.zeros((len(arrs), out_cap), np.float32)
+        counts = np.zeros((len(arrs), 2), np.int32)
+        nms = SbmNmsParams(score_threshold, nms_threshold, eta, top_k)
+        prm = SbmVerifyParams(min_corr, int(keep_unverified), 0)
+        _check(lib().sbm_match_batch_host_verified(self._h, ptrs, len(arrs), r, c, c * ch, ch, C.c_float(threshold), cap, C.byref(nms),
+                                                   C.byref(prm), _p(out), _p(scores), out_cap, _p(counts)))
+        k = [min(int(counts[f, 0]), out_cap) for f in range(len(arrs))]
+        return [out[f, : k[f]].copy() for f in range(len(arrs))], [scores[f, : k[f]].copy() for f in range(len(arrs))], counts
 
     def set_result_mirror(self, mirror_out: int, mirror_count: int):
         """Device-visible (e.g. pinned host) addresses that receive a copy of every result."""

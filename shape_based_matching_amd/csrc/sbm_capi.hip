@@ -27,6 +27,7 @@
 #include "sbm_train_kernels.h"
 #include "sbm_rotate_kernels.h"
 #include "sbm_nms_kernels.h"
+#include "sbm_verify_kernels.h"
 #include "sbm_install_kernels.h"
 
 using namespace sbm;
@@ -39,3 +40,4 @@ using namespace sbm;
 #include "sbm_capi_nms.inc"     // match epilogue + NMS on the device
 #include "sbm_capi_train.inc"   // batched template training on the device
 #include "sbm_capi_install.inc" // device-trained families as the template set
+#include "sbm_capi_verify.inc"  // normalised correlation per kept match on the device

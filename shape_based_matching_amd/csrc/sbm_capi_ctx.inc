@@ -311,6 +311,15 @@ struct sbm_ctx {
     DevBuf d_nms_labels, d_nms_scratch, d_nms_out;
     int32_t* h_nms_counts = nullptr;
     int h_nms_counts_frames = 0;
+    // verify stage (sbm_capi_verify.inc): the patch set of the upload it was made for (verify_gen against templates_gen) -- the
+    // sorted label table and the normalised bytes, on the device and on the host --, the {score, status} scratch of a call, grown
+    // by the rule of d_nms_scratch, and the host sibling's frames, intermediate lists and pinned results
+    uint64_t verify_gen = ~(uint64_t)0;
+    std::vector<VerifyLabel> h_verify_labels;
+    int64_t verify_patch_bytes = 0;
+    DevBuf d_verify_labels, d_verify_patches, d_verify_scratch, d_verify_in, d_verify_lists;
+    uint8_t* h_verify_out = nullptr;
+    size_t h_verify_out_bytes = 0;
     // batched training (sbm_capi_train.inc): the scratch of a batch, grown by the rule of d_nms_scratch; the host form's images, masks and results
     DevBuf d_train, d_train_in, d_train_mask, d_train_out;
     // ragged training: the pinned slot the table of records (and a sweep's scale and coefficient tables) is copied from,

@@ -80,6 +80,7 @@ void sbm_destroy(sbm_ctx* c)
     if (c->h_res) (void)hipHostFree(c->h_res);
     if (c->h_res_count) (void)hipHostFree(c->h_res_count);
     if (c->h_nms_counts) (void)hipHostFree(c->h_nms_counts);
+    if (c->h_verify_out) (void)hipHostFree(c->h_verify_out);
     if (c->h_train_table) (void)hipHostFree(c->h_train_table);
     if (c->h_enqueued) (void)hipHostFree(c->h_enqueued);
     if (c->ev_train_table) (void)hipEventDestroy(c->ev_train_table);

@@ -16,6 +16,11 @@
 //   demo nmsbatch <templ_fmt> <class_id[,class_id...]> <image> <threshold> <num_features> <n_frames> <score_thr> <nms_thr> <eta> <top_k>
 //       Detector::matchBatchNMS over n_frames copies of the image shifted 8 f columns (wrapping): the epilogue and
 //       NMSBoxes on the device; prints every frame's kept matches in NMS order
+//   demo verify <templ_fmt> <class_id[,class_id...]> <image> <threshold> <num_features> <n_frames> <score_thr> <nms_thr> <eta> <top_k>
+//               <min_corr> <keep_unverified> <blank_last>
+//       test_jabil.cpp:121-312 (MATCH, NMS, HCORR) through Detector::matchBatchVerified over the frames of nmsbatch (the last
+//       one all zero when blank_last is 1): the fiducial images are read from the templates' fiducial_src, as the reference
+//       reads them; prints every frame's kept matches with the bits of their similarity and of their correlation
 //   demo latency <templ_fmt> <class_id> <image> <threshold> <num_features> <n> [pad]
 //       n timed calls of detector.match(img, threshold, ids) on one cv::Mat, as a test.cpp-style caller sees them
 //       also: the same call with the frame buffer pinned (Detector::pinBuffer) and matchBatch from pinned host frames
@@ -38,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <thread>
 #include <vector>
 
@@ -269,6 +275,50 @@ int main(int argc, char** argv)
                     uint32_t bits;
                     memcpy(&bits, &m.similarity, 4);
                     printf("k %d %d %u %s %d\n", m.x, m.y, bits, m.class_id.c_str(), m.template_id);
+                }
+            }
+            return 0;
+        }
+        if (mode == "verify") {
+            if (argc < 15) return usage();
+            const std::string fmt = argv[2], path = argv[4];
+            std::vector<std::string> ids;
+            for (const char* p = argv[3]; *p;) {
+                const char* q = p;
+                while (*q && *q != ',') ++q;
+                ids.push_back(std::string(p, q));
+                p = *q ? q + 1 : q;
+            }
+            const float threshold = (float)atof(argv[5]);
+            const int num_features = atoi(argv[6]), nf = atoi(argv[7]);
+            const float score_thr = (float)atof(argv[8]), nms_thr = (float)atof(argv[9]), eta = (float)atof(argv[10]);
+            const int top_k = atoi(argv[11]);
+            const double min_corr = atof(argv[12]);
+            const bool keep_unverified = atoi(argv[13]) != 0, blank_last = atoi(argv[14]) != 0;
+            line2Dup::Detector detector(num_features, {4, 8});
+            detector.readClasses(ids, fmt);
+            // utils.cpp:236-243: one gray image per distinct fiducial_src (a source that cannot be read has no entry)
+            std::map<std::string, Mat> fiducials;
+            for (const std::string& id : detector.classIds())
+                for (int t = 0; t < detector.numTemplates(id); ++t) {
+                    const std::string& src = detector.getTemplates(id, t)[0].fiducial_src;
+                    if (src.empty() || src == "none" || fiducials.count(src)) continue;
+                    const Mat g = imread(src, IMREAD_UNCHANGED);
+                    if (!g.empty() && g.type() == CV_8UC1) fiducials[src] = g;
+                }
+            detector.setFiducials(fiducials);
+            const Mat unpadded = read_padded(path, 0);
+            if (unpadded.empty()) return 1;
+            std::vector<Mat> frames = shifted_frames(crop16(unpadded), nf);
+            if (blank_last) frames.back().setTo(Scalar::all(0));
+            const auto kept = detector.matchBatchVerified(frames, threshold, ids, score_thr, nms_thr, min_corr, eta, top_k, keep_unverified);
+            for (size_t f = 0; f < kept.size(); ++f) {
+                printf("frame %zu kept %zu\n", f, kept[f].size());
+                for (const auto& v : kept[f]) {
+                    uint32_t bits, hbits;
+                    memcpy(&bits, &v.match.similarity, 4);
+                    memcpy(&hbits, &v.hcorr, 4);
+                    printf("v %d %d %u %s %d %u\n", v.match.x, v.match.y, bits, v.match.class_id.c_str(), v.match.template_id, hbits);
                 }
             }
             return 0;

@@ -244,7 +244,8 @@ def read_classes(class_ids: Sequence[str], fmt: str) -> TemplateSet:
 
 
 def write_class_yaml(ts: TemplateSet, path: str, class_idx: int = 0) -> None:
-    """``Detector::writeClass`` (``line2Dup.cpp:1548-1575``) layout."""
+    """``Detector::writeClass`` (``line2Dup.cpp:1548-1575``) layout.  The fork-only keys are written where ``ts.meta``
+    holds them (``scale``, ``orientation``, ``tagFieldID``, ``fiducial_src``: ``[n_templates][n_levels]`` each)."""
     sel = np.nonzero(ts.class_idx == class_idx)[0]
     out = ["%YAML:1.0", "---", f"class_id: {ts.class_ids[class_idx]}", f"pyramid_levels: {ts.n_levels}", "template_pyramids:"]
     for t in sel:
@@ -257,6 +258,16 @@ def write_class_yaml(ts: TemplateSet, path: str, class_idx: int = 0) -> None:
                 f"            height: {int(lv['height'])}",
                 f"            tl_x: {int(lv['tl_x'])}",
                 f"            tl_y: {int(lv['tl_y'])}",
+            ]
+            if "scale" in ts.meta:
+                out.append(f"            scale: {float(ts.meta['scale'][t][l])!r}")
+            if "orientation" in ts.meta:
+                out.append(f"            orientation: {float(ts.meta['orientation'][t][l])!r}")
+            if "tagFieldID" in ts.meta:
+                out.append(f"            tagFieldID: {int(ts.meta['tagFieldID'][t][l])}")
+            if "fiducial_src" in ts.meta:
+                out.append(f"            fiducial_src: \"{ts.meta['fiducial_src'][t][l]}\"")
+            out += [
                 f"            pyramid_level: {int(lv['pyramid_level'])}",
                 "            features:",
             ]
