@@ -18,7 +18,7 @@
 
 #include "../../include/sbm.h"
 #include "sbm_kernels.h"
-#include "sbm_level_forms.h"
+#include "sbm_call_record.h"
 #include "sbm_quantize_stream.h"
 #include "sbm_source_lines.h"
 #include "sbm_frame_ptrs_plan.h"

@@ -208,8 +208,9 @@ struct sbm_ctx {
     int channels = 0;
     int batch = 1;        // frames the per-level buffers, candidate lists and counters are allocated for
     int mask_frames = 1;  // masks d_mask[l], l >= 1, is allocated for: the batch's frames once a call brought a mask per frame
-    int last_frames = 1;  // frames of the last pyramid built (sbm_get_quantized_frame)
-    int levels_valid = 0; // number of levels whose linear memories are resident
+    // What the last match call (or build) left resident and what it launched: every later reader decides by it (sbm_call_record.h)
+    static_assert(LF_MAX_LEVELS == SBM_MAX_LEVELS, "the record holds every level of the pyramid");
+    CallRecord rec;
     int64_t lm_stride[SBM_MAX_LEVELS]{};
     DevBuf d_img[SBM_MAX_LEVELS], d_mask[SBM_MAX_LEVELS], d_quant[SBM_MAX_LEVELS], d_lm[SBM_MAX_LEVELS];
     // Levels that only the refinement pass reads (l < L-1) are built as ONE plane of spread bytes ("compact": an eighth
@@ -229,23 +230,17 @@ struct sbm_ctx {
     // ... and level 0's orientation map itself only where those tiles' strip builders read it (BuildPlan::sparse_gradient): the
     // source pass keeps the batch's level-0 source bytes here (batch x rows x cols x channels, packed), the gradient launch
     // behind the coarse pass reads them, and so does the whole launch that a later reader of d_quant[0] asks for
-    // (ensure_level0_map) -- the caller's image may be gone by then.  map0_whole: d_quant[0] holds every frame's whole map.
+    // (ensure_level0_map) -- the caller's image may be gone by then (CallRecord::map0_whole, src0_ch).
     DevBuf d_src0;
     // ... and of that map only the work items the refinement can read (SBM_SPARSE_RECTS): per frame and band of RT_BAND pixel rows the
     // hull {xmin, xmax} of the map columns some candidate's refinement depends on, emptied where the tile flags are cleared, widened
     // by k_mark_refine_tiles, read by the sparse gradient launch.  Device data: a replayed graph follows each call's candidates.
     DevBuf d_rects;
     // ... and of those items the working ones, listed per frame by k_mark_refine_tiles for the launch to run from (SBM_SPARSE_LIST):
-    // items_cap entries per frame, room for every item of the grid at any rows per item.  sparse_list: {the last call's sparse
-    // launch ran from lists, its waves per frame}
+    // items_cap entries per frame, room for every item of the grid at any rows per item (CallRecord::sparse_list)
     DevBuf d_items;
     int64_t items_cap = 0;
-    int32_t sparse_list[2] = {0, 0};
-    DevBuf d_sparse_items;          // one int32: the working items of the last profiled sparse gradient launch
-    int32_t sparse_items[3] = {0, 0, 0}; // {selection: 0 none, 1 tiles, 2 need rectangles; working items (-1: not counted); items launched}
-    bool sparse_items_pending = false;   // the count is still on the device
-    int src0_ch = 0;
-    bool map0_whole = true;
+    DevBuf d_sparse_items; // one int32: the working items of the last profiled sparse gradient launch (CallRecord::sparse_items)
     // ... and that copy is stored by the last match call enqueued on the context only (section 5 of DESIGN.md has the argument).
     // h_enqueued: a word of pinned host memory that one thread per launch reads in place (d_enqueued: its device address) --
     // match calls whose enqueue has ended (call_enqueued); d_call: CALL_WORDS words of device memory (sbm_lm_kernels.h) -- calls
@@ -260,9 +255,6 @@ struct sbm_ctx {
     hipEvent_t ev_call = nullptr;
     bool call_recorded = false;
     FrameSource sparse_src;
-    // which of d_lm[l], d_lmc[l], d_lbits[l] (and d_blm, at the coarsest level) hold level l's current linear memories
-    // (sbm_level_forms.h; per level, not per frame: the forms rebuilt on demand cover frame 0 only)
-    LevelForms forms[SBM_MAX_LEVELS];
     int refine_bits = -1; // sbm_set_refine_bits: -1 the process default (SBM_LOCAL_BITS, else on), 0 bytes, 1 bits
     DevBuf d_geo; // T[L], W[L], H[L] as int32 then stride[L] as int64
     bool foff_dirty = true;
@@ -337,39 +329,13 @@ struct sbm_ctx {
         hipGraph_t graph = nullptr;
         hipGraphExec_t exec = nullptr;
         uint64_t last_use = 0;
-        int32_t coarse_form[4] = {0, 0, 0, 0}; // what the captured enqueue_coarse launched: a replay repeats it
-        int32_t source_form = 0;               // ... and the captured source pass
-        int32_t refine_form[SBM_MAX_LEVELS][6] = {}; // ... and what the captured enqueue_local launched per level
-        int32_t level_build[SBM_MAX_LEVELS][5] = {}; // ... and the captured builds of the levels' linear memories (LevelBuild)
+        CallRecord rec; // what the capture left in the context, taken once it has ended: a replay restores it (CallRecord::replayed)
     };
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     int quantize_mode = 0, quantize_hs = 0; // sbm_set_quantize_mode
     int pipeline_depth = 1;                 // sbm_set_pipeline_depth: batches the caller keeps in flight on this GPU
     int local_order = tuning().local_order; // -1 by the planes' size, 0 per-frame slots, 2 one frame-major list (sbm_set_refine_order)
-    int32_t coarse_form[4] = {0, 0, 0, 0};  // {kind, P, wide, dw} of the coarse kernel enqueue_coarse last launched (sbm_get_coarse_form)
-    int32_t source_form = 0; // the source pass of the last call: 0 none, 1 the strided form QS_SOURCE, 2 k_source_lines (sbm_get_source_form)
-    // {kind, LW, order, t8, sparse, slots} of the refinement kernel enqueue_local last launched for every level (sbm_get_refine_form)
-    int32_t refine_form[SBM_MAX_LEVELS][6] = {};
-    void note_refine_form(int l, LmForm reads, int LW, int order, bool t8, bool sparse, int slots)
-    {
-        const int kind = reads == LM_BIT_STRIPS ? 4 : reads == LM_SPREAD_STRIP ? 3 : reads == LM_SPREAD ? 2 : 1;
-        const int32_t f[6] = {kind, LW, order, t8 ? 1 : 0, sparse ? 1 : 0, slots};
-        memcpy(refine_form[l], f, sizeof f);
-    }
-    // per level, what the last build of its linear memories was (sbm_get_level_build): the LmForm it was made in (LM_BIT_STRIPS_SPARSE
-    // included), the builder (0 none, 1 k_build_lm_rows, 2 k_build_lm_any, 3 k_build_lm, 4 the unfused path), LmWork's split and allty of
-    // that launch, and which kernel packed the coarsest level's bit planes since (1 k_pack_bitplanes_spread, 2 k_pack_bitplanes, 0 none).
-    // Noted where the launch is made; a replayed graph reports what it was captured with.
-    struct LevelBuild {
-        int32_t form = LM_NONE, builder = 0, split = 0, allty = 0, packed = 0;
-    };
-    LevelBuild level_build[SBM_MAX_LEVELS];
-    void note_level_build(int l, LmForm f, int builder, int split = 0, int allty = 0) { level_build[l] = LevelBuild{(int32_t)f, builder, split, allty, 0}; }
-    void note_coarse_form(int kind, int P, bool wide, int dw)
-    {
-        coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw;
-    }
     int coarse_mode = tuning().coarse;      // 0 auto (bit planes), 1 four waves per item, 2 one wave per item, 3 bit planes, 4 byte kernels by launch size (SBM_COARSE: A/B knob)
     // hipGraph replay of an entry point's launches (sbm_set_graph_mode): -1 auto (default) = the batch entry point and the
     // template-loop entry point replay a captured graph once the caller keeps several calls in flight
@@ -548,7 +514,7 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
             if (c->d_src0.p)
                 if (int e = c->d_sparse_items.ensure(256, true)) return e;
         }
-        c->forms[l].forget();
+        c->rec.forms[l].forget();
     }
     c->d_blm.release(); // fresh, zeroed: the tails of the bit planes must read as 0 too
     if (int e = c->d_blm.ensure(B * 2 * c->lm_stride[c->L - 1] + 256, true)) return e;
@@ -561,8 +527,8 @@ int ensure_geometry(sbm_ctx* c, int rows, int cols, int channels, int frames = 1
     c->mask_frames = (int)MB;
     c->channels = channels;
     c->foff_dirty = true;
-    c->levels_valid = 0;
-    c->map0_whole = true; // nothing resident: nothing to complete
+    c->rec.levels_valid = 0;
+    c->rec.map0_whole = true; // nothing resident: nothing to complete
     c->drop_graphs(); // captured launches hold the old buffer addresses
     return 0;
 }
@@ -586,9 +552,9 @@ int ensure_level(sbm_ctx* c, int l, int rows, int cols)
         c->d_rects.release();
         c->d_items.release();
         c->items_cap = 0;
-        c->map0_whole = true; // the caller sets the whole map
+        c->rec.map0_whole = true; // the caller sets the whole map
     }
-    c->forms[l].forget();
+    c->rec.forms[l].forget();
     if (l == c->L - 1) {
         c->d_blm.release();
         if (int e = c->d_blm.ensure((size_t)2 * c->lm_stride[l] + 256, true)) return e;
@@ -787,7 +753,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
         else if (ch == 1) SBM_LAUNCH(c, "k_quantize", (k_source_lines<1>), g, dim3(256), 0, s, a);
         else SBM_LAUNCH(c, "k_quantize", (k_source_lines<3>), g, dim3(256), 0, s, a);
         HIP_TRY(hipGetLastError());
-        c->source_form = 2;
+        c->rec.source_form = 2;
         return 0;
     }
     if (hs) {
@@ -840,11 +806,11 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
                 a.list_cap = form->list_cap;
                 a.slots = form->slots;
             }
-            c->sparse_items[0] = form->need_rects ? 2 : 1;
-            c->sparse_items[1] = -1;
-            c->sparse_items[2] = a.slots > 0 ? frames * a.slots + quantize_slots_packed(a) : quantize_stream_items(a);
-            c->sparse_items_pending = form->item_count != nullptr;
-            c->sparse_list[0] = a.slots > 0, c->sparse_list[1] = a.slots;
+            c->rec.sparse_items[0] = form->need_rects ? 2 : 1;
+            c->rec.sparse_items[1] = -1;
+            c->rec.sparse_items[2] = a.slots > 0 ? frames * a.slots + quantize_slots_packed(a) : quantize_stream_items(a);
+            c->rec.sparse_items_pending = form->item_count != nullptr;
+            c->rec.sparse_list[0] = a.slots > 0, c->rec.sparse_list[1] = a.slots;
         }
         const dim3 g((unsigned)(a.slots > 0 ? quantize_slots_groups(a) : (quantize_stream_items(a) + 3) / 4));
         // (one timing name for all three forms: the launches of the gradient stage)
@@ -878,7 +844,7 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
 #undef SBM_QS_PTRS
 #undef SBM_QS
         HIP_TRY(hipGetLastError());
-        if (stage == QS_SOURCE) c->source_form = 1;
+        if (stage == QS_SOURCE) c->rec.source_form = 1;
         return 0;
     }
     if (band && !tile_band) return fail(SBM_ERR_INVALID, "a row band needs the streaming gradient kernel (cols %% 4 == 0, no float outputs)");
@@ -990,7 +956,7 @@ int launch_lm_level(sbm_ctx* c, hipStream_t s, int l, LmForm f)
     a.lv[0] = lm_level_args(c, l, f, 1, 0, &blocks);
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3((unsigned)blocks), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
-    c->note_level_build(l, f, 1, a.lv[0].split, a.lv[0].allty);
+    c->rec.note_level_build(l, f, 1, a.lv[0].split, a.lv[0].allty);
     return 0;
 }
 
@@ -1008,7 +974,7 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
         dim3 grid((W + LM_GX - 1) / LM_GX, H);
         SBM_LAUNCH(c, "k_build_lm", k_build_lm, grid, dim3(256), smem, s, d_q, rows, cols, T, W, H, d_lm, lm_stride);
         HIP_TRY(hipGetLastError());
-        c->note_level_build(l, LM_PLANES8, 3);
+        c->rec.note_level_build(l, LM_PLANES8, 3);
         return 0;
     }
     // large strides: unfused path through scratch (spread, 8 response maps)
@@ -1023,7 +989,7 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
     for (int o = 0; o < 8; ++o)
         hipLaunchKernelGGL(k_linearize, dim3(blocks), dim3(256), 0, s, maps + o * n, rows, cols, T, d_lm + o * lm_stride);
     HIP_TRY(hipGetLastError());
-    c->note_level_build(l, LM_PLANES8, 4);
+    c->rec.note_level_build(l, LM_PLANES8, 4);
     return 0;
 }
 
@@ -1032,9 +998,9 @@ int launch_build_lm(sbm_ctx* c, hipStream_t s, int l)
 int ensure_level0_map(sbm_ctx* c, hipStream_t s);
 int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
 {
-    const LmForm src = full_lm_source(c->forms[l]);
+    const LmForm src = full_lm_source(c->rec.forms[l]);
     // nothing current: the level's strips were built sparsely (or nothing was built yet: not resident, nothing to do)
-    if (src == LM_PLANES8 || (src == LM_NONE && l >= c->levels_valid)) return 0;
+    if (src == LM_PLANES8 || (src == LM_NONE && l >= c->rec.levels_valid)) return 0;
     if (l == 0 && src != LM_SPREAD && src != LM_SPREAD_STRIP) // built from the map, which a sparse call left in pieces
         if (int e = ensure_level0_map(c, s)) return e;
     if (src == LM_SPREAD || src == LM_SPREAD_STRIP) {
@@ -1044,7 +1010,7 @@ int ensure_full_lm(sbm_ctx* c, int l, hipStream_t s)
                            c->d_lm[l].as<uint8_t>(), c->lm_stride[l], src == LM_SPREAD_STRIP ? 1 : 0, c->cols[l] / T, c->rows[l] / T);
         HIP_TRY(hipGetLastError());
     } else if (int e = launch_build_lm(c, s, l)) return e;
-    c->forms[l].planes8 = true;
+    c->rec.forms[l].planes8 = true;
     return 0;
 }
 
@@ -1268,7 +1234,7 @@ int launch_lm_any(sbm_ctx* c, hipStream_t s, const BuildPlan& plan, int frames, 
     }
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_any, dim3((unsigned)blocks, frames), dim3(LMA_THREADS), (size_t)smem, s, a);
     HIP_TRY(hipGetLastError());
-    for (int l = 0; l < c->L; ++l) c->note_level_build(l, plan.form[l], 2);
+    for (int l = 0; l < c->L; ++l) c->rec.note_level_build(l, plan.form[l], 2);
     return 0;
 }
 
@@ -1278,11 +1244,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
 {
     PyramidCursor cur{src0, mask0};
     const int frames = src0.frames;
-    c->last_frames = frames;
-    c->source_form = 0;
-    c->sparse_items[0] = 0, c->sparse_items[1] = -1, c->sparse_items[2] = 0;
-    c->sparse_items_pending = false;
-    c->sparse_list[0] = c->sparse_list[1] = 0;
+    c->rec.begin_build(frames);
     const bool all_rows = all_rows_ok(c);
     c->counters_fresh = false;
     c->call_counted = false;
@@ -1372,7 +1334,7 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
         HIP_TRY(hipGetLastError());
         for (int i = 0; i < a.n_levels; ++i) { // (a.lv[] is coarsest first and skips a sparse level 0)
             const int l = c->L - 1 - i;
-            c->note_level_build(l, plan.form[l], 1, a.lv[i].split, a.lv[i].allty);
+            c->rec.note_level_build(l, plan.form[l], 1, a.lv[i].split, a.lv[i].allty);
         }
     } else if (pin.any_batch) {
         if (int e = launch_lm_any(c, s, plan, frames, reset_count)) return e;
@@ -1383,12 +1345,12 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
         SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes_spread, dim3((n_dwords + 255) / 256, frames), dim3(256), 0, s, c->d_lmc[l].as<uint8_t>(),
                    c->lm_stride[l], c->lm_stride[l], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[l]) / 4, n_dwords);
         HIP_TRY(hipGetLastError());
-        c->level_build[l].packed = 1;
+        c->rec.level_build[l].packed = 1;
     }
-    record_build(c->forms, c->L, plan);
-    c->levels_valid = c->L;
-    c->map0_whole = !plan.sparse_gradient;
-    if (plan.sparse_gradient) c->src0_ch = c->channels;
+    record_build(c->rec.forms, c->L, plan);
+    c->rec.levels_valid = c->L;
+    c->rec.map0_whole = !plan.sparse_gradient;
+    if (plan.sparse_gradient) c->rec.src0_ch = c->channels;
     return 0;
 }
 
@@ -1396,9 +1358,9 @@ int enqueue_pyramid(sbm_ctx* c, hipStream_t s, const FrameSource& src0, const Ma
 // gradient launch on the retained source.  On the reader's stream, outside any capture.
 int ensure_level0_map(sbm_ctx* c, hipStream_t s)
 {
-    if (c->map0_whole || c->levels_valid < 1) return 0;
-    const int rows = c->rows[0], cols = c->cols[0], ch = c->src0_ch;
-    if (!c->d_src0.p || (size_t)c->last_frames * rows * cols * ch > c->d_src0.cap) return fail(SBM_ERR_STATE, "level 0's source is not retained");
+    if (c->rec.map0_whole || c->rec.levels_valid < 1) return 0;
+    const int rows = c->rows[0], cols = c->cols[0], ch = c->rec.src0_ch;
+    if (!c->d_src0.p || (size_t)c->rec.last_frames * rows * cols * ch > c->d_src0.cap) return fail(SBM_ERR_STATE, "level 0's source is not retained");
     // The copy this reads is the one of the last match call enqueued, which stores it unless a later call is enqueued before its
     // source pass runs (source_pass_retains).  Wait for that call here: it then ran as the last one enqueued and has stored its
     // copy, whatever the host enqueues behind this reader.  The context's own event stands for the call: the caller's stream may
@@ -1408,12 +1370,12 @@ int ensure_level0_map(sbm_ctx* c, hipStream_t s)
         HIP_TRY(hipDeviceSynchronize());
     }
     QuantizeLaunch q;
-    q.src = retained_frames(c, ch, c->last_frames);
+    q.src = retained_frames(c, ch, c->rec.last_frames);
     q.rows = rows, q.cols = cols;
     q.weak = c->cfg.weak_threshold;
     q.out = c->d_quant[0].as<uint8_t>();
     if (int e = launch_quantize(c, s, q)) return e;
-    c->map0_whole = true;
+    c->rec.map0_whole = true;
     return 0;
 }
 
@@ -1442,7 +1404,7 @@ bool templates_dirty(const sbm_ctx* c, float threshold) { return !c->have_thr ||
 // ... or the geometry, the batch size or the pyramid are about to change
 bool match_dirty(const sbm_ctx* c, int rows, int cols, int channels, int frames, float threshold)
 {
-    return !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->levels_valid == c->L && frames <= c->batch) ||
+    return !(c->channels == channels && c->rows[0] == rows && c->cols[0] == cols && c->rec.levels_valid == c->L && frames <= c->batch) ||
            templates_dirty(c, threshold);
 }
 
@@ -1523,13 +1485,13 @@ int begin_host_match(sbm_ctx* c, const MatchCall& m, bool also_dirty = false)
 int pack_bitplanes(sbm_ctx* c, hipStream_t s, int frames)
 {
     const int lc = c->L - 1, T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
-    if (!c->forms[lc].planes8) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", lc);
+    if (!c->rec.forms[lc].planes8) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", lc);
     const int n_dwords = (int)(((int64_t)T * T * W * H + 31) / 32);
     SBM_LAUNCH(c, "k_pack_bitplanes", k_pack_bitplanes, dim3((n_dwords + 255) / 256, 8, frames), dim3(256), 0, s, c->d_lm[lc].as<uint8_t>(),
                c->lm_stride[lc], (int64_t)8 * c->lm_stride[lc], c->d_blm.as<uint32_t>(), (int64_t)(2 * c->lm_stride[lc]) / 4, n_dwords);
     HIP_TRY(hipGetLastError());
-    c->forms[lc].bit_planes = true;
-    c->level_build[lc].packed = 2;
+    record_pack(c->rec.forms[lc]);
+    c->rec.level_build[lc].packed = 2;
     return 0;
 }
 
@@ -1539,7 +1501,7 @@ int pack_bitplanes(sbm_ctx* c, hipStream_t s, int frames)
 int ensure_coarse_planes(sbm_ctx* c, hipStream_t s)
 {
     if (!coarse_on_bits(c)) return ensure_full_lm(c, c->L - 1, s);
-    return c->forms[c->L - 1].bit_planes ? 0 : pack_bitplanes(c, s, 1);
+    return c->rec.forms[c->L - 1].bit_planes ? 0 : pack_bitplanes(c, s, 1);
 }
 
 // positions of the coarsest level's W x H grid a template is scored at (the host's side of the device's template_positions)
@@ -1609,7 +1571,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
         // a template's span are never candidates); SBM_COARSE / sbm_set_coarse_mode pick a byte kernel instead.
         const PlanInputs pin = plan_inputs(c);
         const bool bits = coarse_on_bits(pin);
-        if (!bits && !c->forms[lc].planes8) {
+        if (!bits && !c->rec.forms[lc].planes8) {
             // a byte kernel after a match call that built the bit planes only (the stage entry point with a threshold < 0)
             if (frames > 1) return fail(SBM_ERR_STATE, "the coarsest level's response planes are not built");
             if (int e = ensure_full_lm(c, lc, s)) return e;
@@ -1617,7 +1579,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
         int max_nf = 0, bits_dw = 1;
         if (bits) {
             for (int32_t t : c->h_active) max_nf = std::max(max_nf, c->h_tls[(size_t)t * L + lc].nf);
-            if (coarse_packs_planes(pin, c->forms[lc], false))
+            if (coarse_packs_planes(pin, c->rec.forms[lc], false))
                 if (int e = pack_bitplanes(c, s, frames)) return e;
             chunks = coarse_chunks(bits_max_npos, CB_POS);
             // Two dwords (64 positions) per lane -- half as many, twice as long work items -- when the one-dword items would
@@ -1634,7 +1596,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             if (bits_block) {
                 const int chunks1 = coarse_chunks(bits_max_npos, CB_POS);
 #define SBM_COARSE_BITS_BLOCK(P_)                                                                                                    \
-                c->note_coarse_form(4, P_, false, 0);                                                                                 \
+                c->rec.note_coarse_form(4, P_, false, 0);                                                                                 \
                 SBM_LAUNCH(c, "k_similarity_coarse", (k_similarity_coarse_bits_block<P_>), dim3(chunks1, cnt, frames), dim3(512), 0, s,   \
                            c->d_blm.as<uint32_t>(), c->lm_stride[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(), c->d_soff.as<int32_t>(),   \
                            c->d_citems.as<CoarseItem>() + first, cnt, c->d_rawkeep.as<int32_t>(), c->d_class.as<int32_t>(),             \
@@ -1652,7 +1614,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
                 if (bits_dw == 2) SBM_COARSE_BITS_D(P_, W_, 2); else SBM_COARSE_BITS_D(P_, W_, 1)
 #define SBM_COARSE_BITS_D(P_, W_, D_)                                                                                                \
                 do {                                                                                                                  \
-                c->note_coarse_form(3, P_, W_, D_);                                                                                   \
+                c->rec.note_coarse_form(3, P_, W_, D_);                                                                                   \
                 SBM_LAUNCH(c, "k_similarity_coarse", (k_similarity_coarse_bits<P_, W_, D_>), dim3(chunks, (cnt + 3) / 4, frames), dim3(256), 0, s, \
                            c->d_blm.as<uint32_t>(), c->lm_stride[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(), c->d_soff.as<int32_t>(),   \
                            c->d_citems.as<CoarseItem>() + first, c->d_cfoff.as<int32_t>() + (size_t)first * 64, cnt,                     \
@@ -1670,7 +1632,7 @@ int enqueue_coarse(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap,
             // large launches: one wave per (chunk, template, frame); small ones (a single frame with a few hundred
             // templates): four waves share an item's features so that enough loads are in flight
             const bool per_wave = c->coarse_mode == 2 || (c->coarse_mode != 1 && (int64_t)chunks * cnt * frames >= 8192);
-            c->note_coarse_form(per_wave ? 2 : 1, 0, false, 0);
+            c->rec.note_coarse_form(per_wave ? 2 : 1, 0, false, 0);
             if (per_wave)
                 SBM_LAUNCH(c, "k_similarity_coarse", k_similarity_coarse_wave, dim3(chunks, (cnt + 3) / 4, frames), dim3(256), 0, s,
                            c->d_lm[lc].as<uint8_t>(), c->lm_stride[lc], c->rows[lc], c->cols[lc], T, W, H, L, lc, c->d_tls.as<DevTL>(),
@@ -1717,7 +1679,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
         int order = c->local_order >= 0 ? c->local_order : (planes > (32 << 20) ? 2 : 0);
         const dim3 local_dim = order == 2 ? dim3((unsigned)(std::min(frames, 64) * local_grid), (unsigned)((frames + 63) / 64))
                                           : dim3(frames, local_grid);
-        const LmForm reads = l == 0 && sparse0 ? LM_BIT_STRIPS : refine_reads(c->forms[l]);
+        const LmForm reads = l == 0 && sparse0 ? LM_BIT_STRIPS : refine_reads(c->rec.forms[l]);
         if (reads == LM_NONE) return fail(SBM_ERR_STATE, "linear memories of level %d are not built", l);
         const int local_waves = tuning().local_waves; // 4 or 16
         const bool small_blocks = local_waves ? local_waves == 4 : frames >= 4;
@@ -1753,7 +1715,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
             if (order == 2) SBM_LOCAL_BITS(2);
             else SBM_LOCAL_BITS(0);
 #undef SBM_LOCAL_BITS
-            c->note_refine_form(l, reads, 1, order, false, l == 0 && sparse0, slots);
+            c->rec.note_refine_form(l, reads, 1, order, false, l == 0 && sparse0, slots);
         }
         else if (reads == LM_SPREAD_STRIP) { SBM_LOCAL(2, c->d_lmc[l].as<uint8_t>(), 1); }
         else if (reads == LM_SPREAD) { SBM_LOCAL(1, c->d_lmc[l].as<uint8_t>(), 1); }
@@ -1762,7 +1724,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
 #undef SBM_LOCAL_LW
 #undef SBM_LOCAL_O
 #undef SBM_LOCAL_T
-        if (reads != LM_BIT_STRIPS) c->note_refine_form(l, reads, small_blocks ? 4 : LOCAL_WAVES, order, reads == LM_SPREAD_STRIP && T == 8, false, local_grid);
+        if (reads != LM_BIT_STRIPS) c->rec.note_refine_form(l, reads, small_blocks ? 4 : LOCAL_WAVES, order, reads == LM_SPREAD_STRIP && T == 8, false, local_grid);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -1773,7 +1735,7 @@ int enqueue_local(sbm_ctx* c, hipStream_t s, sbm_match_rec* d_out, int64_t cap, 
 // from the orientation map, and the loop reads that).
 bool sparse_refine(const sbm_ctx* c)
 {
-    return c->L == 2 && c->levels_valid == c->L && refine_reads(c->forms[0]) == LM_NONE &&
+    return c->L == 2 && c->rec.levels_valid == c->L && refine_reads(c->rec.forms[0]) == LM_NONE &&
            plan_build(plan_inputs(c), all_rows_ok(c), true).form[0] == LM_BIT_STRIPS_SPARSE;
 }
 
@@ -1806,7 +1768,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
 {
     const int T = c->cfg.T[0], W = c->cols[0] / T, H = c->rows[0] / T, n_tiles = refine_tile_count(W, H), n_bands = refine_band_count(c->rows[0]);
     // the record of need rectangles only where this call's gradient launch reads it (the flags alone serve the strip builder)
-    int32_t* const rects = !c->map0_whole && tuning().sparse_rects ? c->d_rects.as<int32_t>() : nullptr;
+    int32_t* const rects = !c->rec.map0_whole && tuning().sparse_rects ? c->d_rects.as<int32_t>() : nullptr;
     // ... and the lists of working items where that launch runs from them
     const SparseListPlan lp = rects ? sparse_list_plan(c, c->sparse_src) : SparseListPlan{};
     MarkList ml;
@@ -1820,7 +1782,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
                (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles, rects, n_bands, ml);
     HIP_TRY(hipGetLastError());
-    if (!c->map0_whole) {
+    if (!c->rec.map0_whole) {
         // the call ran the source pass only (BuildPlan::sparse_gradient): level 0's gradient stage now, from the retained
         // source, in the work items whose output the flagged tiles' builders load.  The map stays in pieces (map0_whole).
         QSForm form{QS_SPARSE, nullptr, 0, c->d_tiles.as<uint8_t>(), n_tiles, T, W, H};
@@ -1857,7 +1819,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
     a.call_enqueued = c->d_enqueued;
     SBM_LAUNCH(c, "k_build_lm", k_build_lm_rows, dim3(blocks, frames), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
-    c->note_level_build(0, LM_BIT_STRIPS_SPARSE, 1, a.lv[0].split, a.lv[0].allty);
+    c->rec.note_level_build(0, LM_BIT_STRIPS_SPARSE, 1, a.lv[0].split, a.lv[0].allty);
     return 0;
 }
 
@@ -1880,7 +1842,7 @@ int ensure_local_forms(sbm_ctx* c, hipStream_t s)
     const PlanInputs pin = plan_inputs(c);
     if (int e = ensure_level0_map(c, s)) return e; // every rebuild below reads the orientation maps
     for (int l = 0; l < c->L - 1; ++l) {
-        LevelForms& f = c->forms[l];
+        LevelForms& f = c->rec.forms[l];
         if (refine_reads(f) == LM_NONE) {
             // nothing current: a match call built the level's strips sparsely.  Whole strips from the orientation map, or the
             // response planes where strips are not wanted (any more)
@@ -1911,7 +1873,7 @@ int ensure_local_forms(sbm_ctx* c, hipStream_t s)
 // matchClass over the active templates; results into d_out/d_count (device)
 int enqueue_templates(sbm_ctx* c, hipStream_t s, float threshold, sbm_match_rec* d_out, int64_t cap, int32_t* d_count)
 {
-    if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
+    if (c->rec.levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->rec.levels_valid, c->L);
     if (int e = prepare_templates(c, threshold, cap)) return e;
     if (int e = ensure_local_forms(c, s)) return e;
     return enqueue_loop(c, s, d_out, cap, d_count, 1, /* raised: no gradient launches around a template-loop-only call */ true);
@@ -1975,11 +1937,7 @@ int graph_replay(sbm_ctx* c, const GraphKey& key, hipStream_t s, bool* launched,
             (void)hipGraphDestroy(ge.graph);
             return fail(SBM_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(he));
         }
-        memcpy(ge.coarse_form, c->coarse_form, sizeof ge.coarse_form);
-        ge.source_form = c->source_form;
-        memcpy(ge.refine_form, c->refine_form, sizeof ge.refine_form);
-        static_assert(sizeof ge.level_build == sizeof c->level_build, "LevelBuild is five int32");
-        memcpy(ge.level_build, c->level_build, sizeof ge.level_build);
+        ge.rec = c->rec; // (the capture wrote it as it enqueued)
         c->graphs.push_back(ge);
         hit = &c->graphs.back();
     } else {
@@ -1987,12 +1945,7 @@ int graph_replay(sbm_ctx* c, const GraphKey& key, hipStream_t s, bool* launched,
     }
     hit->last_use = ++c->graph_clock;
     HIP_TRY(hipGraphLaunch(hit->exec, s));
-    memcpy(c->coarse_form, hit->coarse_form, sizeof c->coarse_form);
-    c->source_form = hit->source_form;
-    memcpy(c->refine_form, hit->refine_form, sizeof c->refine_form);
-    // the builds: a match call's graph made every level; the template loop's (kind < 0) only level 0's sparse strips, if any
-    if (key.kind >= 0) memcpy(c->level_build, hit->level_build, sizeof c->level_build);
-    else if (hit->level_build[0][0] == LM_BIT_STRIPS_SPARSE) memcpy(&c->level_build[0], hit->level_build[0], sizeof c->level_build[0]);
+    c->rec.replayed(hit->rec, key.kind);
     *launched = true;
     return 0;
 }
@@ -2009,25 +1962,6 @@ int end_capture(hipStream_t m, int rc, hipGraph_t* graph)
     if (e != hipSuccess || !g) return fail(SBM_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
     *graph = g;
     return 0;
-}
-
-// what a match entry point leaves resident, for the calls that replay its launches as a captured graph
-// sparse_grad: the captured call made level 0's map sparsely (its graph key says so)
-// any_batch: the captured call was a batch through k_build_lm_any (PlanInputs::any_batch)
-// sparse_rects: ... with its work items taken from the record of need rectangles
-// sparse_slots: ... by that many waves per frame from the lists of working items (0: a wave per item)
-void record_match(sbm_ctx* c, bool one_launch, bool sparse_grad, bool any_batch, bool sparse_rects = false, int sparse_slots = 0)
-{
-    c->sparse_list[0] = sparse_slots > 0, c->sparse_list[1] = sparse_slots;
-    c->sparse_items[0] = sparse_grad ? (sparse_rects ? 2 : 1) : 0;
-    c->sparse_items[1] = -1; // a replay counts nothing
-    c->sparse_items_pending = false;
-    PlanInputs pin = plan_inputs(c);
-    pin.any_batch = any_batch;
-    record_match(c->forms, pin, one_launch, c->h_active.empty());
-    c->levels_valid = c->L;
-    c->map0_whole = !sparse_grad;
-    if (sparse_grad) c->src0_ch = c->channels;
 }
 
 // A match call is counted on the device by one thread of one of its launches, behind its source pass (CALL_EXECUTED,
@@ -2070,6 +2004,7 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
     const int L = c->L;
     hipStream_t st = c->stream, sd = c->side;
     PyramidCursor cur{m.src, m.mask}; // one frame
+    c->rec.begin_build(1);
     bool forked = false;
     for (int l = 0; l < L; ++l) {
         if (int e = enqueue_gradient_level(c, st, l, true, cur, 0, c->rows[l])) return e;
@@ -2079,8 +2014,9 @@ int enqueue_match_forked(sbm_ctx* c, const MatchCall& m)
         forked = forked || fork;
         if (int e = launch_build_lm(c, fork ? sd : st, l)) return e;
     }
-    record_build(c->forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
-    c->map0_whole = true;
+    record_build(c->rec.forms, L, plan_build(plan_inputs(c), false, true)); // the generic builder: the 8-plane form at every level
+    c->rec.levels_valid = L;
+    c->rec.map0_whole = true;
     c->call_counted = false;
     if (int e = enqueue_call_executed(c, st)) return e;
     if (int e = enqueue_coarse(c, st, m.out, m.cap, m.counts)) return e;
@@ -2101,7 +2037,7 @@ GraphKey graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     key.mirror_out = c->mirror_out, key.mirror_count = c->mirror_count;
     key.kind = kind;
     // (the template loop has no frames: what its launches depend on instead is the form every level is held in)
-    if (kind < 0) key.forms_signature = forms_signature(c->forms, c->L);
+    if (kind < 0) key.forms_signature = forms_signature(c->rec.forms, c->L);
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
     key.sparse_grad = kind > 0 && plans_sparse_gradient(c, m.src, m.mask, nullptr, false);
     key.sparse_rects = key.sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
@@ -2117,7 +2053,7 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
 {
     if (kind != 1 && graph_wanted(c, kind)) {
         if (kind < 0) {
-            if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->levels_valid, c->L);
+            if (c->rec.levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built (%d of %d levels)", c->rec.levels_valid, c->L);
             if (int e = prepare_templates(c, m.thr, m.cap)) return e;
             // the forms rebuilt here read the orientation maps that the caller's stream may still be writing (a match call
             // enqueued just before): launched on s, as enqueue_templates does, they are ordered after it without a host wait.
@@ -2137,13 +2073,8 @@ int match_or_replay(sbm_ctx* c, hipStream_t s, const MatchCall& m, int kind)
             }))
             return e;
         if (launched) {
-            // what the replayed call leaves resident: the forked DAG is the generic builder's; a batch is the one-launch
-            // builder's where that takes every level, else the batched any-stride builder's; the template loop builds nothing
-            if (kind >= 0) {
-                record_match(c, kind > 0 && all_rows_ok(c), key.sparse_grad, kind > 1 && any_batch_ok(c), key.sparse_rects, key.sparse_slots);
-                c->last_frames = m.src.frames;
-                call_enqueued(c, s); // (the graph holds the launch that counts the call on the device)
-            }
+            // (graph_replay has restored the record the capture left; the graph holds the launch that counts the call on the device)
+            if (kind >= 0) call_enqueued(c, s);
             return 0;
         }
     }

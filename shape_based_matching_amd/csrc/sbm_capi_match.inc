@@ -793,7 +793,7 @@ int sbm_build_pyramid(sbm_ctx* c, const uint8_t* img, int32_t rows, int32_t cols
 int sbm_set_quantized(sbm_ctx* c, int32_t level, const uint8_t* q, int32_t rows, int32_t cols)
 {
     if (!c || !q || level < 0 || level >= c->L) return fail(SBM_ERR_INVALID, "bad level");
-    if (level > c->levels_valid) return fail(SBM_ERR_STATE, "levels must be set from 0 upwards");
+    if (level > c->rec.levels_valid) return fail(SBM_ERR_STATE, "levels must be set from 0 upwards");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = order_after_caller_work(c)) return e;
     if (int e = ensure_level(c, level, rows, cols)) return e;
@@ -803,16 +803,16 @@ int sbm_set_quantized(sbm_ctx* c, int32_t level, const uint8_t* q, int32_t rows,
         if (int e = ensure_level0_map(c, c->stream)) return e;
     HIP_TRY(hipMemcpyAsync(c->d_quant[level].p, q, (size_t)rows * cols, hipMemcpyHostToDevice, c->stream));
     if (int e = launch_build_lm(c, c->stream, level)) return e;
-    c->forms[level].set(LM_PLANES8);
+    c->rec.forms[level].set(LM_PLANES8);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->levels_valid = std::max(c->levels_valid, level + 1);
+    c->rec.levels_valid = std::max(c->rec.levels_valid, level + 1);
     if (c->profiling) collect_timings(c);
     return 0;
 }
 
 int sbm_get_quantized(sbm_ctx* c, int32_t level, uint8_t* out)
 {
-    if (!c || !out || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
+    if (!c || !out || level < 0 || level >= c->rec.levels_valid) return fail(SBM_ERR_STATE, "level not resident");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = order_after_caller_work(c)) return e;
     if (level == 0)
@@ -825,8 +825,8 @@ int sbm_get_quantized(sbm_ctx* c, int32_t level, uint8_t* out)
 int sbm_get_quantized_frame(sbm_ctx* c, int32_t level, int32_t frame, uint8_t* out)
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
-    if (level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
-    if (frame < 0 || frame >= c->last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->last_frames);
+    if (level < 0 || level >= c->rec.levels_valid) return fail(SBM_ERR_STATE, "level not resident");
+    if (frame < 0 || frame >= c->rec.last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->rec.last_frames);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     HIP_TRY(hipDeviceSynchronize()); // the batch may have been built on the caller's stream
     if (level == 0) { // a sparse call left the map in pieces: the whole launch on the retained source, once
@@ -840,7 +840,7 @@ int sbm_get_quantized_frame(sbm_ctx* c, int32_t level, int32_t frame, uint8_t* o
 
 int sbm_get_linear_memories(sbm_ctx* c, int32_t level, uint8_t* out, int64_t cap_bytes, int64_t* lm_stride)
 {
-    if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
+    if (!c || level < 0 || level >= c->rec.levels_valid) return fail(SBM_ERR_STATE, "level not resident");
     if (lm_stride) *lm_stride = c->lm_stride[level];
     if (!out) return 0;
     const int64_t need = 8 * c->lm_stride[level];
@@ -856,12 +856,12 @@ int sbm_get_linear_memories(sbm_ctx* c, int32_t level, uint8_t* out, int64_t cap
 int sbm_get_coarse_bitplanes(sbm_ctx* c, int32_t frame, uint8_t* out, int64_t cap_bytes)
 {
     if (!c || !out || frame < 0 || frame >= c->batch) return fail(SBM_ERR_INVALID, "bad argument");
-    if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
+    if (c->rec.levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
     const int64_t need = 2 * c->lm_stride[c->L - 1];
     if (cap_bytes < need) return fail(SBM_ERR_CAPACITY, "need %lld bytes", (long long)need);
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     HIP_TRY(hipDeviceSynchronize());
-    if (!c->forms[c->L - 1].bit_planes || !c->d_blm.p) return fail(SBM_ERR_STATE, "the last call did not build the coarsest level's bit planes");
+    if (!c->rec.forms[c->L - 1].bit_planes || !c->d_blm.p) return fail(SBM_ERR_STATE, "the last call did not build the coarsest level's bit planes");
     HIP_TRY(hipMemcpy(out, c->d_blm.as<uint8_t>() + (size_t)frame * need, (size_t)need, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -869,7 +869,7 @@ int sbm_get_coarse_bitplanes(sbm_ctx* c, int32_t frame, uint8_t* out, int64_t ca
 int sbm_get_coarse_form(sbm_ctx* c, int32_t out[4])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
-    memcpy(out, c->coarse_form, sizeof c->coarse_form);
+    memcpy(out, c->rec.coarse_form, sizeof c->rec.coarse_form);
     return 0;
 }
 
@@ -877,14 +877,14 @@ int sbm_get_refine_form(sbm_ctx* c, int32_t level, int32_t out[6])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
     if (level < 0 || level >= c->L - 1) return fail(SBM_ERR_INVALID, "level %d is no refinement level", level);
-    memcpy(out, c->refine_form[level], sizeof c->refine_form[level]);
+    memcpy(out, c->rec.refine_form[level], sizeof c->rec.refine_form[level]);
     return 0;
 }
 
 int sbm_get_source_form(sbm_ctx* c, int32_t* out)
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
-    *out = c->source_form;
+    *out = c->rec.source_form;
     return 0;
 }
 
@@ -902,19 +902,19 @@ int sbm_get_source_retention(sbm_ctx* c, int32_t out[2])
 int sbm_get_sparse_items(sbm_ctx* c, int32_t out[3])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
-    if (c->sparse_items_pending) { // the profiled launch counted on the device: fetch it once
+    if (c->rec.sparse_items_pending) { // the profiled launch counted on the device: fetch it once
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(&c->sparse_items[1], c->d_sparse_items.p, sizeof(int32_t), hipMemcpyDeviceToHost));
-        c->sparse_items_pending = false;
+        HIP_TRY(hipMemcpy(&c->rec.sparse_items[1], c->d_sparse_items.p, sizeof(int32_t), hipMemcpyDeviceToHost));
+        c->rec.sparse_items_pending = false;
     }
-    memcpy(out, c->sparse_items, sizeof c->sparse_items);
+    memcpy(out, c->rec.sparse_items, sizeof c->rec.sparse_items);
     return 0;
 }
 
 int sbm_get_sparse_list(sbm_ctx* c, int32_t out[2])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
-    memcpy(out, c->sparse_list, sizeof c->sparse_list);
+    memcpy(out, c->rec.sparse_list, sizeof c->rec.sparse_list);
     return 0;
 }
 
@@ -922,8 +922,8 @@ int sbm_get_level_build(sbm_ctx* c, int32_t level, int32_t out[6])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
     if (level < 0 || level >= c->L) return fail(SBM_ERR_INVALID, "level %d of %d", level, c->L);
-    const LevelForms& f = c->forms[level];
-    const sbm_ctx::LevelBuild& b = c->level_build[level];
+    const LevelForms& f = c->rec.forms[level];
+    const LevelBuild& b = c->rec.level_build[level];
     out[0] = (f.planes8 ? 1 : 0) | (f.spread ? 2 : 0) | (f.spread && f.spread_strip ? 4 : 0) | (f.bit_strips ? 8 : 0) | (f.bit_planes ? 16 : 0);
     out[1] = b.form, out[2] = b.builder, out[3] = b.split, out[4] = b.allty, out[5] = b.packed;
     return 0;
@@ -936,7 +936,7 @@ int sbm_get_level_stored(sbm_ctx* c, int32_t level, int32_t frame, int32_t which
         return fail(SBM_ERR_INVALID, "no buffer %d at level %d", which, level);
     const DevBuf& buf = which == 0 ? c->d_lm[level] : which == 1 ? c->d_lmc[level] : which == 2 ? c->d_lbits[level] : c->d_tiles;
     if (!buf.p) return fail(SBM_ERR_STATE, "buffer %d of level %d is not allocated", which, level);
-    if (frame < 0 || frame >= c->last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->last_frames);
+    if (frame < 0 || frame >= c->rec.last_frames) return fail(SBM_ERR_INVALID, "frame %d outside the last batch (%d frames)", frame, c->rec.last_frames);
     const int T = c->cfg.T[level];
     const int64_t need = which == 0   ? 8 * c->lm_stride[level]
                          : which == 1 ? c->lm_stride[level]
@@ -954,7 +954,7 @@ int sbm_get_level_stored(sbm_ctx* c, int32_t level, int32_t frame, int32_t which
 
 int sbm_level_dims(sbm_ctx* c, int32_t level, int32_t* rows, int32_t* cols)
 {
-    if (!c || level < 0 || level >= c->levels_valid) return fail(SBM_ERR_STATE, "level not resident");
+    if (!c || level < 0 || level >= c->rec.levels_valid) return fail(SBM_ERR_STATE, "level not resident");
     if (rows) *rows = c->rows[level];
     if (cols) *cols = c->cols[level];
     return 0;

@@ -259,7 +259,7 @@ extern "C" {
 int sbm_coarse_bytes(sbm_ctx* c, int64_t* bytes)
 {
     if (!c || !bytes) return fail(SBM_ERR_INVALID, "null argument");
-    if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
+    if (c->rec.levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
     if (int e = ensure_host_fxy(c)) return e; // (a device install leaves the features on the device)
     const int lc = c->L - 1, T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
     int64_t total = 0;

@@ -207,7 +207,7 @@ int sbm_linearize(sbm_ctx* c, const uint8_t* map, int32_t rows, int32_t cols, in
 int sbm_similarity(sbm_ctx* c, int32_t t, uint16_t* dst)
 {
     if (!c || !dst || t < 0 || t >= c->n_templates) return fail(SBM_ERR_INVALID, "bad template index");
-    if (c->levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
+    if (c->rec.levels_valid < c->L) return fail(SBM_ERR_STATE, "pyramid not built");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = ensure_foff(c, c->stream)) return e;
     const int lc = c->L - 1, T = c->cfg.T[lc], W = c->cols[lc] / T, H = c->rows[lc] / T;
@@ -226,7 +226,7 @@ int sbm_similarity(sbm_ctx* c, int32_t t, uint16_t* dst)
 int sbm_similarity_local(sbm_ctx* c, int32_t level, int32_t t, int32_t cx, int32_t cy, uint16_t* dst)
 {
     if (!c || !dst || t < 0 || t >= c->n_templates || level < 0 || level >= c->L) return fail(SBM_ERR_INVALID, "bad argument");
-    if (c->levels_valid <= level) return fail(SBM_ERR_STATE, "level not resident");
+    if (c->rec.levels_valid <= level) return fail(SBM_ERR_STATE, "level not resident");
     HIP_TRY(hipSetDevice(c->cfg.device_id));
     if (int e = ensure_foff(c, c->stream)) return e;
     HIP_TRY(hipDeviceSynchronize());

@@ -179,12 +179,17 @@ inline void record_build(LevelForms* f, int L, const BuildPlan& b)
     if (b.pack_spread) f[L - 1].bit_planes = true;
 }
 
-// What a match entry point's launches leave current: the build by its plan, then the coarse pass.  enqueue_pyramid and
-// enqueue_coarse record the same two steps as they launch; a call that replays them as a captured graph records them here.
+// ... and the coarse pass of a match entry point that packs the coarsest level's bit planes from its 8 response planes
+// (coarse_packs_planes; pack_bitplanes): they are current beside those
+inline void record_pack(LevelForms& coarsest) { coarsest.bit_planes = true; }
+
+// The two steps in the order a match entry point makes them (enqueue_pyramid, then enqueue_coarse), for the CPU models of a whole
+// call (tests/emu).  The host side records each step where it launches it and keeps a graph's record with the graph
+// (sbm_call_record.h): nothing there derives a record through this.
 inline void record_match(LevelForms* f, const PlanInputs& p, bool one_launch, bool empty_selection)
 {
     record_build(f, p.L, plan_build(p, one_launch, true));
-    if (coarse_packs_planes(p, f[p.L - 1], empty_selection)) f[p.L - 1].bit_planes = true;
+    if (coarse_packs_planes(p, f[p.L - 1], empty_selection)) record_pack(f[p.L - 1]);
 }
 
 // One level's share of a k_build_lm_rows launch: LmLevelArgs::split and ::allty, and the work items (256 per block).

@@ -286,7 +286,10 @@ def test_first_call_template_loop_in_fresh_process(oracle, graph):
     assert r.returncode == 0 and "child ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
 
 
-@pytest.mark.parametrize("refine_bits,coarse", [(None, "auto"), (False, "auto"), (True, "bits"), (None, "bytes"), (True, "block")])
+BATCH_FORMS = [(None, "auto"), (False, "auto"), (True, "bits"), (None, "bytes"), (True, "block")]  # (set_refine_bits, set_coarse_mode)
+
+
+@pytest.mark.parametrize("refine_bits,coarse", BATCH_FORMS)
 def test_forms_after_batch_graph_replay(oracle, ctx_factory, case1, refine_bits, coarse):
     """(c) pipeline depth 2, automatic graphs: the same batch tuple until it replays, then every stage read and the template
     loop against the oracle -- the flags the replay leaves must describe what the captured launches built"""
@@ -337,3 +340,148 @@ def test_forms_after_batch_graph_replay(oracle, ctx_factory, case1, refine_bits,
     assert c[1] == 0 and key(one.cpu().numpy().view(MATCH_DTYPE)[: c[0]]) == key(want)
     assert key(ctx.match_templates(thr)) == key(want)
     pyr.free()
+
+
+# ---- the record a graph replay leaves (csrc/sbm_call_record.h) ----------------------------------------------------------
+RECORD_GEO = (448, 576, 3)  # tests/test_gpu_sparse_list.py's "P": the smallest sparse-eligible two-level T = 4 geometry there
+RECORD_THR = 75.0
+RECORD_NAMES = ["centre", "right", "absent"]
+
+
+@pytest.fixture(scope="module")
+def record_world(oracle):
+    """the frames of RECORD_GEO, their per-frame masks and the oracle's lists without and with them -- computed once, never changed"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_sparse_geometry import cut_frames
+    from test_gpu_sparse_gradient import load_templates
+
+    rows, cols, ch = RECORD_GEO
+    ts = load_templates()
+    fr = cut_frames(oracle, ts, rows, cols, ch)
+    frames = np.stack([fr[n] for n in RECORD_NAMES])
+    masks = np.zeros((len(frames), rows, cols), np.uint8)
+    for b in range(len(frames)):
+        masks[b, 100 + 40 * b:, 90:] = 255  # (cuts a part of the object: another list, not an empty one)
+    want = {}
+    for name, ms in (("plain", [None] * len(frames)), ("masked", masks)):
+        want[name] = []
+        for f, m in zip(frames, ms):
+            p = oracle.Pyramid.build(f, [4, 8], 30.0, mask=m)
+            want[name].append(key(p.match(ts.levels, ts.features, ts.class_idx, ts.template_id, RECORD_THR, n_threads=min(16, os.cpu_count() or 1))))
+            p.free()
+    assert 20 < len(want["plain"][0]) < 4096 and want["plain"][0] != want["plain"][1]
+    assert want["masked"][0] not in ([], want["plain"][0]) and want["masked"][1] not in ([], want["plain"][1])
+    return {"ts": ts, "frames": frames, "masks": masks, "want": want}
+
+
+def call_record(ctx, frames):
+    """everything the accessors tell of what the last call left and launched; level 0's map of the last frame is read last
+    (the read completes a map that a sparse call left in pieces)"""
+    from shape_based_matching_amd import capi
+
+    rec = {("level_build", l): ctx.level_build(l) for l in range(2)}
+    rec.update({"coarse_form": ctx.coarse_form(), ("refine_form", 0): ctx.refine_form(0), "source_form": ctx.source_form(),
+                "sparse_items": ctx.sparse_items(), "sparse_list": ctx.sparse_list()})
+    rec["last map"] = ctx.get_quantized_frame(0, frames - 1).tobytes()
+    with pytest.raises(capi.SbmError):  # ... and the batch had no more frames than these
+        ctx.get_quantized_frame(0, frames)
+    return rec
+
+
+@pytest.mark.parametrize("refine_bits,coarse,variant", [(r, c, "plain") for r, c in BATCH_FORMS] +
+                         [(None, "auto", "empty"), (None, "auto", "masked"), (None, "auto", "any")])
+def test_replay_leaves_the_record_of_the_plain_call(oracle, ctx_factory, record_world, refine_bits, coarse, variant):
+    """The same batch call on two fresh contexts, as plain launches (graph mode 0) and as capture then replay (graph mode 1),
+    with a plain call of one frame in between (a batch of one frame is never captured): afterwards both contexts tell the
+    same of every level's build and current forms, the coarse, refinement and source forms, the sparse launch's selection,
+    items launched and lists, and the last frame's level-0 map -- and the lists are the oracle's.  variant: empty -- no
+    template selected; masked -- a mask per frame (level 0 built whole); any -- the (5, 8) pyramid of k_build_lm_any."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import any_geometry_cases as AG
+    from test_gpu_batch_any_geometry import Batch
+    from test_gpu_sparse_gradient import SPARSE_ON
+
+    if variant == "any":
+        case = AG.case(oracle, "bgr_5_8")
+        T, ts, frames, thr = case.T, case.ts, case.frames[:3], AG.THRS[0]
+        want = [case.want(f, thr) for f in range(3)]
+        assert sum(len(w) for w in want) > 0
+    else:
+        T, ts, frames, thr = (4, 8), record_world["ts"], record_world["frames"], RECORD_THR
+        want = [[]] * 3 if variant == "empty" else record_world["want"]["masked" if variant == "masked" else "plain"]
+    rows, cols = frames[0].shape[:2]
+    recs = []
+    for graph in (False, True):
+        import torch
+
+        ctx = ctx_factory(T=T)
+        ctx.upload_templates(ts)
+        if variant != "any":
+            ctx.set_quantize_mode("stream", 32)  # (a batch this small takes the tile kernel otherwise: no sparse level 0)
+        ctx.set_graph_mode(graph)
+        ctx.set_refine_bits(refine_bits)
+        ctx.set_coarse_mode(coarse)
+        if variant == "empty":
+            ctx.select_templates([])
+        batch, one = Batch(frames), Batch(frames[:1])
+        d_masks = torch.from_numpy(record_world["masks"]).to(torch.device("cuda", 0)) if variant == "masked" else None
+        stride = rows * cols if variant == "masked" else None
+        batch.run(ctx, thr, d_masks, stride)  # graph mode 1: the capture
+        one.run(ctx, thr)                     # plain launches on either context
+        got = batch.run(ctx, thr, d_masks, stride)  # graph mode 1: the replay
+        assert ctx.graph_count() == (1 if graph else 0), graph
+        assert got == want, (graph, [len(g) for g in got])
+        recs.append(call_record(ctx, len(frames)))
+    plain, replay = recs
+    for field in plain:
+        assert replay[field] == plain[field], (field, plain[field] if field != "last map" else "", replay[field] if field != "last map" else "")
+    assert plain["sparse_items"][1] == -1  # working items are counted under profiling only
+    if variant == "plain" and (refine_bits, coarse) == (None, "auto") and SPARSE_ON:
+        assert plain["source_form"] != 0 and plain["sparse_items"][0] != 0 and plain["sparse_items"][2] > 0  # the sparse level-0 path ran
+    if variant in ("masked", "any"):
+        assert plain["source_form"] == 0 and plain["sparse_items"] == (0, -1, 0) and plain["sparse_list"] == (0, 0)
+    if variant == "any":
+        assert plain["level_build", 0][2] == plain["level_build", 1][2] == 2  # k_build_lm_any made both levels
+
+
+def test_template_loop_replay_reports_no_source_pass(oracle, ctx_factory, record_world):
+    """The template loop has no source pass: the replay of its captured graph leaves source_form as the context has it.  A
+    sparse batch (a source pass), the loop captured, a masked batch (level 0 whole: no source pass), the loop replayed."""
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_gpu_batch_any_geometry import CAP, Batch
+    from test_gpu_sparse_gradient import SPARSE_ON
+
+    dev = torch.device("cuda", 0)
+    rows, cols, _ = RECORD_GEO
+    w = record_world
+    ctx = ctx_factory()
+    ctx.upload_templates(w["ts"])
+    ctx.set_quantize_mode("stream", 32)
+    ctx.set_pipeline_depth(2)
+    ctx.set_graph_mode(True)
+    batch = Batch(w["frames"])
+    d_masks = torch.from_numpy(w["masks"]).to(dev)
+    one = torch.zeros(CAP * REC, dtype=torch.uint8, device=dev)
+    one_cnt = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def template_loop():
+        ctx.match_templates_device(RECORD_THR, one.data_ptr(), CAP, one_cnt.data_ptr(), stream=batch.stream.cuda_stream)
+        batch.stream.synchronize()
+        c = one_cnt.cpu().numpy()
+        assert c[1] == 0
+        return key(one.cpu().numpy().view(MATCH_DTYPE)[: c[0]])
+
+    # (the first call with a mask per frame sizes the levels' mask buffers, which drops every captured graph: have it done)
+    assert batch.run(ctx, RECORD_THR, d_masks, rows * cols) == w["want"]["masked"]
+    assert batch.run(ctx, RECORD_THR) == w["want"]["plain"]
+    if SPARSE_ON:
+        assert ctx.source_form() != 0
+    assert template_loop() == w["want"]["plain"][0]  # (frame 0 of the batch: what the forms rebuilt on demand cover)
+    assert batch.run(ctx, RECORD_THR, d_masks, rows * cols) == w["want"]["masked"]
+    assert ctx.source_form() == 0
+    n_graphs = ctx.graph_count()
+    assert template_loop() == w["want"]["masked"][0]
+    assert ctx.graph_count() == n_graphs, "the template loop was captured again instead of replayed"
+    assert ctx.source_form() == 0
