@@ -289,10 +289,18 @@ int sbm_set_refine_order(sbm_ctx* ctx, int32_t order);
 /* Hint: how many batches the caller keeps in flight on this GPU at the same time (through other contexts and
  * streams; bench.py runs three).  1 (default): every launch is sized for its own latency -- all its work items resident
  * at once.  >= 2: launches are sized for throughput -- the row-streaming gradient kernel takes fewer, longer work items
- * (less warm-up work in total; the SIMDs such a launch leaves idle are used by the other batches' kernels): 7.6 % more
- * frames per second on 16 x 1024 x 1024 x 3 batches with three in flight, at 1.3x the latency of a batch alone.
+ * (less warm-up work in total), down to one wave per SIMD of the chip ("Rows per work item"), at about
+ * 1.3x the latency of a batch alone.
  * Results are identical either way. */
 int sbm_set_pipeline_depth(sbm_ctx* ctx, int32_t batches_in_flight);
+
+/* The sparse level-0 gradient launch of a batch call runs a frame of few coarse candidates from a list of its working items
+ * (sbm_get_sparse_list).  rows_per_item: the rows per work item of the grid those lists are made on.  -1 (default): the process
+ * default -- SBM_SPARSE_LIST_HS in the environment, else chosen like the rows per item of a whole-level launch from the frames of
+ * the call when several batches are in flight (sbm_set_pipeline_depth >= 2), and the launch's own rows per item otherwise and
+ * wherever sbm_set_quantize_mode has set those; 0: always the launch's own; > 0: that many (rounded up to even).  A frame without
+ * a list keeps the launch's own grid.  Identical results; a test / tuning knob. */
+int sbm_set_sparse_list_rows(sbm_ctx* ctx, int32_t rows_per_item);
 
 /* Optional second destination for the results of sbm_match_device /
  * sbm_match_templates: every match record (up to the call's cap) and the final
@@ -544,10 +552,12 @@ int sbm_get_source_retention(sbm_ctx* ctx, int32_t out[2]);
  * replayed from a captured graph; with sbm_match's overflow retry, the retry's launch.  launched: the work items of the grid.
  * Waits for the device when a count is still outstanding.  A parity-test accessor. */
 int sbm_get_sparse_items(sbm_ctx* ctx, int32_t out[3]);
-/* {list_mode, slots_per_frame} of the last call's sparse level-0 gradient launch: list_mode 1 when it ran, by slots_per_frame
- * waves per frame, from the per-frame lists of working items that the mark launch leaves (0, 0: a wave per item, each testing
- * itself, or no sparse launch at all). */
-int sbm_get_sparse_list(sbm_ctx* ctx, int32_t out[2]);
+/* {list_mode, slots_per_frame, list_rows} of the last call's sparse level-0 gradient launch: list_mode 1 when it ran, by
+ * slots_per_frame waves per frame, from the per-frame lists of working items that the mark launch leaves (0, 0, 0: a wave per
+ * item, each testing itself, or no sparse launch at all).  list_rows: the rows per work item of the grid the lists are made on,
+ * which a listed frame's items have; a frame without a list, the packed last-strip waves and the number of waves launched keep
+ * the launch's own rows per item (SBM_SPARSE_LIST_HS=0 in the environment: the lists are made on that grid too). */
+int sbm_get_sparse_list(sbm_ctx* ctx, int32_t out[3]);
 /* How the linear memories of `level` were last built: out = {current, form, builder, split, allty, packed}.  current: the
  * buffers that hold the level's current contents, as a bit set: 1 the 8 response planes, 2 the plane of spread bytes, 4 that
  * plane is strip-interleaved, 8 the bit strips, 16 the coarsest level's bit planes.  form: the form of the last build, -1 none

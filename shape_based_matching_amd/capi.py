@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "sbm_get_source_retention",
     "sbm_get_refine_form",
     "sbm_get_sparse_items",
-    "sbm_get_sparse_list",
+    "sbm_get_sparse_list", "sbm_set_sparse_list_rows",
     "sbm_match_batch_device_ptrs",
     "sbm_match_batch_device_planes",
     "sbm_get_level_build",
@@ -326,6 +326,7 @@ def lib() -> C.CDLL:
     L.sbm_train_rotate_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
     L.sbm_train_rotate.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
     L.sbm_set_pipeline_depth.argtypes = [vp, i32]
+    L.sbm_set_sparse_list_rows.argtypes = [vp, i32]
     L.sbm_set_coarse_mode.argtypes = [vp, i32]
     L.sbm_set_refine_order.argtypes = [vp, i32]
     L.sbm_set_refine_bits.argtypes = [vp, i32]
@@ -1013,6 +1014,11 @@ class Context:
         """hint: the caller keeps this many batches in flight on the GPU -> launches are sized for throughput (>= 2)"""
         _check(lib().sbm_set_pipeline_depth(self._h, batches_in_flight))
 
+    def set_sparse_list_rows(self, rows_per_item: int = -1):
+        """rows per work item of the grid the lists of working items of the sparse level-0 gradient launch are made on: -1 the
+        process default, 0 the launch's own rows per item, > 0 that many (sbm.h); identical results"""
+        _check(lib().sbm_set_sparse_list_rows(self._h, rows_per_item))
+
     def graph_count(self) -> int:
         n = C.c_int32(0)
         _check(lib().sbm_graph_count(self._h, C.byref(n)))
@@ -1103,9 +1109,16 @@ class Context:
     def sparse_list(self) -> Tuple[int, int]:
         """(list_mode, slots_per_frame) of the last call's sparse level-0 gradient launch: list_mode 1 when it ran from the lists
         of working items, with slots_per_frame waves per frame; (0, 0) otherwise"""
-        out = np.zeros(2, np.int32)
+        out = np.zeros(3, np.int32)
         _check(lib().sbm_get_sparse_list(self._h, _p(out)))
-        return tuple(int(v) for v in out)
+        return tuple(int(v) for v in out[:2])
+
+    def sparse_list_rows(self) -> int:
+        """rows per work item of the grid the last call's lists of working items were made on (the third value of
+        sbm_get_sparse_list): what a listed frame's items have in the sparse level-0 gradient launch; 0 when it ran from no lists"""
+        out = np.zeros(3, np.int32)
+        _check(lib().sbm_get_sparse_list(self._h, _p(out)))
+        return int(out[2])
 
     def level_build(self, level: int) -> Tuple[int, int, int, int, int, int]:
         """(current, form, builder, split, allty, packed) of ``level``: the buffers that are current as the bit set planes8 1,

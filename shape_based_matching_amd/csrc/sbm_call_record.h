@@ -29,10 +29,11 @@ struct CallRecord {
     int32_t refine_form[LF_MAX_LEVELS][6] = {}; // {kind, LW, order, t8, sparse, slots} of every level's refinement kernel (sbm_get_refine_form)
     LevelBuild level_build[LF_MAX_LEVELS];
     // the sparse level-0 gradient launch: {selection: 0 none, 1 tiles, 2 need rectangles; working items (-1: not counted); items launched};
-    // the count is still on the device (profiling only: never in a captured record); {it ran from item lists, its waves per frame}
+    // the count is still on the device (profiling only: never in a captured record); {it ran from item lists, its waves per frame,
+    // the rows per item of the grid the lists' entries name (the list grid; the launch's own grid where the two are one)}
     int32_t sparse_items[3] = {0, 0, 0};
     bool sparse_items_pending = false;
-    int32_t sparse_list[2] = {0, 0};
+    int32_t sparse_list[3] = {0, 0, 0};
 
     // a call begins to build the pyramid of `frames` frames: no source pass and no sparse launch yet
     void begin_build(int frames)
@@ -41,7 +42,7 @@ struct CallRecord {
         source_form = 0;
         sparse_items[0] = 0, sparse_items[1] = -1, sparse_items[2] = 0;
         sparse_items_pending = false;
-        sparse_list[0] = sparse_list[1] = 0;
+        sparse_list[0] = sparse_list[1] = sparse_list[2] = 0;
     }
     void note_level_build(int l, LmForm f, int builder, int split = 0, int allty = 0) { level_build[l] = LevelBuild{(int32_t)f, builder, split, allty, 0}; }
     void note_coarse_form(int kind, int P, bool wide, int dw) { coarse_form[0] = kind, coarse_form[1] = P, coarse_form[2] = wide ? 1 : 0, coarse_form[3] = dw; }

@@ -20,6 +20,7 @@
 #include "sbm_kernels.h"
 #include "sbm_call_record.h"
 #include "sbm_quantize_stream.h"
+#include "sbm_quantize_rows_plan.h"
 #include "sbm_source_lines.h"
 #include "sbm_frame_ptrs_plan.h"
 #include "sbm_frame_planes_plan.h"

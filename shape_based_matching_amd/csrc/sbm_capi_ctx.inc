@@ -113,6 +113,8 @@ int64_t lm_stride_for(int rows, int cols, int T)
 //                             of SBM_SPARSE_SLOTS waves per frame that run from the lists of working items k_mark_refine_tiles leaves
 //                             (sbm_refine_tiles.h: gradient_rect_list); nothing is allocated for the lists.  SBM_SPARSE_RECTS=0 implies it
 //   SBM_SPARSE_SLOTS=n        waves per frame of that launch (default and at most: the items per frame)
+//   SBM_SPARSE_LIST_HS=n      rows per item of the grid the lists are made on (default: sparse_list_plan's rule); 0: the launch's own
+//                             grid, so that a listed frame's items are those the launch would test itself -- the A/B knob
 //   SBM_QS_SRC_HS=n           rows per work item of the source pass (default 32: 35 row iterations in six groups of 6)
 //   SBM_SOURCE_LINES=0        the source pass always in its strided form (QS_SOURCE), never as k_source_lines (sbm_source_lines.h), which
 //                             otherwise runs wherever the caller's layout admits it (source_lines_ok): the A/B knob of the two forms
@@ -127,6 +129,7 @@ struct Tuning {
     int src_hs = 0;
     bool sparse_list = true;
     int sparse_slots = 0;
+    int sparse_list_hs = -1;
     bool retain_always = false;
 };
 static const Tuning& tuning()
@@ -161,6 +164,7 @@ static const Tuning& tuning()
         k.sparse_rects = k.sparse_gradient && num("SBM_SPARSE_RECTS", 1) != 0;
         k.sparse_list = k.sparse_rects && num("SBM_SPARSE_LIST", 1) != 0;
         k.sparse_slots = std::max(0, num("SBM_SPARSE_SLOTS", 0));
+        k.sparse_list_hs = std::min(4096, std::max(-1, num("SBM_SPARSE_LIST_HS", -1)));
         k.src_hs = std::min(4096, std::max(0, num("SBM_QS_SRC_HS", 0)));
         k.source_lines = num("SBM_SOURCE_LINES", 1) != 0;
         k.retain_always = num("SBM_RETAIN_ALWAYS", 0) != 0;
@@ -334,6 +338,7 @@ struct sbm_ctx {
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     int quantize_mode = 0, quantize_hs = 0; // sbm_set_quantize_mode
+    int sparse_list_rows = -1;              // sbm_set_sparse_list_rows
     int pipeline_depth = 1;                 // sbm_set_pipeline_depth: batches the caller keeps in flight on this GPU
     int local_order = tuning().local_order; // -1 by the planes' size, 0 per-frame slots, 2 one frame-major list (sbm_set_refine_order)
     int coarse_mode = tuning().coarse;      // 0 auto (bit planes), 1 four waves per item, 2 one wave per item, 3 bit planes, 4 byte kernels by launch size (SBM_COARSE: A/B knob)
@@ -617,35 +622,30 @@ int quantize_stream_rows(const sbm_ctx* c, int rows, int cols, const FrameSource
     if (wf || (mode == 1 && !band) || cols < 4 || (cols & 3) || (int64_t)rows * cols >= (int64_t)0x7ff00000) return 0;
     const int64_t strips = (cols + QS_USEFUL - 1) / QS_USEFUL;
     if (force_hs > 0) return (force_hs + 1) & ~1;
-    // The kernel is bound by vector-instruction issue, and a SIMD needs its full set of resident waves (3 at the
-    // BGR kernel's register count, 6 for gray) to hide the scalar bookkeeping and dependency bubbles of each: a launch
-    // takes about  ceil(waves / resident slots) x (hs + 10 halo rows).  Choose the rows per wave that minimise it.
+    // One batch at a time, a SIMD needs its full set of resident waves (3 at the BGR kernel's register count, 6 for gray) to
+    // hide the scalar bookkeeping and dependency bubbles of each: a launch alone on the chip takes about
+    // ceil(waves / resident slots) x (hs + 10 halo rows), and the latency branch below minimises that.
     const int64_t slots = (int64_t)c->n_simd * (ch == 3 ? 3 : 6); // resident waves: 3 per SIMD at the BGR kernel's registers, 6 gray
     // waves per row block: one per strip and frame, except that a narrow last strip is shared by several frames
     const int pack = qs_pack_lanes(rows, cols, src, mask);
     const int64_t per_rb = pack ? (strips - 1) * frames + (frames + 64 / pack - 1) / (64 / pack) : strips * frames;
-    int hs = 0;
-    int64_t best = INT64_MAX;
     // a work item runs whole groups of 7 row iterations (sbm_quantize_stream.h): rows + 10 warm-up / drain, rounded up
+    // (sbm_quantize_rows_plan.h has the arithmetic of both branches)
+    int hs;
     if (c->pipeline_depth >= 2) {
-        // Throughput sizing (the caller keeps several batches in flight on other streams / contexts, sbm_set_pipeline_depth):
-        // what matters is the launch's TOTAL work, waves x row iterations -- the 10 warm-up / drain rows of every work item
-        // are pure overhead, so fewer, longer items -- and not that one launch alone fills every SIMD: the other batches'
-        // kernels take the SIMDs this one leaves idle.  Items longer than 42 iterations stopped paying in the measurement
-        // (profiles/r03_rows_per_item_sweep.txt: 16 x 1024^2 x 3, three batches in flight, us per step: 126.0 with the
-        // latency sizing 24 / 10 rows, 116.4 with 32 / 32, 122.0 with 46 / 46, 137 with 60 / 60).
-        for (int h = 4; h <= 32; h += 2) {
-            const int64_t waves = per_rb * ((out_rows + h - 1) / h);
-            const int64_t cost = waves * ((std::min(h, out_rows) + 10 + 6) / 7 * 7);
-            if (cost <= best) best = cost, hs = h;
-        }
+        // Throughput sizing (the caller keeps several batches in flight on other streams / contexts, sbm_set_pipeline_depth).
+        // The 10 warm-up / drain rows of every work item are pure overhead, so the launch's TOTAL work, waves x row iterations,
+        // asks for few long items, at most 42 iterations (profiles/r03_rows_per_item_sweep.txt) -- but only down to one wave
+        // per SIMD.  The step is no longer bound by vector issue (the whole step issues about 0.6 of the ceiling), the launches
+        // of a call are a chain, and the other batches' kernels do NOT take up what a launch of fewer waves than SIMDs leaves
+        // idle: level 1 of 16 x 1024^2 x 3 at 32 rows is 576 waves of 42 iterations and lasts 62.1 us pipelined, at 18 rows 1044
+        // waves of 28 iterations and 50.5 us, and that alone takes 2.0 us off a step of 73.2; 12 rows lose and 10 rows tie with
+        // 32 (profiles/gradient_item_sizing.txt, sections 1, 4, 5).  So: the least total work among the launches that have a
+        // wave for every SIMD.  A launch that has them at its least-work size keeps that size (level 0 of that batch: 2240 waves at 32 rows).
+        hs = qs_rows_throughput(per_rb, out_rows, c->n_simd);
     } else {
         // Latency sizing: every work item resident at once, as few row iterations as that allows
-        for (int h = 4; h <= 130; h += 2) {
-            const int64_t waves = per_rb * ((out_rows + h - 1) / h);
-            const int64_t cost = ((waves + slots - 1) / slots) * ((std::min(h, out_rows) + 10 + 6) / 7 * 7);
-            if (cost <= best) best = cost, hs = h;
-        }
+        hs = qs_rows_latency(per_rb, out_rows, slots);
     }
     // small launches: the 16 x 64 tiles of k_quantize finish sooner than a few long serial chains
     if (!band && mode != 2 && (int64_t)rows * cols * frames < ((int64_t)4 << 20)) return 0;
@@ -666,7 +666,8 @@ struct QSForm {
     // QS_SPARSE by slots (sparse_list_plan): the frames' lists of working items and the grid they were made for; slots 0: a wave per item
     const int32_t* item_list = nullptr;
     int64_t list_stride = 0;
-    int list_cap = 0, slots = 0, list_hs = 0, list_n_full = 0;
+    // (fixed_hs, list_n_full: the launch's own grid as the plan saw it; list_hs: the rows per item of the grid the lists' entries name)
+    int list_cap = 0, slots = 0, fixed_hs = 0, list_n_full = 0, list_hs = 0;
     // QS_SOURCE: the call counters the work items decide by whether they store the copy, and where the decision is noted (QSArgs)
     const uint32_t* call_enqueued = nullptr;
     const uint32_t* call_executed = nullptr;
@@ -799,18 +800,21 @@ int launch_quantize(sbm_ctx* c, hipStream_t s, const QuantizeLaunch& q)
             }
             if (form->slots > 0) {
                 // (the lists were made for one grid: the one this launch runs)
-                if (form->list_hs != hs || form->list_n_full != (a.pack_lanes ? a.n_strips - 1 : a.n_strips) || !form->need_rects)
+                if (form->fixed_hs != hs || form->list_n_full != (a.pack_lanes ? a.n_strips - 1 : a.n_strips) || !form->need_rects ||
+                    form->list_hs < 2 || (form->list_hs & 1))
                     return fail(SBM_ERR_STATE, "the lists of working items were made for another grid than the sparse gradient launch runs");
                 a.item_list = form->item_list;
                 a.list_stride = form->list_stride;
                 a.list_cap = form->list_cap;
                 a.slots = form->slots;
+                a.list_hs = form->list_hs;
+                a.list_n_rblocks = (rows + form->list_hs - 1) / form->list_hs;
             }
             c->rec.sparse_items[0] = form->need_rects ? 2 : 1;
             c->rec.sparse_items[1] = -1;
             c->rec.sparse_items[2] = a.slots > 0 ? frames * a.slots + quantize_slots_packed(a) : quantize_stream_items(a);
             c->rec.sparse_items_pending = form->item_count != nullptr;
-            c->rec.sparse_list[0] = a.slots > 0, c->rec.sparse_list[1] = a.slots;
+            c->rec.sparse_list[0] = a.slots > 0, c->rec.sparse_list[1] = a.slots, c->rec.sparse_list[2] = a.slots > 0 ? a.list_hs : 0;
         }
         const dim3 g((unsigned)(a.slots > 0 ? quantize_slots_groups(a) : (quantize_stream_items(a) + 3) / 4));
         // (one timing name for all three forms: the launches of the gradient stage)
@@ -1744,8 +1748,10 @@ bool sparse_refine(const sbm_ctx* c)
 // workgroup whose flag is 0 returns at once).  The unflagged tiles keep whatever an earlier call left: nothing reads them.
 // The grid of the sparse gradient launch of a call of `frames` frames and how many waves per frame run it from the lists of
 // working items: SBM_SPARSE_SLOTS or the default, at most the items of a frame.  slots 0: no lists, a wave per item.
+// hs, n_full, n_rblocks: the launch's own grid, the FIXED grid, which a frame without a list walks, the packed waves run and the
+// waves launched follow.  list_hs, list_n_rblocks: the LIST grid, the one k_mark_refine_tiles tests and lists a frame's items on.
 struct SparseListPlan {
-    int slots = 0, hs = 0, n_full = 0, n_rblocks = 0;
+    int slots = 0, hs = 0, n_full = 0, n_rblocks = 0, list_hs = 0, list_n_rblocks = 0;
 };
 constexpr int SPARSE_SLOTS_DEFAULT = INT_MAX; // the items per frame (profiles/sparse_list.txt, section 5)
 SparseListPlan sparse_list_plan(const sbm_ctx* c, const FrameSource& src)
@@ -1761,6 +1767,19 @@ SparseListPlan sparse_list_plan(const sbm_ctx* c, const FrameSource& src)
     if (per_frame < 1 || per_frame > c->items_cap) return p;
     p.hs = hs, p.n_full = n_full, p.n_rblocks = n_rblocks;
     p.slots = (int)std::min<int64_t>(per_frame, tuning().sparse_slots > 0 ? tuning().sparse_slots : SPARSE_SLOTS_DEFAULT);
+    // The list grid.  Only a frame of few candidates has a list (at most 256, one workgroup of the mark launch), and its working
+    // items follow the candidates' need rectangles: a few objects, each about a strip wide.  The estimate of the waves that work
+    // in a launch of listed frames is therefore ONE strip per frame and row block, frames x ceil(rows / h) -- what works if
+    // objects cover every row; fewer work where they do not, and the rule then errs towards longer items.  With that for the
+    // waves, the rule of the whole-level launches (qs_rows_throughput; several batches in flight only), never longer items than
+    // the fixed grid's.  The finer grid must fit the lists' room as well.
+    // A context whose rows per item the caller has set (sbm_set_quantize_mode) has that one grid, unless the list grid is set too.
+    const int set = c->sparse_list_rows >= 0 ? c->sparse_list_rows : tuning().sparse_list_hs;
+    int list_hs = hs;
+    if (set > 0) list_hs = (set + 1) & ~1;
+    else if (set < 0 && !c->quantize_hs && c->pipeline_depth >= 2) list_hs = std::min(hs, qs_rows_throughput(src.frames, rows, c->n_simd));
+    if (list_hs < 2 || (int64_t)n_full * ((rows + list_hs - 1) / list_hs) > c->items_cap) list_hs = hs;
+    p.list_hs = list_hs, p.list_n_rblocks = (rows + list_hs - 1) / list_hs;
     return p;
 }
 
@@ -1777,7 +1796,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
         ml.items = c->d_items.as<int32_t>();
         ml.stride = refine_list_stride(c->items_cap);
         ml.capacity = (int32_t)c->items_cap;
-        ml.n_full = lp.n_full, ml.n_rblocks = lp.n_rblocks, ml.hs = lp.hs, ml.useful = QS_USEFUL;
+        ml.n_full = lp.n_full, ml.n_rblocks = lp.list_n_rblocks, ml.hs = lp.list_hs, ml.useful = QS_USEFUL; // (the list grid)
     }
     SBM_LAUNCH(c, "k_mark_refine_tiles", k_mark_refine_tiles, dim3(4, frames), dim3(256), 0, s, c->d_cands.as<Cand>(), c->d_counters.as<int32_t>(),
                (int)c->cand_cap, c->rows[0], c->cols[0], T, W, H, c->d_fext.as<uint32_t>(), c->L, 0, c->d_tiles.as<uint8_t>(), n_tiles, rects, n_bands, ml);
@@ -1792,7 +1811,7 @@ int enqueue_sparse_strips(sbm_ctx* c, hipStream_t s, int frames)
             form.item_list = ml.items;
             form.list_stride = ml.stride;
             form.list_cap = ml.capacity;
-            form.slots = lp.slots, form.list_hs = lp.hs, form.list_n_full = lp.n_full;
+            form.slots = lp.slots, form.fixed_hs = lp.hs, form.list_n_full = lp.n_full, form.list_hs = lp.list_hs;
         }
         if (c->profiling && c->d_sparse_items.p) { // (no capture while profiling: graph_wanted)
             HIP_TRY(hipMemsetAsync(c->d_sparse_items.p, 0, sizeof(int32_t), s));
@@ -2041,7 +2060,8 @@ GraphKey graph_key(const sbm_ctx* c, const MatchCall& m, int kind)
     // (a batch call whose plan makes level 0's map sparsely records other launches than a whole one at the same geometry)
     key.sparse_grad = kind > 0 && plans_sparse_gradient(c, m.src, m.mask, nullptr, false);
     key.sparse_rects = key.sparse_grad && tuning().sparse_rects && c->d_rects.p != nullptr;
-    key.sparse_slots = key.sparse_rects ? sparse_list_plan(c, sparse_gradient_frames(c, m.src)).slots : 0;
+    const SparseListPlan lp = key.sparse_rects ? sparse_list_plan(c, sparse_gradient_frames(c, m.src)) : SparseListPlan{};
+    key.sparse_slots = lp.slots, key.sparse_list_hs = lp.slots > 0 ? lp.list_hs : 0;
     return key;
 }
 

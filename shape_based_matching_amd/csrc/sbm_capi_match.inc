@@ -366,6 +366,14 @@ int sbm_set_quantize_mode(sbm_ctx* c, int32_t mode, int32_t rows_per_wave)
     return 0;
 }
 
+int sbm_set_sparse_list_rows(sbm_ctx* c, int32_t rows_per_item)
+{
+    if (!c || rows_per_item < -1 || rows_per_item > 4096) return fail(SBM_ERR_INVALID, "bad rows per listed work item");
+    c->sparse_list_rows = rows_per_item;
+    c->drop_graphs(); // captured launches hold the old grid of the lists
+    return 0;
+}
+
 int sbm_set_coarse_mode(sbm_ctx* c, int32_t mode)
 {
     if (!c || mode < 0 || mode > 4) return fail(SBM_ERR_INVALID, "bad coarse mode");
@@ -911,7 +919,7 @@ int sbm_get_sparse_items(sbm_ctx* c, int32_t out[3])
     return 0;
 }
 
-int sbm_get_sparse_list(sbm_ctx* c, int32_t out[2])
+int sbm_get_sparse_list(sbm_ctx* c, int32_t out[3])
 {
     if (!c || !out) return fail(SBM_ERR_INVALID, "null argument");
     memcpy(out, c->rec.sparse_list, sizeof c->rec.sparse_list);

@@ -112,6 +112,7 @@ struct GraphKey {
     bool sparse_grad = false;    // the call's plan makes level 0's map sparsely (another launch sequence at the same geometry)
     bool sparse_rects = false;   // ... with its work items taken from the record of need rectangles (other kernel arguments)
     int sparse_slots = 0;        // ... by that many waves per frame from the lists of working items, 0: a wave per item (another grid)
+    int sparse_list_hs = 0;      // ... the lists made on a grid of that many rows per item (other arguments of two launches)
 };
 
 inline bool operator==(const GraphKey& a, const GraphKey& b)
@@ -119,7 +120,7 @@ inline bool operator==(const GraphKey& a, const GraphKey& b)
     return a.src == b.src && a.mask == b.mask && a.rows == b.rows && a.cols == b.cols && a.thr_bits == b.thr_bits && a.out == b.out &&
            a.cap == b.cap && a.count == b.count && a.mirror_out == b.mirror_out && a.mirror_count == b.mirror_count && a.kind == b.kind &&
            a.forms_signature == b.forms_signature && a.sparse_grad == b.sparse_grad && a.sparse_rects == b.sparse_rects &&
-           a.sparse_slots == b.sparse_slots;
+           a.sparse_slots == b.sparse_slots && a.sparse_list_hs == b.sparse_list_hs;
 }
 
 } // namespace sbm

@@ -126,6 +126,11 @@ struct QSArgs {
     int64_t list_stride;
     int32_t list_cap;         // entries a frame's list has room for: a larger count is cut to it
     int32_t slots;
+    // The lists may be made on a row grid of their own, the LIST grid: list_hs rows per item, list_n_rblocks = ceil(rows / list_hs)
+    // row blocks, an entry's rb a row block of that grid (list_hs 0: the lists are on the launch's grid, hs and n_rblocks).  A
+    // listed frame has few working items, and those are better short (sbm_quantize_rows_plan.h); a frame without a list, whose
+    // every item may work, keeps the launch's grid, and so do the packed waves and the number of waves launched.
+    int32_t list_hs, list_n_rblocks;
     // QS_SOURCE (and k_source_lines): the two call counters that decide whether a work item stores its rows of the retained copy
     // (source_pass_retains, sbm_source_lines_plan.h) -- two words of device memory: the host's count of calls enqueued as an
     // earlier launch last read it from host memory, and the calls executed (sbm_lm_kernels.h, CallWord).  The addresses never
@@ -388,8 +393,9 @@ __device__ __forceinline__ void quantize_source_wave(const QSArgs& a, int strip,
 // One work item: strip `strip`, output rows [rb*hs, min(rb*hs+hs, rows)), frame `frame`.
 // nseg == 0: the whole wave is strip `strip` of frame `frame`; nseg > 0: packed last strip of frames frame .. frame+nseg-1
 // x_listed >= 0 (QS_SPARSE): the item comes from a list of working items -- it works, and its strip begins at that column
+// hs_listed > 0 (with x_listed): rb counts row blocks of that many rows, the list grid's, instead of a.hs
 template <int CH, int STAGE = QS_WHOLE, bool PTRS = false, bool PLANES = false>
-__device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0, int x_listed = -1)
+__device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip, int rb, int frame, int nseg = 0, int x_listed = -1, int hs_listed = 0)
 {
     using namespace wv;
     static_assert(!PLANES || (PTRS && CH == 3 && STAGE != QS_SPARSE), "the plane form is a table form of three channels");
@@ -435,9 +441,10 @@ __device__ __forceinline__ void quantize_stream_wave(const QSArgs& a, int strip,
     // Every work item owns exactly min(hs, row_hi - row_lo) output rows: the last row block is moved up to end at the
     // launch's last row (it then recomputes a few rows of the block above -- the same bytes, stored twice).  All items of a launch run
     // the same number of row iterations, in whole groups of 7 (see the row loop).
-    int R0 = a.row_lo + rb * a.hs;
-    if (R0 + a.hs > a.row_hi) R0 = a.row_hi - a.row_lo > a.hs ? a.row_hi - a.hs : a.row_lo;
-    const int R1 = R0 + a.hs < a.row_hi ? R0 + a.hs : a.row_hi;
+    const int hs = STAGE == QS_SPARSE && x_listed >= 0 && hs_listed > 0 ? hs_listed : a.hs; // (wave-uniform)
+    int R0 = a.row_lo + rb * hs;
+    if (R0 + hs > a.row_hi) R0 = a.row_hi - a.row_lo > hs ? a.row_hi - hs : a.row_lo;
+    const int R1 = R0 + hs < a.row_hi ? R0 + hs : a.row_hi;
     const int cb = x_first - QS_HALO_LANES * QS_LANE_PX; // column of lane 0, pixel 0
     const uint8_t* img = PLANES ? qs_table_entry(a.img, 3 * frame) : PTRS ? qs_table_entry(a.img, frame) : a.img + (int64_t)frame * a.img_fs;
     const uint8_t* img1 = PLANES ? qs_table_entry(a.img, 3 * frame + 1) : img; // plane form: channels 1 and 2
@@ -948,15 +955,17 @@ __device__ __forceinline__ void quantize_stream_slot_wave(const QSArgs& a, int g
     // takes everything else from the arguments again (qs_per_item: as far as the compiler knows, a new value per trip).
     for (int e = j; e < n; e += a.slots) {
         const int fr = qs_per_item(frame, e), nf = qs_per_item(a.n_strips, e) - (a.pack_lanes ? 1 : 0);
-        int k, rb, x = -1;
-        if (listed) {
+        int k, rb, x = -1, lhs = 0;
+        if (listed) { // an entry is an item of the list grid
             const int32_t* ent = a.item_list + (int64_t)fr * a.list_stride + RT_LIST_HEAD + (int64_t)RT_LIST_ENTRY * e;
             k = ent[0], rb = ent[1], x = ent[2];
-            if (k < 0 || k >= nf || rb < 0 || rb >= a.n_rblocks || x < 0 || x >= a.cols) continue; // no item of this launch
+            lhs = qs_per_item(a.list_hs, e);
+            const int n_rb = lhs > 0 ? a.list_n_rblocks : a.n_rblocks;
+            if (k < 0 || k >= nf || rb < 0 || rb >= n_rb || x < 0 || x >= a.cols) continue; // no item of this launch
         } else {
             rb = e / nf, k = e - rb * nf;
         }
-        quantize_stream_wave<CH, QS_SPARSE>(a, k, rb, fr, 0, x);
+        quantize_stream_wave<CH, QS_SPARSE>(a, k, rb, fr, 0, x, lhs);
     }
 }
 
